@@ -34,7 +34,8 @@ under torchrun (WORLD_SIZE set) it just runs as rank RANK.  EBO_BENCH_REHEARSE=1
 N > 1 code path on a box with fewer GPUs than ranks (all ranks share the visible GPUs, collectives
 over gloo) and says so in the JSON line — never a scaling measurement.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0; `ms_per_step` in it is the wall time of one of the K timed steps.
+`--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import importlib
@@ -494,6 +495,36 @@ def bucket_rows(ev, cfg, row_b, row_e):
     return ev[sel[order]], counts
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files of a run together, written as float64
+
+
+def dump_outputs(out_dir, arrays, rank, world, torch):
+    """--dump-outputs: `arrays` (name -> device tensor or numpy array, what the timed path's last step left) as
+    out_dir/<name>.npy in float64, so that two builds can be compared output for output on the same inputs.  With
+    N > 1 every rank writes what it holds, its file names end in _rank<r>, and the ranks share the budget.  The budget
+    is filled smallest array first, each taking at most an equal share of what is left: an array within its share is
+    written whole, a larger one as the elements at seeded random flat indices (sorted; the same indices on every run
+    of the same arguments), flattened.  Returns the manifest that goes into the JSON line."""
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = {name: int(a.numel() if hasattr(a, "numel") else a.size) for name, a in arrays.items()}
+    left, keep = DUMP_BUDGET_BYTES // 8 // world, {}
+    for i, name in enumerate(sorted(sizes, key=lambda nm: (sizes[nm], nm))):
+        keep[name] = min(sizes[name], left // (len(sizes) - i))
+        left -= keep[name]
+    manifest = {}
+    for k, name in enumerate(sorted(arrays)):
+        a, n = arrays[name], sizes[name]
+        shape = list(a.shape)
+        if keep[name] < n:
+            idx = np.unique(np.random.default_rng(1000 + k).integers(0, n, keep[name]))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device) if hasattr(a, "numel") else idx]
+        a = a.double().cpu().numpy() if hasattr(a, "numel") else np.asarray(a, dtype=np.float64)
+        fname = name + ("_rank%d" % rank if world > 1 else "") + ".npy"
+        np.save(os.path.join(out_dir, fname), a)
+        manifest[fname] = {"shape": shape, "sampled_elements": int(a.size) if keep[name] < n else None}
+    return manifest
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -525,6 +556,9 @@ def main():
                     help="untimed steps BEFORE the W warm-up steps that bring the GPU's clocks up (the same count on every "
                          "rank: steps may hold collectives).  profiles/r04_step_loop.txt: the first ~10 ms of kernels after the "
                          "idle set-up phase run ~6 %% slower, whatever launches them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, at most 64 MB "
+                         "in all: a seeded sample of larger outputs); the inputs are the same on every run of the same arguments")
     args = ap.parse_args()
     if args.replicas:
         args.workload = "replicas"
@@ -544,6 +578,8 @@ def main():
         args.steps = {"eval": 200, "c4": 20, "replicas": 50}[workload]
     if args.warmup is None:
         args.warmup = {"eval": 10, "c4": 2, "replicas": 3}[workload]
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.windows is None:
         args.windows = 128 if args.config >= 3 else 256  # (C3: 64 / 128 / 256 windows per launch = 26.1 / 27.2 / 27.3 Gev/s)
     extras_on = rank == 0 and world == 1 and not args.no_extras and workload == "eval"
@@ -803,7 +839,7 @@ def main():
                 T["step"] += 1
                 T["mine"] = pts  # the points this step added to the rank's tracks
                 allp, counts = comm.allgather_tracks(exchange, ctx, pts)
-                T["gathered"], T["counts"] = len(allp), counts
+                T["gathered"], T["counts"], T["all"] = len(allp), counts, allp
 
         units_per_step = float(S["active"])
         kernel_fn = eval_step
@@ -904,6 +940,22 @@ def main():
     dt = time.perf_counter() - t0
     dt = comm.reduce(dt, "MAX")
     HEADLINE_DT = dt  # the line at the end uses THIS name: nothing the extras compute may shadow the timed region
+    # what the last timed step computed, before anything below launches on the same buffers (the extras' value-only
+    # evaluations overwrite d_out)
+    dumped = None
+    if args.dump_outputs:
+        if workload == "c4":
+            outs = {"flows_gathered": S["d_all"], "solver_stats": S["d_stats"]}
+            if S.get("band") is not None:
+                outs["count_image_own_rows"] = S["B"]["img_own"]
+            elif S["d_img"] is not None:
+                outs["count_image"] = S["d_img"]
+        else:
+            outs = {"residual_jacobian": S["d_out"].view(args.windows, S["P"], 3)}
+            if tracks_state is not None:
+                tr = tracks_state["all"]
+                outs["tracks_gathered"] = np.stack([tr[f].astype(np.float64) for f in ("id", "t_us", "x", "y")], 1)
+        dumped = dump_outputs(args.dump_outputs, outs, rank, world, torch)
     total_units = comm.reduce(units_per_step, "SUM")
     comm_total_events = comm.reduce(float(S["n_events"]), "SUM") if workload == "c4" else None
     band_counted, band_full = None, None
@@ -1281,6 +1333,8 @@ def main():
             "cpu_baseline": base,
             "extras": extras,
         }
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": dumped}
         if rehearse or (comm.active and world == 1):
             line["rehearsal"] = "N > 1 code path on shared GPU(s) over %s: not a scaling measurement" % (comm.backend,)
         print(json.dumps(line), flush=True)

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <vector>
 #include <memory>
+#include <string>
 
 #include "../../event-based-odomety_amd/include/feature_tracker/contrast_functor.h"
 #include "../../event-based-odomety_amd/include/feature_tracker/feature_detector.h"
@@ -30,6 +31,14 @@ static int g_fail = 0;
 		}                                                                   \
 	} while (0)
 #define EXPECT_NEAR(a, b, tol) EXPECT_TRUE(std::fabs((a) - (b)) <= (tol))
+
+// Scratch files go under $TMPDIR (the pytest driver passes a directory of the test's own), /tmp without it: a fixed
+// name in a shared /tmp belongs to whichever user wrote it first.
+static std::string scratchDir()
+{
+	const char* dir = std::getenv("TMPDIR");
+	return dir && *dir ? dir : "/tmp";
+}
 
 static unsigned long long g_state = 88172645463325252ull;
 static unsigned rnd()
@@ -305,8 +314,8 @@ int main()
 
 	// ---- EventPump: events.txt -> reader -> evaluator's window rule -> detector --------------
 	{
-		const char* path = "/tmp/ebo_facade_events.txt";
-		FILE* fp = std::fopen(path, "w");
+		const std::string path = scratchDir() + "/ebo_facade_events.txt";
+		FILE* fp = std::fopen(path.c_str(), "w");
 		for (const auto& s : samples)
 		{
 			std::fprintf(fp, "%.9f %d %d %d\n", s.timestamp.count() * 1e-6, s.value.point.x, s.value.point.y,
@@ -318,8 +327,9 @@ int main()
 		EXPECT_TRUE(read[777].value.point.x == samples[777].value.point.x);
 		EXPECT_TRUE(read[777].value.sign == samples[777].value.sign);
 		// the packed binary sidecar gives the same events back without parsing
-		tools::EventPump::writeEventsBin("/tmp/ebo_facade_events.ebo", read);
-		const auto readBin = tools::EventPump::readEventsBin("/tmp/ebo_facade_events.ebo");
+		const std::string pathBin = scratchDir() + "/ebo_facade_events.ebo";
+		tools::EventPump::writeEventsBin(pathBin, read);
+		const auto readBin = tools::EventPump::readEventsBin(pathBin);
 		bool sameBin = readBin.size() == read.size();
 		for (size_t i = 0; i < read.size() && sameBin; ++i)
 		{

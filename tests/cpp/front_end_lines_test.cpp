@@ -21,6 +21,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iomanip>
@@ -50,6 +51,14 @@ static int g_fail = 0;
 	} while (0)
 #define EXPECT_EQ(a, b) EXPECT_TRUE((a) == (b))
 #define ASSERT_EQ(a, b) EXPECT_TRUE((a) == (b))
+
+// Scratch files go under $TMPDIR (the pytest driver passes a directory of the test's own), /tmp without it: a fixed
+// name in a shared /tmp belongs to whichever user wrote it first.
+static std::string scratchDir()
+{
+	const char* dir = std::getenv("TMPDIR");
+	return dir && *dir ? dir : "/tmp";
+}
 
 // Two flavours of this program: without OpenCV on the include path the driver below spells the two OpenCV types of the
 // front end's interface with the facade's stand-ins; built with -Istubs_opencv (test-only declarations of cv::Size_,
@@ -131,7 +140,7 @@ static std::unordered_map<tracker::TrackId, Landmark> landmarksOf(const tracker:
 struct WindowRule
 {
 	FrameSize sensor = {240, 180};
-	std::string resultsDir = "/tmp";
+	std::string resultsDir = scratchDir();
 	bool draw = false;
 	uint32_t periodMicros = 300000;  // the evaluator's compensationFrequencyTime default
 	uint32_t eventCap = 15000;       // compensationFrequencyEvents
@@ -460,7 +469,7 @@ int main(int argc, char** argv)
 	// ---- the evaluator loop: ONE FeatureDetector against the former pair ----------------------------
 	{
 		WindowRule ep;
-		ep.resultsDir = "/tmp";
+		ep.resultsDir = scratchDir();
 		ep.eventCap = 6000;
 		ep.periodMicros = 4000000000u;  // windows by event count only
 		FrontEndDriver evaluator(ep);
@@ -579,7 +588,7 @@ int main(int argc, char** argv)
 		// ~FrontEndDriver: preExit, trajectory.txt, final_cost.txt
 	}
 	{
-		std::ifstream costs("/tmp/final_cost.txt"), traj("/tmp/trajectory.txt");
+		std::ifstream costs(scratchDir() + "/final_cost.txt"), traj(scratchDir() + "/trajectory.txt");
 		std::string line;
 		size_t nCosts = 0, nTraj = 0;
 		while (std::getline(costs, line))

@@ -7,6 +7,7 @@
 //       points each, written as "id ts x y" and parsed back within EXPECT_FLOAT_EQ
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <fstream>
 #include <tuple>
 #include <utility>
@@ -25,6 +26,14 @@ static int g_fail = 0;
 			++g_fail;                                                  \
 		}                                                              \
 	} while (0)
+
+// Scratch files go under $TMPDIR (the pytest driver passes a directory of the test's own), /tmp without it: a fixed
+// name in a shared /tmp belongs to whichever user wrote it first.
+static std::string scratchDir()
+{
+	const char* dir = std::getenv("TMPDIR");
+	return dir && *dir ? dir : "/tmp";
+}
 
 using Stamp = std::pair<common::timestamp_t, tools::EventType>;
 
@@ -103,7 +112,7 @@ int main(int argc, char** argv)
 			}
 			patches.push_back(patch);
 		}
-		const std::string out = "/tmp/ebo_tools_test_trajectory.txt";
+		const std::string out = scratchDir() + "/ebo_tools_test_trajectory.txt";
 		tools::saveFeaturesTrajectory(patches, out);
 		std::ifstream file(out);
 		EXPECT_TRUE(static_cast<bool>(file));

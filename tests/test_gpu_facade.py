@@ -9,6 +9,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CPP = os.path.join(HERE, "cpp")
 
 
+def scratch_env(tmp_path):
+    """The environment of a C++ test that writes files: its scratch files go to the test's own directory
+    ($TMPDIR), not to fixed names in the shared /tmp."""
+    return dict(os.environ, TMPDIR=str(tmp_path))
+
+
 def test_facade_compiles_against_the_abi(ebo, orc):
     """CPU: the facade headers + test program compile and link against libebo_hip.so."""
     ebo.lib()
@@ -17,10 +23,11 @@ def test_facade_compiles_against_the_abi(ebo, orc):
 
 
 @pytest.mark.gpu
-def test_facade_against_oracle_on_gpu(ebo, orc):
+def test_facade_against_oracle_on_gpu(ebo, orc, tmp_path):
     ebo.lib()
     subprocess.check_call(["make", "-s", "-C", CPP, "facade_test"])
-    out = subprocess.run([os.path.join(CPP, "facade_test")], capture_output=True, text=True, timeout=600)
+    out = subprocess.run([os.path.join(CPP, "facade_test")], capture_output=True, text=True, timeout=600,
+                         env=scratch_env(tmp_path))
     print(out.stdout[-3000:], out.stderr[-2000:])
     assert out.returncode == 0, out.stdout[-3000:]
     assert "all passed" in out.stdout
@@ -75,7 +82,7 @@ def test_reference_construction_lines_solve_like_ebo_solve(ebo):
     assert "all passed" in out.stdout
 
 
-def test_reference_replayer_and_trajectory_scenarios(ebo):
+def test_reference_replayer_and_trajectory_scenarios(ebo, tmp_path):
     """CPU: tools/replayer/test/replayer_test.cpp:67-125 (nextTest, nextImageTest, resetTest on the
     reference's own two data files) through tools::StreamPump, and
     tools/evaluator/test/evaluator_test.cpp:19-83 (saveTrajectoryTest) through
@@ -83,7 +90,7 @@ def test_reference_replayer_and_trajectory_scenarios(ebo):
     ebo.lib()
     subprocess.check_call(["make", "-s", "-C", CPP, "tools_test"])
     out = subprocess.run([os.path.join(CPP, "tools_test"), os.path.join(HERE, "golden", "replayer")],
-                         capture_output=True, text=True, timeout=120)
+                         capture_output=True, text=True, timeout=120, env=scratch_env(tmp_path))
     assert out.returncode == 0 and "all passed" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
 
 
@@ -102,13 +109,14 @@ def test_front_end_lines_compile_and_host_subset(ebo):
 
 
 @pytest.mark.gpu
-def test_front_end_lines_run_like_the_pair(ebo):
+def test_front_end_lines_run_like_the_pair(ebo, tmp_path):
     """The evaluator's event loop through the one FeatureDetector (tracker + compensation on one device
     context): patches, flows and both images bit-equal to the stand-alone TrackedPatches + FeatureDetector
     pair; the newImage life cycle through FrontEndHooks; Keyframe over getPatches()."""
     ebo.lib()
     subprocess.check_call(["make", "-s", "-C", CPP, "front_end_lines_test"])
-    out = subprocess.run([os.path.join(CPP, "front_end_lines_test")], capture_output=True, text=True, timeout=900)
+    out = subprocess.run([os.path.join(CPP, "front_end_lines_test")], capture_output=True, text=True, timeout=900,
+                         env=scratch_env(tmp_path))
     print(out.stdout[-4000:], out.stderr[-2000:])
     assert out.returncode == 0, out.stdout[-4000:]
     assert "all passed" in out.stdout
@@ -128,10 +136,11 @@ def test_front_end_lines_with_opencv_types_compile_and_host_subset(ebo):
 
 
 @pytest.mark.gpu
-def test_front_end_lines_with_opencv_types_run_like_the_pair(ebo):
+def test_front_end_lines_with_opencv_types_run_like_the_pair(ebo, tmp_path):
     ebo.lib()
     subprocess.check_call(["make", "-s", "-C", CPP, "front_end_lines_opencv_test"])
-    out = subprocess.run([os.path.join(CPP, "front_end_lines_opencv_test")], capture_output=True, text=True, timeout=900)
+    out = subprocess.run([os.path.join(CPP, "front_end_lines_opencv_test")], capture_output=True, text=True, timeout=900,
+                         env=scratch_env(tmp_path))
     print(out.stdout[-4000:], out.stderr[-2000:])
     assert out.returncode == 0, out.stdout[-4000:]
     assert "all passed" in out.stdout
