@@ -893,6 +893,50 @@ class Context:
     def comm_destroy(self):
         self._check(lib().ebo_comm_destroy(self._h))
 
+    # -- image front end (FeatureDetector::newImage without OpenCV) -----------
+    def _image(self, image):
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        assert img.shape == (self.params.image_h, self.params.image_w), img.shape
+        return img
+
+    def image_gradients(self, image):
+        """getLogImage + getGradients: uint8 [h][w] -> (grad_x, grad_y), float64 [h][w]."""
+        img = self._image(image)
+        gx = np.zeros(img.shape)
+        gy = np.zeros(img.shape)
+        self._check(lib().ebo_image_gradients(self._h, _vp(img), _dp(gx), _dp(gy)))
+        return gx, gy
+
+    def good_features(self, image, mask=None, max_corners=100, quality_level=0.01, min_distance=10.0, block_size=3,
+                      harris_k=0.04):
+        """goodFeaturesToTrack in Harris mode: -> float32 [n][2] corners (x, y), in selection order."""
+        img = self._image(image)
+        m = None if mask is None else self._image(mask)
+        out = np.zeros((int(max_corners), 2), dtype=np.float32)
+        n = C.c_int()
+        self._check(lib().ebo_good_features(self._h, _vp(img), _vp(m) if m is not None else None, int(max_corners),
+                                            C.c_double(quality_level), C.c_double(min_distance), int(block_size),
+                                            C.c_double(harris_k), _vp(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def lk_add_image(self, image):
+        """FlowEstimator::addImage: pyramid + derivatives on the device; the last two images are kept."""
+        img = self._image(image)
+        self._check(lib().ebo_lk_add_image(self._h, _vp(img)))
+
+    def lk_track(self, prev_xy, win=(21, 21), max_level=3, max_count=30, epsilon=0.01, min_eig_threshold=1e-4):
+        """calcOpticalFlowPyrLK from the older image to the newer one: -> (next_xy float32 [n][2], status uint8 [n],
+        err float32 [n])."""
+        pts = np.ascontiguousarray(prev_xy, dtype=np.float32).reshape(-1, 2)
+        n = len(pts)
+        nxt = np.zeros((max(n, 1), 2), dtype=np.float32)
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        err = np.zeros(max(n, 1), dtype=np.float32)
+        self._check(lib().ebo_lk_track(self._h, n, _vp(pts), _vp(nxt), _vp(st), _vp(err), int(win[0]), int(win[1]),
+                                       int(max_level), int(max_count), C.c_double(epsilon),
+                                       C.c_double(min_eig_threshold)))
+        return nxt[:n], st[:n], err[:n]
+
     # -- timing --------------------------------------------------------------
     def timer_begin(self):
         self._check(lib().ebo_timer_begin(self._h))

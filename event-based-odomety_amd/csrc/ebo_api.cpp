@@ -1619,6 +1619,12 @@ void ebo_destroy(ebo_ctx* c)
 	hipFree(c->d_chunk_hist);
 	hipFree(c->d_field);
 	hipFree(c->d_tvf);
+	hipFree(c->d_fe_lut);
+	hipFree(c->d_fe);
+	hipFree(c->d_fe_pyr[0]);
+	hipFree(c->d_fe_pyr[1]);
+	hipFree(c->d_fe_lv);
+	hipFree(c->d_fe_pts);
 	if (c->ev0) hipEventDestroy(c->ev0);
 	if (c->ev1) hipEventDestroy(c->ev1);
 	if (c->own_stream && c->stream)

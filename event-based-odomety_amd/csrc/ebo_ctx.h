@@ -106,6 +106,17 @@ struct ebo_ctx
 	int field_nfixed = 0;
 	void* d_tvf = nullptr;           // workspace of ebo_interpolate_motion_field
 	size_t tvf_cap = 0;
+	double* d_fe_lut = nullptr;      // image front end: the 256 log-image values of ebo_image_gradients
+	void* d_fe = nullptr;            // its per-call workspace (image, mask, outputs, Harris response, candidate lists)
+	size_t fe_cap = 0;
+	char* d_fe_pyr[2] = {};          // pyramids + derivatives of the last two ebo_lk_add_image images
+	FeLevel* d_fe_lv = nullptr;      // their level table (both have the image's shape)
+	std::vector<FeLevel> fe_lv;
+	size_t fe_pyr_bytes = 0;
+	int fe_newer = 0;                // slot of the newer image
+	int fe_images = 0;               // images added, up to 2
+	void* d_fe_pts = nullptr;        // ebo_lk_track's points, status and errors
+	size_t fe_pts_cap = 0;
 	void* comm = nullptr;            // ncclComm_t of ebo_comm_init
 	int comm_rank = 0, comm_size = 1;
 	uint64_t* d_comm_cnt = nullptr;  // [nranks + 2] counts / flags of the exchange (allocated by ebo_comm_init)

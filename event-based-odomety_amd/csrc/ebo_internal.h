@@ -473,4 +473,33 @@ struct RouteLaunch
 };
 int launch_route(const RouteLaunch& L, void* stream);
 
+// Image front end of FeatureDetector::newImage (ebo_frontend.inc, ebo_frontend.cpp).
+constexpr int kFeLevels = 8;         // pyramid levels kept per image (ebo.h: max_level <= 7)
+constexpr int kFeMaxWindow = 1024;   // LK window pixels (64 lanes x 16)
+constexpr int kFeMaxCornersLds = 8192;  // ebo_good_features' max_corners limit
+constexpr int kFeSortLds = 4096;     // candidate lists up to this length are sorted in LDS
+struct FeLevel
+{
+	int w, h;
+	unsigned long long img;  // byte offset of the level's image in its pyramid allocation
+	unsigned long long der;  // byte offset of its short2 (Ix, Iy) derivatives
+};
+int launch_fe_gradients(const uint8_t* d_img, const double* d_lut, int w, int h, double* d_gx, double* d_gy,
+						void* stream);
+// response + per-workgroup masked maximum (d_bmax: fe_harris_blocks(w, h) entries), then threshold / NMS /
+// compaction into (d_candR, d_candI), *d_count candidates (zeroed here)
+int fe_harris_blocks(int w, int h);
+int launch_fe_harris(const uint8_t* d_img, const uint8_t* d_mask, int w, int h, int block_size, double k,
+					 double quality, double* d_resp, double* d_bmax, double* d_candR, int* d_candI, int* d_count,
+					 void* stream);
+// sorted list + greedy pick; n = the candidate count (host copy of *d_count), cap = capacity of the lists
+// (a power of two >= n when n > kFeSortLds: the lists are padded and sorted in global memory first)
+int launch_fe_select(double* d_candR, int* d_candI, const int* d_count, int n, int cap, int w, int max_corners,
+					 double min_distance, float* d_corners, int* d_nout, void* stream);
+// levels 1 .. n_levels-1 from level 0, then the derivatives of every level (lv: host copy of the table)
+int launch_fe_pyramid(char* d_pyr, const FeLevel* lv, int n_levels, void* stream);
+int launch_fe_lk(const char* d_prev, const char* d_next, const FeLevel* d_lv, int n_levels, int n, const float* d_prev_xy,
+				 float* d_next_xy, uint8_t* d_status, float* d_err, int win_w, int win_h, int max_count, double eps2,
+				 float min_eig, void* stream);
+
 }  // namespace ebo

@@ -2950,6 +2950,7 @@ __global__ void __launch_bounds__(64) k_route(const uint32_t* __restrict__ xy, u
 #include "ebo_fieldtv.inc"
 #include "ebo_optimizer.inc"
 #include "ebo_band.inc"
+#include "ebo_frontend.inc"
 
 int check_launch()
 {
@@ -4086,6 +4087,111 @@ int launch_patch_integrate(const PatchIntLaunch& L, void* stream)
 	return check_launch();
 }
 
+}  // namespace ebo
+
+// ---- image front end (ebo_frontend.inc) ----
+namespace ebo
+{
+int launch_fe_gradients(const uint8_t* d_img, const double* d_lut, int w, int h, double* d_gx, double* d_gy, void* stream)
+{
+	const dim3 grid((w + kFeTileW - 1) / kFeTileW, (h + kFeTileH - 1) / kFeTileH);
+	hipLaunchKernelGGL(k_fe_gradients, grid, dim3(kFeTileW, kFeTileH), 0, static_cast<hipStream_t>(stream), d_img, d_lut,
+					   w, h, d_gx, d_gy);
+	return check_launch();
+}
+
+int fe_harris_blocks(int w, int h)
+{
+	return ((w + kFeHarrisT - 1) / kFeHarrisT) * ((h + kFeHarrisT - 1) / kFeHarrisT);
+}
+
+int launch_fe_harris(const uint8_t* d_img, const uint8_t* d_mask, int w, int h, int block_size, double k, double quality,
+					 double* d_resp, double* d_bmax, double* d_candR, int* d_candI, int* d_count, void* stream)
+{
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	if (hipMemsetAsync(d_count, 0, sizeof(int), s) != hipSuccess)
+	{
+		return -2;
+	}
+	const dim3 grid((w + kFeHarrisT - 1) / kFeHarrisT, (h + kFeHarrisT - 1) / kFeHarrisT);
+	hipLaunchKernelGGL(k_fe_harris, grid, dim3(kFeHarrisT, kFeHarrisT), 0, s, d_img, d_mask, w, h, block_size, k, d_resp,
+					   d_bmax);
+	if (check_launch())
+	{
+		return -2;
+	}
+	const int npx = w * h;
+	hipLaunchKernelGGL(k_fe_candidates, dim3((npx + 255) / 256), dim3(256), 0, s, d_resp, d_mask, w, h, quality, d_bmax,
+					   fe_harris_blocks(w, h), d_candR, d_candI, d_count);
+	return check_launch();
+}
+
+int launch_fe_select(double* d_candR, int* d_candI, const int* d_count, int n, int cap, int w, int max_corners,
+					 double min_distance, float* d_corners, int* d_nout, void* stream)
+{
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	const int sorted = n > kFeLdsSort ? 1 : 0;
+	if (sorted)
+	{
+		int N = 1;
+		while (N < n)
+		{
+			N <<= 1;
+		}
+		if (N > cap)
+		{
+			return -1;
+		}
+		hipLaunchKernelGGL(k_fe_pad, dim3((N + 255) / 256), dim3(256), 0, s, d_candR, d_candI, d_count, N);
+		for (int kk = 2; kk <= N; kk <<= 1)
+		{
+			for (int jj = kk >> 1; jj > 0; jj >>= 1)
+			{
+				hipLaunchKernelGGL(k_fe_bitonic_step, dim3((N + 255) / 256), dim3(256), 0, s, d_candR, d_candI, N, kk, jj);
+			}
+		}
+		if (check_launch())
+		{
+			return -2;
+		}
+	}
+	hipLaunchKernelGGL(k_fe_select, dim3(1), dim3(1024), 0, s, d_candR, d_candI, d_count, sorted, w, max_corners,
+					   min_distance, d_corners, d_nout);
+	return check_launch();
+}
+
+int launch_fe_pyramid(char* d_pyr, const FeLevel* lv, int n_levels, void* stream)
+{
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	for (int l = 1; l < n_levels; ++l)
+	{
+		const int np = lv[l].w * lv[l].h;
+		hipLaunchKernelGGL(k_fe_pyrdown, dim3((np + 255) / 256), dim3(256), 0, s,
+						   reinterpret_cast<const uint8_t*>(d_pyr + lv[l - 1].img), lv[l - 1].w, lv[l - 1].h,
+						   reinterpret_cast<uint8_t*>(d_pyr + lv[l].img), lv[l].w, lv[l].h);
+	}
+	for (int l = 0; l < n_levels; ++l)
+	{
+		const int np = lv[l].w * lv[l].h;
+		hipLaunchKernelGGL(k_fe_scharr, dim3((np + 255) / 256), dim3(256), 0, s,
+						   reinterpret_cast<const uint8_t*>(d_pyr + lv[l].img), lv[l].w, lv[l].h,
+						   reinterpret_cast<short2*>(d_pyr + lv[l].der));
+	}
+	return check_launch();
+}
+
+int launch_fe_lk(const char* d_prev, const char* d_next, const FeLevel* d_lv, int n_levels, int n, const float* d_prev_xy,
+				 float* d_next_xy, uint8_t* d_status, float* d_err, int win_w, int win_h, int max_count, double eps2,
+				 float min_eig, void* stream)
+{
+	if (n == 0)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_fe_lk, dim3((n + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), d_prev, d_next, d_lv,
+					   n_levels, n, d_prev_xy, d_next_xy, d_status, d_err, win_w, win_h, max_count, eps2, min_eig);
+	return check_launch();
+}
 }  // namespace ebo
 
 #ifdef EBO_EDGE_TIMING

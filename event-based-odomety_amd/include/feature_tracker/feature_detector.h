@@ -19,7 +19,8 @@
 // reference's bookkeeping (patch association, archive, optimizer user counts).  The three OpenCV-only
 // pieces of newImage — cv::goodFeaturesToTrack (:568-583), log image + cv::Sobel (:713-731) and
 // cv::calcOpticalFlowPyrLK (flow_estimator.cpp:86-108) — are outside the event-warping path: they are
-// taken as FrontEndHooks (three lambdas holding the reference's own OpenCV calls); without them
+// taken as FrontEndHooks (three lambdas holding the reference's own OpenCV calls), or installed by
+// useDeviceFrontEnd() as the device's own (include/ebo.h, "image front end"); without either,
 // newImage / extractPatches / detectFeatures report EBO_ERR_UNSUPPORTED through the error policy.
 //
 // Result images are CV_64F-like (tracker::Mat64, row-major doubles, rows x cols = imageSize), valid
@@ -27,6 +28,7 @@
 // without a copy:  cv::Mat view(m.rows, m.cols, CV_64F, const_cast<double*>(m.ptr()));
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <functional>
 #include <list>
@@ -105,6 +107,20 @@ struct FrontEndHooks
 	// this one for ONE point (cv::Point2f in and out); false = status 0.  Called from the second image on.
 	std::function<bool(float x, float y, float& nextX, float& nextY)> flow;
 	double patchTimeWithoutUpdateScale = 1e6;  // FlowEstimatorParams (flow_estimator.h:16)
+	// FlowEstimator::addImage (flow_estimator.cpp:16-25), called by newImage where the reference calls it (optional)
+	std::function<void(const common::Image8&)> addImage;
+	// the flow of ALL un-initialised patches in one call (preferred over `flow` when set): prevXY [n][2] in,
+	// nextXY [n][2] and status [n] (0 = no flow) out
+	std::function<void(const std::vector<float>& prevXY, std::vector<float>& nextXY, std::vector<uint8_t>& status)>
+		flowBatch;
+};
+
+// FlowEstimatorParams (flow_estimator.h:11-17)
+struct FlowEstimatorParams
+{
+	int32_t numLevels = 3;
+	Size window = {21, 21};
+	double patchTimeWithoutUpdateScale = 1e6;  // seconds in double to microseconds
 };
 
 class FeatureDetector
@@ -140,6 +156,66 @@ class FeatureDetector
 
 	void setFrontEndHooks(const FrontEndHooks& hooks) { hooks_ = hooks; }
 
+	// Installs FrontEndHooks backed by this detector's own device context: ebo_good_features with the reference's
+	// maxCorners_ (W*H / (2*patchExtent+1)^2), mask_ (a border of patchExtent), qualityLevel, minDistance, blockSize
+	// and k = 0.04 (feature_detector.cpp:32-45,568-583); ebo_image_gradients (:713-731); ebo_lk_add_image and one
+	// ebo_lk_track for all new patches with the flow estimator's window, levels and OpenCV's default criteria
+	// (flow_estimator.cpp:16-25,86-108).  Grey images only (the reference's cvtColor branch is not built).
+	void useDeviceFrontEnd(const FlowEstimatorParams& flowParams = {})
+	{
+		FrontEndHooks h;
+		h.patchTimeWithoutUpdateScale = flowParams.patchTimeWithoutUpdateScale;
+		h.detectFeatures = [this](const common::Image8& image) {
+			const int w = params_.imageSize.width, ht = params_.imageSize.height, e = params_.patchExtent;
+			const int maxCorners = w * ht / ((2 * e + 1) * (2 * e + 1));
+			std::vector<uint8_t> mask(static_cast<size_t>(w) * ht, 0);
+			for (int y = e; y < ht - e; ++y)
+			{
+				for (int x = e; x < w - e; ++x)
+				{
+					mask[static_cast<size_t>(y) * w + x] = 1;
+				}
+			}
+			std::vector<float> xy(2 * static_cast<size_t>(std::max(maxCorners, 1)));
+			int n = 0;
+			Corners corners;
+			std::vector<uint8_t> tmp;
+			if (maxCorners >= 1 && check(ebo_good_features(ctx_, greyPixels(image, tmp), mask.data(), maxCorners,
+														  params_.qualityLevel, params_.minDistance, params_.blockSize,
+														  0.04, xy.data(), &n)))
+			{
+				for (int k = 0; k < n; ++k)
+				{
+					corners.push_back(Corner(xy[2 * k], xy[2 * k + 1]));
+				}
+			}
+			return corners;  // (a failure is in status(); detectFeatures() itself never throws under ERRORS_STATUS)
+		};
+		h.gradients = [this](const common::Image8& image, Mat64& gradX, Mat64& gradY) {
+			gradX = Mat64(params_.imageSize.height, params_.imageSize.width);
+			gradY = Mat64(params_.imageSize.height, params_.imageSize.width);
+			std::vector<uint8_t> tmp;
+			check(ebo_image_gradients(ctx_, greyPixels(image, tmp), gradX.ptr(), gradY.ptr()));
+			throwIfFailed();
+		};
+		h.addImage = [this](const common::Image8& image) {
+			std::vector<uint8_t> tmp;
+			check(ebo_lk_add_image(ctx_, greyPixels(image, tmp)));
+			throwIfFailed();
+		};
+		h.flowBatch = [this, flowParams](const std::vector<float>& prevXY, std::vector<float>& nextXY,
+										 std::vector<uint8_t>& status) {
+			const int n = static_cast<int>(prevXY.size() / 2);
+			nextXY.assign(prevXY.size(), 0.f);
+			status.assign(static_cast<size_t>(n), 0);
+			// cv::calcOpticalFlowPyrLK's defaults: TermCriteria(COUNT + EPS, 30, 0.01), minEigThreshold 1e-4
+			check(ebo_lk_track(ctx_, n, prevXY.data(), nextXY.data(), status.data(), nullptr, flowParams.window.width,
+							   flowParams.window.height, flowParams.numLevels, 30, 0.01, 1e-4));
+			throwIfFailed();
+		};
+		hooks_ = h;
+	}
+
 	// feature_detector.cpp:493-541.  Needs the detectFeatures and gradients hooks (EBO_ERR_UNSUPPORTED
 	// without them); without the flow hook new patches stay un-initialised, as before the reference's
 	// second image (flow_estimator.cpp:29-32).
@@ -156,11 +232,15 @@ class FeatureDetector
 		guarded([&] {
 			extractPatchesImpl(image);
 			// flowEstimator_->addImage / getFlowPatches (flow_estimator.cpp:16-85)
+			if (hooks_.addImage)
+			{
+				hooks_.addImage(image.value);
+			}
 			if (imageCounter_ < 2)
 			{
 				imageCounter_++;
 			}
-			if (imageCounter_ == 2 && hooks_.flow)
+			if (imageCounter_ == 2 && (hooks_.flow || hooks_.flowBatch))
 			{
 				flowPatches();
 			}
@@ -618,9 +698,30 @@ class FeatureDetector
 		associatePatches(newPatches, image.timestamp);
 	}
 
-	// FlowEstimator::getFlowPatches (flow_estimator.cpp:27-85), the point flow through the hook
+	// FlowEstimator::getFlowPatches (flow_estimator.cpp:27-85), the point flow through the hook (all points in one
+	// flowBatch call when it is set)
 	void flowPatches()
 	{
+		std::vector<float> prevXY, nextXY;
+		std::vector<uint8_t> status;
+		if (hooks_.flowBatch)
+		{
+			for (Patch& patch : tracked_->getPatches())
+			{
+				if (!patch.isInit())
+				{
+					const Corner corner = patch.toCorner();
+					prevXY.push_back(static_cast<float>(corner.x));
+					prevXY.push_back(static_cast<float>(corner.y));
+				}
+			}
+			hooks_.flowBatch(prevXY, nextXY, status);
+			if (nextXY.size() != prevXY.size() || status.size() != prevXY.size() / 2)
+			{
+				throw std::runtime_error("FrontEndHooks::flowBatch: one next point and one status per point");
+			}
+		}
+		size_t k = 0;
 		for (Patch& patch : tracked_->getPatches())
 		{
 			if (patch.isInit())
@@ -629,7 +730,19 @@ class FeatureDetector
 			}
 			const Corner corner = patch.toCorner();
 			float nx = 0.f, ny = 0.f;
-			if (!hooks_.flow(static_cast<float>(corner.x), static_cast<float>(corner.y), nx, ny))
+			bool found;
+			if (hooks_.flowBatch)
+			{
+				nx = nextXY[2 * k];
+				ny = nextXY[2 * k + 1];
+				found = status[k] != 0;
+				++k;
+			}
+			else
+			{
+				found = hooks_.flow(static_cast<float>(corner.x), static_cast<float>(corner.y), nx, ny);
+			}
+			if (!found)
 			{
 				patch.setLost();
 				continue;
@@ -668,6 +781,41 @@ class FeatureDetector
 			{
 				tracked_->warpImages(group.second, opt->second->handle());
 			}
+		}
+	}
+
+	// the device front end's image: CV_8U single channel, rows x cols = imageSize (copied from a cv::Mat row by row)
+	const uint8_t* greyPixels(const common::Image8& image, std::vector<uint8_t>& tmp)
+	{
+		const int w = params_.imageSize.width, h = params_.imageSize.height;
+#ifdef EBO_HAVE_OPENCV
+		const bool grey = image.type() == CV_8U;
+#else
+		const bool grey = image.data.size() == static_cast<size_t>(image.rows) * image.cols;
+#endif
+		if (!grey || image.rows != h || image.cols != w)
+		{
+			throw std::invalid_argument("device front end: an 8-bit grey image of imageSize is needed");
+		}
+#ifdef EBO_HAVE_OPENCV
+		tmp.resize(static_cast<size_t>(w) * h);
+		for (int y = 0; y < h; ++y)
+		{
+			const uint8_t* row = image.template ptr<uint8_t>(y);
+			std::copy(row, row + w, tmp.begin() + static_cast<size_t>(y) * w);
+		}
+		return tmp.data();
+#else
+		(void)tmp;
+		return image.data.data();
+#endif
+	}
+	// a failed ebo_* call inside a hook ends the guarded newImage / extractPatches like any other failure
+	void throwIfFailed()
+	{
+		if (status_ != EBO_OK)
+		{
+			throw std::runtime_error(lastError_);
 		}
 	}
 

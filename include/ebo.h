@@ -569,6 +569,85 @@ int ebo_allgather_track_counts(ebo_ctx* ctx, size_t n_local, size_t* n_all, size
 int ebo_write_tracks_txt(const char* path, const ebo_track_point* pts, size_t n);
 int ebo_read_tracks_txt(const char* path, ebo_track_point* out, size_t cap, size_t* n);
 
+/* ---- image front end (FeatureDetector::newImage without OpenCV) ------------------------------
+ * Images are 8-bit grey, [image_h][image_w] row-major, at the context's ebo_params size.  Every
+ * entry is synchronous and returns EBO_ERR_STATE while a graph is being recorded.  Agreement with
+ * OpenCV is by construction of the rules below, not bit for bit: OpenCV is not a dependency, and the
+ * rules are what the tests restate on the CPU.  refl(i, n) is BORDER_REFLECT_101 (..., 2, 1 | 0 .. n-1 | n-2, ...).
+ *
+ * ebo_image_gradients: FeatureDetector::getLogImage + getGradients (feature_detector.cpp:713-731).
+ *   L[v] = std::log(v * (1.0 / 255.0) + 0.1) / 8 for v = 0..255, a table evaluated on the host in
+ *   double (convertTo with alpha 1/255, + 10e-2, cv::log, / 8).  cv::log is OpenCV's own
+ *   approximation, so the table agrees with OpenCV only to a few ulp; that cannot be checked without it.
+ *   Then the separable 3x3 Sobel of cv::Sobel(L, CV_64F, dx, dy, 3), indices through refl(), in double,
+ *   one rounding per operation in exactly this association (no contraction):
+ *     grad_x: r(x, y) = L(x+1, y) - L(x-1, y);                gx = (r(x, y-1) + 2 * r(x, y)) + r(x, y+1)
+ *     grad_y: s(x, y) = (L(x-1, y) + 2 * L(x, y)) + L(x+1, y); gy = s(x, y+1) - s(x, y-1)
+ *   grad_x, grad_y: host double [image_h][image_w]; what ebo_optimizer_set_grad takes.
+ *
+ * ebo_good_features: cv::goodFeaturesToTrack(image, corners, max_corners, quality_level, min_distance, mask,
+ *   block_size, useHarrisDetector = true, harris_k) (feature_detector.cpp:568-583):
+ *   1. dx, dy: integer 3x3 Sobel of the image (refl()).  A, B, C: block_size x block_size box sums of
+ *      dx*dx, dx*dy, dy*dy (window rows / columns i - block_size/2 .. i - block_size/2 + block_size - 1, the
+ *      moment image read through refl()); exact in integers.
+ *   2. R = (double)(A*C - B*B) - harris_k * ((double)(A+C) * (double)(A+C)): the determinant exact in int64,
+ *      then the double operations rounded in this order.  OpenCV's positive scale of the derivatives changes
+ *      no selection and is dropped; where two responses differ by less than OpenCV's float32 rounding the
+ *      order can differ from OpenCV's float32 pipeline.
+ *   3. maxVal = max of R over mask != 0 (all pixels with mask == NULL); T = R where R > quality_level * maxVal, else 0.
+ *   4. Candidates: 1 <= x <= w-2, 1 <= y <= h-2, mask != 0, T != 0 and T equal to the maximum of T over its 3x3
+ *      neighbourhood (pixels outside the image do not count).
+ *   5. Sorted by R descending, ties by LARGER raster index y*w + x first (OpenCV >= 3.4's comparator; the
+ *      reference's OpenCV 3.2 leaves ties unspecified).
+ *   6. Greedy in that order: a candidate is accepted when no accepted corner lies at Euclidean distance
+ *      < min_distance ((dx*dx + dy*dy) < min_distance * min_distance in double); stop at max_corners.
+ *   corners_xy: host float [max_corners][2] (x, y); *n_out = corners found.  The list is deterministic.
+ *   max_corners >= 1, 1 <= block_size <= 7, else EBO_ERR_ARG.
+ *
+ * ebo_lk_add_image: FlowEstimator::addImage (flow_estimator.cpp:16-25).  Builds the image's pyramid and the
+ *   Scharr derivatives of every level on the device; the context keeps the last two images (the newer one
+ *   becomes the older one on the next call, nothing is recomputed).
+ *   Pyramid: level l+1 = cv::pyrDown(level l): 5x5 kernel [1 4 6 4 1]^T [1 4 6 4 1], source read through
+ *   refl(), (sum + 128) >> 8; size ((w+1)/2, (h+1)/2).  Levels are built while the new level is at least 2 x 2,
+ *   at most 8.
+ *   Derivatives (calcSharrDeriv), int16 per level: v0 = 3*(I(x, y-1) + I(x, y+1)) + 10*I(x, y), v1 = I(x, y+1) -
+ *   I(x, y-1); Ix = v0(x+1) - v0(x-1), Iy = 3*(v1(x-1) + v1(x+1)) + 10*v1(x), all indices through refl().
+ *
+ * ebo_lk_track: cv::calcOpticalFlowPyrLK(older, newer, prev_xy, next_xy, status, err, (win_w, win_h), max_level,
+ *   TermCriteria(COUNT + EPS, max_count, epsilon), flags 0, min_eig_threshold) for n points in one launch
+ *   (flow_estimator.cpp:86-108 calls it per point with (21, 21), 3, (30, 0.01), 1e-4).  EBO_ERR_STATE before two
+ *   images were added.  Rules (Bouguet; float32 arithmetic, one rounding per operation, no contraction):
+ *   - Levels: the pyramid is used up to the first level l < max_level whose next level is not larger than the
+ *     window in both dimensions ((w_{l+1} <= win_w || h_{l+1} <= win_h) stops at l), at most max_level.
+ *   - Image reads: I, J at (x, y) for -win <= x < w + win read refl(); derivatives read 0 outside the level.
+ *   - Bilinear with 14-bit weights: a, b = fractional parts (float), w00 = rint((1-a)*(1-b)*16384), w01 =
+ *     rint(a*(1-b)*16384), w10 = rint((1-a)*b*16384), w11 = 16384 - w00 - w01 - w10 (rint: half to even);
+ *     image samples descale by 9 bits ((s + 256) >> 9, 5 fractional bits kept), derivative samples by 14 bits.
+ *   - Per level l from the top: result = prev_xy / 2^l at the top level, else 2 * result; p = prev_xy / 2^l - half,
+ *     half = ((win_w-1)/2, (win_h-1)/2) as float; q = result - half.  floor(p) outside [-win, w_l) x [-win, h_l):
+ *     status = 0 at level 0, the level is skipped otherwise.  G = the window's sums of IxIx, IxIy, IyIy, exact in
+ *     int64, times 2^-20 as float; D = G11*G22 - G12*G12; minEig = ((G22 + G11) - sqrt((G11-G22)*(G11-G22) +
+ *     (4*G12)*G12)) / (2*win_w*win_h).  minEig < (float)min_eig_threshold or D < FLT_EPSILON: status = 0 at level 0,
+ *     the level is skipped otherwise.
+ *   - Iteration k < max_count: floor(q) outside [-win, w_l) x [-win, h_l): status = 0 at level 0, stop.  b = the sums of
+ *     (J(q) - I(p)) * (Ix, Iy), exact in int64, times 2^-20 as float; delta = ((G12*b2 - G22*b1) * (1/D),
+ *     (G12*b1 - G11*b2) * (1/D)); q += delta; result = q + half.  Stop when (double)dx^2 + (double)dy^2 <=
+ *     epsilon^2; for k > 0 take the half-step exit when |delta + delta_prev| < 0.01 in both components:
+ *     result -= 0.5 * delta, stop.
+ *   - Then, with status 1: floor(result - half) outside the level-0 bounds gives status 0; err = sum |J - I| over
+ *     the window at the result (integer sum) / (32 * win_w * win_h) as float (OpenCV computes it whenever an
+ *     error vector is passed, as the reference does; its position check applies with err == NULL too).
+ *   prev_xy, next_xy: host float [n][2]; status: host uint8 [n]; err: host float [n] (may be NULL).
+ *   err is 0 where status is 0.  As OpenCV, max_count is clamped to 100 and epsilon to 10.
+ *   3 <= win_w, win_h and win_w * win_h <= 1024, 0 <= max_level <= 7, max_count >= 1, else EBO_ERR_ARG.  Bit
+ *   parity with OpenCV is not claimed (its sums are float, in a SIMD-dependent order). */
+int ebo_image_gradients(ebo_ctx* ctx, const uint8_t* image, double* grad_x, double* grad_y);
+int ebo_good_features(ebo_ctx* ctx, const uint8_t* image, const uint8_t* mask, int max_corners, double quality_level,
+					  double min_distance, int block_size, double harris_k, float* corners_xy, int* n_out);
+int ebo_lk_add_image(ebo_ctx* ctx, const uint8_t* image);
+int ebo_lk_track(ebo_ctx* ctx, int n, const float* prev_xy, float* next_xy, uint8_t* status, float* err, int win_w,
+				 int win_h, int max_level, int max_count, double epsilon, double min_eig_threshold);
+
 /* Device-side timing of everything enqueued between begin and end on the
  * context's stream (hipEvent based). */
 int ebo_timer_begin(ebo_ctx* ctx);
