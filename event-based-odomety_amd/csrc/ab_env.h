@@ -7,7 +7,7 @@
 //   EBO_SOLVE_TRACE, EBO_INGEST_TRACE    diagnostics on stderr
 // Everything else -- forcing an implementation a launch would not pick at this size, block shapes, ablations,
 // the switches the equivalence tests flip -- goes through ab_env() / ab_size(), which look at the environment only
-// in the -DEBO_AB build (`make ab` -> libebo_hip_ab.so: what tools/ab/*, tools/sweep_impl.py and the tests' `ebo_ab`
+// in the -DEBO_AB build (`make ab` -> libebo_hip_ab.so: what tools/ab/*, the tools' A/B scripts and the tests' `ebo_ab`
 // fixture load).  In the shipped build they are constant: one path per call, no knob string in the binary.
 #pragma once
 

@@ -155,12 +155,9 @@ int ensure_scratch(ebo_ctx* c, size_t bytes)
 	return rc;
 }
 
-// Evaluation geometry.  tiles: row tiles per unit (parallel workgroups).  More
-// tiles = more workgroups and less LDS each; the events of a unit are re-read
-// (from L2) by each of its tiles.  EBO_EVAL_TILES / EBO_EVAL_BLOCK override.
-// impl 1/2: the image is the bounding box of the warped events; one workgroup owns
-// `cap` pixels of LDS (default 32 KiB => 5 workgroups per CU) and walks larger boxes
-// in sequential sub-bands.  A full canvas row must fit.
+// LDS of one k_eval3 / k_solve_independent workgroup.  The image is the bounding box of
+// the warped events; one workgroup owns `capDoubles` pixels of LDS behind a header and
+// walks larger boxes in sequential sub-bands.  A full canvas row must fit.
 int image_capacity(ebo_ctx* c, int& capDoubles, size_t& lds, size_t defaultKb = 40)
 {
 	const size_t headerBytes = 160 * sizeof(double);
@@ -178,42 +175,6 @@ int image_capacity(ebo_ctx* c, int& capDoubles, size_t& lds, size_t defaultKb = 
 	}
 	capDoubles = static_cast<int>((bytes - headerBytes) / sizeof(double));
 	lds = bytes;
-	return EBO_OK;
-}
-
-int eval_impl()
-{
-	const int v = static_cast<int>(ab_size("EBO_EVAL_IMPL", 3));
-	return (v < 0 || v > 3) ? 3 : v;
-}
-
-int eval_geometry(ebo_ctx* c, int channels, int& tiles, int& block, size_t& lds)
-{
-	const size_t budget = ab_size("EBO_LDS_BUDGET", kLdsBudget);
-	const int fit = min_tiles(channels, c->max_rw, c->max_rh, budget);
-	if (fit < 0)
-	{
-		return c->fail(EBO_ERR_UNSUPPORTED, "patch too wide for LDS row tiling");
-	}
-	int t = static_cast<int>(ab_size("EBO_EVAL_TILES", 0));
-	if (t <= 0)
-	{
-		t = fit;
-		const int nUnits = static_cast<int>(c->n_flows());
-		// fill the chip (256 CUs) when there are few units, but keep >= 16 rows per tile
-		while (nUnits * t < 512 && (3 * c->max_rh) / (t + 1) >= 16)
-		{
-			++t;
-		}
-	}
-	t = std::max(t, fit);
-	tiles = t;
-	block = static_cast<int>(ab_size("EBO_EVAL_BLOCK", 256));
-	if (block < 64 || block > 1024 || (block & 63))
-	{
-		return c->fail(EBO_ERR_ARG, "EBO_EVAL_BLOCK must be a multiple of 64 in [64,1024]");
-	}
-	lds = lds_for(channels, t, c->max_rw, c->max_rh);
 	return EBO_OK;
 }
 
@@ -539,69 +500,56 @@ int run_eval_device(ebo_ctx* c, const double* d_flows, int want_jac, double* d_o
 	L.flow_sets = central ? 5 : 1;
 	L.channels = (want_jac && !central) ? 3 : 1;
 	L.fd_step = central ? c->prm.fd_step : 0.0;
-	L.impl = eval_impl();
-	L.cap_doubles = 0;
-	L.rotate = ab_size("EBO_EVAL_ROT", 1) ? 1 : 0;
-	L.deal = ab_size("EBO_EVAL_DEAL", 0) ? 1 : 0;
-	int rc;
-	if (L.impl == 0)
-	{
-		rc = eval_geometry(c, L.channels, L.tiles, L.block, L.lds_bytes);
-	}
-	else
-	{
-		// Many units: k_eval3 runs four waves per SIMD (128 VGPRs), i.e. 16 waves per CU, and what a launch
-		// chooses is how to cut them into workgroups -- more, smaller workgroups overlap their barrier-separated
-		// passes better on the CU's one LDS, but each gets less of it, and a box that does not fit is counted in
-		// sequential sub-bands (every event warped again per sub-band).  By the canvas of the REGULAR patch (the
-		// geometry only, never the data: a window evaluates bit-identically alone and inside any batch):
-		//    canvas <= 32 KB (the reference's 20x20 patches, C3's 21x16): 7 workgroups of 128 lanes, 22 KB
-		//    larger (C2 30x22, C4 40x22):                                  4 workgroups of 256 lanes, 39 KB
-		// Measured against three waves per SIMD with four 192-lane workgroups of 40 KB (round 2), evaluation with
-		// Jacobian at flows 0 / 0.5 / 1.0 x ground truth: 20x20 patches of 139 events -23 / -19 / -13 % time,
-		// C3 -8.5 / -5.3 / +0.8 %, C2 -6.3 / -2.5 / -2.3 %, C4 -3.9 / -2.9 / -4.4 % (profiles/r03_eval3_waves4_ab.txt;
-		// 128 lanes x 19 KB: better still at small flows, +6 % at the ground truth of C3; 192 lanes x 31 KB:
-		// -2 ... -4 % everywhere at C3, but only -8 ... -11 % on the 20x20 patches).
-		const int nUnitsAll = std::max(1, static_cast<int>(c->n_flows()));
-		const int regW = c->reg_rw, regH = c->reg_rh;
-		const bool smallCanvas = static_cast<size_t>(9) * regW * regH * sizeof(double) <= 32 * 1024;
-		const int manyBlock = smallCanvas ? 128 : 256;
-		rc = image_capacity(c, L.cap_doubles, L.lds_bytes, nUnitsAll < 1024 ? 40 : (smallCanvas ? 22 : 39));
-		// Measured (tools/sweep_impl.py): one row band per unit is best at every batch size
-		// (each band workgroup pays the bounding-box pass over all events); with few units
-		// a 512-thread workgroup shortens the per-unit critical path (29 vs 46 us for one
-		// 64-patch window); with many units the smaller workgroups chosen above pack the CU better and
-		// waste fewer lanes in a unit's last round of events.  (The sums of a unit are reduced over the
-		// workgroup, so the two regimes differ in the last bits: a window is bit-identical alone
-		// and inside a batch as long as both are on the same side of 1024 units.)
-		const int nUnits = std::max(1, static_cast<int>(c->n_flows()));
-		L.block = static_cast<int>(ab_size("EBO_EVAL_BLOCK", nUnits < 1024 ? 512 : manyBlock));
-		if (L.block < 64 || L.block > 512 || (L.block & 63))
-		{
-			return c->fail(EBO_ERR_ARG, "EBO_EVAL_BLOCK must be a multiple of 64 in [64,512]");
-		}
-		int t = static_cast<int>(ab_size("EBO_EVAL_TILES", 0));
-		if (t <= 0)
-		{
-			// One workgroup per unit, unless a unit's image needs many sequential sub-bands (a
-			// patch as large as the frame, configs[0]: a 720x540 canvas): then its rows are split
-			// over a few parallel workgroups (measured there: 4-8 tiles best for few windows, 2 for
-			// many).  The choice depends on the patch geometry only, NOT on the batch size, so that
-			// a window evaluates bit-identically alone and inside any batch.
-			const long canvas = 9L * c->max_rw * c->max_rh;
-			const long subBands = (canvas + L.cap_doubles - 1) / std::max(L.cap_doubles, 1);
-			t = static_cast<int>(std::min<long>(std::max<long>(subBands / 6, 1), 4));
-			while (t > 1 && (3 * c->max_rh) / t < 16)
-			{
-				--t;
-			}
-		}
-		L.tiles = std::max(1, std::min(t, 64));
-	}
+	// Many units: k_eval3 runs four waves per SIMD (128 VGPRs), i.e. 16 waves per CU, and what a launch
+	// chooses is how to cut them into workgroups -- more, smaller workgroups overlap their barrier-separated
+	// passes better on the CU's one LDS, but each gets less of it, and a box that does not fit is counted in
+	// sequential sub-bands (every event warped again per sub-band).  By the canvas of the REGULAR patch (the
+	// geometry only, never the data: a window evaluates bit-identically alone and inside any batch):
+	//    canvas <= 32 KB (the reference's 20x20 patches, C3's 21x16): 7 workgroups of 128 lanes, 22 KB
+	//    larger (C2 30x22, C4 40x22):                                  4 workgroups of 256 lanes, 39 KB
+	// Measured against three waves per SIMD with four 192-lane workgroups of 40 KB (round 2), evaluation with
+	// Jacobian at flows 0 / 0.5 / 1.0 x ground truth: 20x20 patches of 139 events -23 / -19 / -13 % time,
+	// C3 -8.5 / -5.3 / +0.8 %, C2 -6.3 / -2.5 / -2.3 %, C4 -3.9 / -2.9 / -4.4 % (profiles/r03_eval3_waves4_ab.txt;
+	// 128 lanes x 19 KB: better still at small flows, +6 % at the ground truth of C3; 192 lanes x 31 KB:
+	// -2 ... -4 % everywhere at C3, but only -8 ... -11 % on the 20x20 patches).
+	const int nUnits = std::max(1, static_cast<int>(c->n_flows()));
+	const int regW = c->reg_rw, regH = c->reg_rh;
+	const bool smallCanvas = static_cast<size_t>(9) * regW * regH * sizeof(double) <= 32 * 1024;
+	const int manyBlock = smallCanvas ? 128 : 256;
+	int rc = image_capacity(c, L.cap_doubles, L.lds_bytes, nUnits < 1024 ? 40 : (smallCanvas ? 22 : 39));
 	if (rc)
 	{
 		return rc;
 	}
+	// Measured (tools/sweep_eval.py): one row band per unit is best at every batch size
+	// (each band workgroup pays the bounding-box pass over all events); with few units
+	// a 512-thread workgroup shortens the per-unit critical path (29 vs 46 us for one
+	// 64-patch window); with many units the smaller workgroups chosen above pack the CU better and
+	// waste fewer lanes in a unit's last round of events.  (The sums of a unit are reduced over the
+	// workgroup, so the two regimes differ in the last bits: a window is bit-identical alone
+	// and inside a batch as long as both are on the same side of 1024 units.)
+	L.block = static_cast<int>(ab_size("EBO_EVAL_BLOCK", nUnits < 1024 ? 512 : manyBlock));
+	if (L.block < 64 || L.block > 512 || (L.block & 63))
+	{
+		return c->fail(EBO_ERR_ARG, "EBO_EVAL_BLOCK must be a multiple of 64 in [64,512]");
+	}
+	int t = static_cast<int>(ab_size("EBO_EVAL_TILES", 0));
+	if (t <= 0)
+	{
+		// One workgroup per unit, unless a unit's image needs many sequential sub-bands (a
+		// patch as large as the frame, configs[0]: a 720x540 canvas): then its rows are split
+		// over a few parallel workgroups (measured there: 4-8 tiles best for few windows, 2 for
+		// many).  The choice depends on the patch geometry only, NOT on the batch size, so that
+		// a window evaluates bit-identically alone and inside any batch.
+		const long canvas = 9L * c->max_rw * c->max_rh;
+		const long subBands = (canvas + L.cap_doubles - 1) / std::max(L.cap_doubles, 1);
+		t = static_cast<int>(std::min<long>(std::max<long>(subBands / 6, 1), 4));
+		while (t > 1 && (3 * c->max_rh) / t < 16)
+		{
+			--t;
+		}
+	}
+	L.tiles = std::max(1, std::min(t, 64));
 	rc = ensure_partials(c, static_cast<size_t>(L.flow_sets) * L.n_units * L.tiles * kPartialStride);
 	if (rc)
 	{
@@ -1031,7 +979,6 @@ int run_solve_device(ebo_ctx* c, const ebo_solver_opts* o, double* d_flows_out, 
 	L.d_events = c->d_events;
 	L.d_units = c->d_units;
 	L.n_units = static_cast<int>(c->units.size());
-	L.impl = std::max(1, eval_impl());
 	// k_solve_independent runs three waves per SIMD (152-166 VGPRs since round 3: one next_step() site in the
 	// solver; 205 and two waves before), i.e. 12 waves per CU.  By the canvas of the regular patch, as the
 	// batched evaluation does: up to 32 KB six workgroups of 128 lanes with 26 KB each, above that four of 192

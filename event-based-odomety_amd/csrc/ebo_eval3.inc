@@ -1,8 +1,26 @@
-// ebo_eval3.inc — third-generation variance evaluation (impl 3), included inside
-// ebo_kernels.hip's anonymous namespace after eval_unit2 (same algorithm: scatter the
-// value as exact fixed point, gather the derivatives; same bounding-box / band /
-// sub-band structure).  What changes is the instruction count per tap, which the PMC
-// profile of impl 2 showed to be the problem (~1000 VALU instructions per event):
+// ebo_eval3.inc — the variance objective of one unit at one flow (k_eval3, and the evaluation inside
+// k_solve_independent), included inside ebo_kernels.hip's anonymous namespace.
+//
+// Scatter the VALUE, gather the DERIVATIVES.  The Jacobian of the variance objective needs only
+// D1k = sum_px dI_k  and  D2k = sum_px I dI_k  over the touched pixels (every touched pixel has I > 0:
+// Gaussian taps are strictly positive).  With dI_k(px) = sum_e d_k(e, px):
+//     D1k = sum_e sum_taps d_k(e,tap)                    -- no image at all
+//     D2k = sum_e sum_taps I(px(e,tap)) d_k(e,tap)       -- a READ of the value image
+// i.e. forward-mode Jets are re-associated into "value image, then one gather pass": 49 LDS atomics +
+// 49 LDS reads per event instead of 147 atomics, and a third of the LDS.  Mathematically identical to
+// the Jet result.
+//
+// Further: (a) the image covers only the bounding box of the warped events inside the 3W x 3H canvas
+// (the canvas is mostly empty), split in `tiles` row bands (parallel workgroups) and, if a band exceeds
+// the workgroup's LDS, in sequential sub-bands; (b) taps accumulate as exact 64-bit fixed point
+// (ds_add_u64): tap values are < 0.5, so (v + 1.5) has ulp 2^-52 and its mantissa IS the fixed-point
+// number.  Integer adds commute: the image, and with the fixed reduction order the whole result, is
+// bit-reproducible from run to run; it is also faster than ds_add_f64 under same-address conflicts
+// (tools/microbench/lds_atomics.hip); (c) the 7 taps of an axis come from 3 exps:
+// exp(hs (k-f)^2) = exp(hs k^2) exp(hs f^2) exp(f/s^2)^k.
+//
+// What binds is the instruction count per tap (a straightforward version of this algorithm took ~1000
+// VALU instructions per event by its PMC profile), hence:
 //   * interior fast path: an event whose 7x7 footprint lies inside the band (almost all
 //     of them) runs unpredicated loops: per tap  v_fma_f64 + v_sub_u32 + ds_add_u64
 //     with immediate offsets (scatter) /  ds_read_b64 + 2 v_fma_f64 (gather);
@@ -75,21 +93,7 @@ struct EvalReuse
 	double s0, s1, s2;   // sum I, sum I^2, number of non-zero pixels
 };
 
-// BAL: the events a wave holds in one loop step are re-dealt over its lanes before the scatter
-// and the gather.  An LDS b64 operation serves 16 lanes per cycle through 16 bank pairs; lane l
-// touches pair (pixel index of its event's footprint origin + tap offset) mod 16, the same
-// offset for every lane, so the conflicts of all 49 tap instructions are decided by the
-// footprint origins mod 16 of the 16 lanes of a group.  Sorting the wave's 64 events by that
-// residue (counting sort by ballots) and dealing them round-robin to the four 16-lane groups
-// gives every group as many different residues as the wave has.  Any permutation of a unit's
-// events is allowed: the accumulation is exact (integer adds commute).
-// MEASURED (C2 x 256 windows): dealt 0.635-0.645 ms vs 0.638-0.642 ms as loaded -- no gain; the
-// control (sorted but NOT dealt, i.e. equal residues on neighbouring lanes) 0.997 ms.  So the
-// bank model is right, but a random order already sits close to what dealing reaches (u64 LDS
-// atomics top out at 8.5 lanes/clk even conflict-free vs 5.6 random, microbenchmark), and the
-// second warp evaluation plus the 17-ballot sort cost what is gained.  Off by default
-// (EBO_EVAL_DEAL=1 turns it on).
-template <bool SMALL, bool BAL = false>
+template <bool SMALL>
 __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, const Unit& u, double m0,
 											double m1, bool wantJac, int tile, int tiles,
 											int capDoubles, const EvalConsts& c, double* lds,
@@ -232,62 +236,10 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 		}
 		EDGE_TICK(17);
 
-		// residue of the footprint origin's pixel index; 16: the event does not touch this band
-		auto bankKey = [&](uint64_t rec) -> int {
-			int pxc, pyc;
-			double fx, fy, tau;
-			if (!warp_event(rec, rx, ry, rw, rh, m0, m1, c, pxc, pyc, fx, fy, tau))
-			{
-				return 16;
-			}
-			const int rowLo = pyc - 3 - sy0;
-			if (rowLo + 6 < 0 || rowLo >= srows)
-			{
-				return 16;
-			}
-			return (rowLo * cols + (pxc - 3 - x0)) & 15;
-		};
-		auto for_each_dealt = [&](auto&& body) {
-			if (!BAL)
-			{
-				for_each_event(body);
-				return;
-			}
-			const int lane = threadIdx.x & 63;
-			const unsigned long long lower = (1ull << lane) - 1ull;
-			for (uint32_t base = 0; base < nEv; base += blockDim.x)  // wave-uniform trip count
-			{
-				const uint32_t e = base + threadIdx.x;
-				const bool have = e < nEv;
-				uint64_t rec = have ? ev[e] : 0x80000000ull;  // bit 31 of the low dword: no event
-				const int k = have ? bankKey(rec) : 16;
-				int rank = 0, below = 0;
-#pragma unroll
-				for (int r = 0; r <= 16; ++r)
-				{
-					const unsigned long long m = __ballot(k == r);
-					if (k == r)
-					{
-						rank = below + __popcll(m & lower);
-					}
-					below += __popcll(m);
-				}
-				const int dest = ((rank & 3) << 4) | (rank >> 2);
-				const unsigned lo = static_cast<unsigned>(
-					__builtin_amdgcn_ds_permute(dest << 2, static_cast<int>(static_cast<unsigned>(rec))));
-				const unsigned hi = static_cast<unsigned>(
-					__builtin_amdgcn_ds_permute(dest << 2, static_cast<int>(static_cast<unsigned>(rec >> 32))));
-				if (!(lo & 0x80000000u))
-				{
-					body((static_cast<uint64_t>(hi) << 32) | lo);
-				}
-			}
-		};
-
 		// ---- scatter the value taps ----
 		if (!reuse)
 		{
-		for_each_dealt([&](uint64_t rec) {
+		for_each_event([&](uint64_t rec) {
 			int pxc, pyc;
 			double fx, fy, tau;
 			if (!warp_event(rec, rx, ry, rw, rh, m0, m1, c, pxc, pyc, fx, fy, tau))
@@ -377,7 +329,7 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 
 		// ---- gather the derivative sums ----
 		double g3 = 0.0, g4 = 0.0, g5 = 0.0, g6 = 0.0;
-		for_each_dealt([&](uint64_t rec) {
+		for_each_event([&](uint64_t rec) {
 			int pxc, pyc;
 			double fx, fy, tau;
 			if (!warp_event(rec, rx, ry, rw, rh, m0, m1, c, pxc, pyc, fx, fy, tau))
@@ -533,7 +485,7 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 	EDGE_TICK_FLUSH;
 }
 
-template <bool SMALL, bool BAL>
+template <bool SMALL>
 // Four waves per SIMD = 128 VGPRs (round 3; 137 VGPRs and three waves before).  The kernel is bound by the
 // LDS, which idles while a workgroup is between its tap passes, so a fifth 192-lane workgroup per CU is worth
 // 4-5 % -- but only without spills: the first attempt (round 1) spilled inside the tap loops and was 8x slower.
@@ -590,7 +542,7 @@ __global__ void __launch_bounds__(512, 4) k_eval3(const uint64_t* __restrict__ e
 	double m1 = flows[2 * u.flow_idx + 1];
 	fd_offset(set, fdStep, m0, m1);
 	double S[7];
-	eval_unit3<SMALL, BAL>(events + u.ev_off, u, m0, m1, wantJac != 0, tile, tiles, capDoubles, c, lds, S);
+	eval_unit3<SMALL>(events + u.ev_off, u, m0, m1, wantJac != 0, tile, tiles, capDoubles, c, lds, S);
 	if (threadIdx.x == 0)
 	{
 		if (fused)

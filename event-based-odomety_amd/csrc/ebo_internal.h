@@ -154,18 +154,13 @@ struct EvalLaunch
 	int channels;          // 1 or 3
 	int tiles;             // row tiles per unit
 	int block;             // threads per workgroup
-	int impl;              // 0: 3-channel f64 atomics on the full canvas (first version)
-	                       // 1: scatter value / gather derivatives, f64 atomics
-	                       // 2: same with exact fixed-point (u64) accumulation
-	int cap_doubles;       // impl 1/2: image capacity of one workgroup's LDS, in pixels
-	int rotate;            // impl 1/2: per-lane tap rotation in the scatter pass
-	int deal;              // impl 3: re-deal a wave's events over its lanes by LDS bank residue (EBO_EVAL_DEAL)
+	int cap_doubles;       // k_eval3: image capacity of one workgroup's LDS, in pixels
 	size_t lds_bytes;
 	double* d_partials;    // [flow sets][n_units][tiles][kPartialStride]
 	double* d_out;         // [n_flow][3]
 	double fd_step;        // > 0: combine as central differences
-	const unsigned char* d_modes = nullptr;  // per flow slot: 0 skip, 1 value, 2 value + Jacobian (impl 3, fused path)
-	LiveWindows live;      // n > 0: only these windows (impl 3, fused path)
+	const unsigned char* d_modes = nullptr;  // per flow slot: 0 skip, 1 value, 2 value + Jacobian (tiles == 1, one flow set)
+	LiveWindows live;      // n > 0: only these windows (tiles == 1, one flow set)
 	EvalConsts c;
 };
 int launch_eval_variance(const EvalLaunch& L, void* stream);
@@ -270,7 +265,6 @@ struct SolveLaunch
 	const uint64_t* d_events;
 	const Unit* d_units;
 	int n_units;
-	int impl;            // 1 or 2 (see EvalLaunch)
 	int cap_doubles;
 	int block;
 	size_t lds_bytes;

@@ -319,42 +319,9 @@ __device__ __forceinline__ void splat_rows(const uint64_t* __restrict__ ev, uint
 	}
 }
 
-// Sums over the pixels with I > 0 of one tile (contrast_functor.h:111-121,
-// :129-139 folded into one pass): S1 = sum I, S2 = sum I^2, n, D1k = sum dIk,
-// D2k = sum I dIk.
-template <int C>
-__device__ __forceinline__ void tile_sums(const double* __restrict__ img, int plane,
-										   double* red, double (&out)[7])
-{
-	double v[7] = {0, 0, 0, 0, 0, 0, 0};
-	for (int p = threadIdx.x; p < plane; p += blockDim.x)
-	{
-		const double I = img[p];
-		if (I > 0.0)
-		{
-			v[0] += I;
-			v[1] += I * I;
-			v[2] += 1.0;
-			if (C == 3)
-			{
-				const double a = img[plane + p];
-				const double b = img[2 * plane + p];
-				v[3] += a;
-				v[4] += b;
-				v[5] += I * a;
-				v[6] += I * b;
-			}
-		}
-	}
-	block_sum<7>(v, red);
-#pragma unroll
-	for (int k = 0; k < 7; ++k)
-	{
-		out[k] = v[k];
-	}
-}
-
-// contrast_functor.h:122-149 from the sums.  counterNonZero starts at 1 (:110).
+// contrast_functor.h:122-149 from the sums S1 = sum I, S2 = sum I^2, n, D1k = sum dIk,
+// D2k = sum I dIk over the pixels with I > 0 (contrast_functor.h:111-121, :129-139).
+// counterNonZero starts at 1 (:110).
 //   mean = S1/cnt;  var = sum_{I>0}(I-mean)^2 / cnt = (S2 - 2 mean S1 + n mean^2)/cnt
 //   r = maxRes - var, or the out-of-window penalty maxRes (1 + m0^2 + m1^2) if mean <= 0.
 __device__ __forceinline__ void variance_from_sums(const double* S, bool wantJac, double m0,
@@ -393,28 +360,9 @@ __device__ __forceinline__ void fd_offset(int set, double h, double& m0, double&
 }
 
 // ===========================================================================
-// Second-generation evaluation (impl 1 / 2): scatter the VALUE, gather the
-// DERIVATIVES.
-//
-// The Jacobian of the variance objective needs only  D1k = sum_px dI_k  and
-// D2k = sum_px I dI_k  over the touched pixels (every touched pixel has I > 0:
-// Gaussian taps are strictly positive).  With dI_k(px) = sum_e d_k(e, px):
-//     D1k = sum_e sum_taps d_k(e,tap)                    -- no image at all
-//     D2k = sum_e sum_taps I(px(e,tap)) d_k(e,tap)       -- a READ of the value image
-// i.e. forward-mode Jets are re-associated into "value image, then one gather
-// pass": 49 LDS atomics + 49 LDS reads per event instead of 147 atomics, and a
-// third of the LDS.  Mathematically identical to the Jet result.
-//
-// Further: (a) the image covers only the bounding box of the warped events inside
-// the 3W x 3H canvas (the canvas is mostly empty), split in `tiles` row bands
-// (parallel workgroups) and, if a band exceeds the workgroup's LDS, in sequential
-// sub-bands; (b) impl 2 accumulates taps as exact 64-bit fixed point
-// (ds_add_u64): tap values are < 0.5, so (v + 1.5) has ulp 2^-52 and its mantissa
-// IS the fixed-point number -- one v_add_f64 + a 64-bit integer subtract.  Integer
-// adds commute: the image, and with the fixed reduction order the whole result,
-// is bit-reproducible from run to run; it is also faster than ds_add_f64 under
-// same-address conflicts (tools/microbench/lds_atomics.hip); (c) the 7 taps of
-// an axis come from 3 exps:  exp(hs (k-f)^2) = exp(hs k^2) exp(hs f^2) exp(f/s^2)^k.
+// Shared by the variance evaluation (ebo_eval3.inc) and the edge loss
+// (ebo_edge.inc): the LDS header, the warp of one event onto its unit's canvas,
+// the seven taps of one axis and the workgroup's bounding box.
 // ===========================================================================
 constexpr int kRedDoubles = 128;  // 16 waves x 8
 constexpr int kLdsHeader = 160;   // red[128] + 32 doubles of int scratch
@@ -493,371 +441,6 @@ __device__ __forceinline__ void block_minmax(int& xmin, int& xmax, int& ymin, in
 		ymax = max(ymax, ired[w * 4 + 3]);
 	}
 }
-
-// w'[k] = w[(k + r) mod 7], r in 0..6: a 3-stage barrel rotation on registers
-// (v_cndmask only; a runtime-indexed register array would go to scratch).
-__device__ __forceinline__ void rotate7(double (&w)[7], int r)
-{
-	if (r & 1)
-	{
-		const double t = w[0];
-		w[0] = w[1]; w[1] = w[2]; w[2] = w[3]; w[3] = w[4]; w[4] = w[5]; w[5] = w[6]; w[6] = t;
-	}
-	if (r & 2)
-	{
-		const double t0 = w[0], t1 = w[1];
-		w[0] = w[2]; w[1] = w[3]; w[2] = w[4]; w[3] = w[5]; w[4] = w[6]; w[5] = t0; w[6] = t1;
-	}
-	if (r & 4)
-	{
-		const double t0 = w[0], t1 = w[1], t2 = w[2], t3 = w[3];
-		w[0] = w[4]; w[1] = w[5]; w[2] = w[6]; w[3] = t0; w[4] = t1; w[5] = t2; w[6] = t3;
-	}
-}
-
-// The seven sums of one (unit, row band) at flow (m0, m1); every thread returns
-// the same totals.  lds: [red 128][int scratch 32][image capDoubles].
-template <bool FIXED, bool ROT>
-__device__ __forceinline__ void eval_unit2(const uint64_t* __restrict__ ev, const Unit& u, double m0,
-											double m1, bool wantJac, int tile, int tiles,
-											int capDoubles, const EvalConsts& c, double* lds,
-											double (&S)[7])
-{
-	double* red = lds;
-	int* ired = reinterpret_cast<int*>(lds + kRedDoubles);
-	double* img = lds + kLdsHeader;
-	unsigned long long* imgq = reinterpret_cast<unsigned long long*>(img);
-	const int rx = u.rx, ry = u.ry, rw = u.rw, rh = u.rh;
-	const int W3 = 3 * rw, H3 = 3 * rh;
-	const uint32_t nEv = u.n_ev;
-#pragma unroll
-	for (int k = 0; k < 7; ++k)
-	{
-		S[k] = 0.0;
-	}
-
-	// ---- pass A: bounding box of the centre taps that touch the canvas ----
-	int xmin = 0x7fffffff, xmax = -0x7fffffff, ymin = 0x7fffffff, ymax = -0x7fffffff;
-	for (uint32_t e = threadIdx.x; e < nEv; e += blockDim.x)
-	{
-		int pxc, pyc;
-		double fx, fy, tau;
-		if (warp_event(ev[e], rx, ry, rw, rh, m0, m1, c, pxc, pyc, fx, fy, tau))
-		{
-			xmin = min(xmin, pxc);
-			xmax = max(xmax, pxc);
-			ymin = min(ymin, pyc);
-			ymax = max(ymax, pyc);
-		}
-	}
-	block_minmax(xmin, xmax, ymin, ymax, ired);
-	if (xmin > xmax)
-	{
-		return;  // nothing lands in the window: all sums 0 => penalty branch
-	}
-	const int x0 = max(xmin - 3, 0), x1 = min(xmax + 3, W3 - 1);
-	const int y0 = max(ymin - 3, 0), y1 = min(ymax + 3, H3 - 1);
-	const int cols = x1 - x0 + 1;
-	const int rowsAll = y1 - y0 + 1;
-	const int R = (rowsAll + tiles - 1) / tiles;
-	const int ty0 = y0 + tile * R;
-	const int ty1 = min(ty0 + R, y1 + 1);
-	const int maxRows = max(capDoubles / cols, 1);
-	const unsigned long long biasBits = static_cast<unsigned long long>(__double_as_longlong(c.fix_bias));
-	const int lane = threadIdx.x & 63;
-	const int rotRow = ROT ? (lane % 7) : 0;
-	const int rotCol = ROT ? ((lane / 7) % 7) : 0;
-
-	for (int sy0 = ty0; sy0 < ty1; sy0 += maxRows)
-	{
-		const int srows = min(maxRows, ty1 - sy0);
-		const int npx = srows * cols;
-		__syncthreads();
-		for (int i = threadIdx.x; i < npx; i += blockDim.x)
-		{
-			img[i] = 0.0;  // also the all-zero bit pattern of the fixed-point image
-		}
-		__syncthreads();
-
-		// ---- pass B: scatter the value taps ----
-		for (uint32_t e = threadIdx.x; e < nEv; e += blockDim.x)
-		{
-			int pxc, pyc;
-			double fx, fy, tau;
-			if (!warp_event(ev[e], rx, ry, rw, rh, m0, m1, c, pxc, pyc, fx, fy, tau))
-			{
-				continue;
-			}
-			const int rowLo = pyc - 3 - sy0;  // band-local row of tap j = 0
-			if (rowLo + 6 < 0 || rowLo >= srows)
-			{
-				continue;
-			}
-			double wx[7], wy[7];
-			axis_taps(fx, c.norm, c, wx);
-			axis_taps(fy, 1.0, c, wy);
-			const int colLo = pxc - 3 - x0;
-			// Tap rotation: lane l walks the 7x7 taps starting at (l%7, (l/7)%7).  Two
-			// lanes whose events share a centre pixel then never address the same pixel
-			// in the same wave instruction (same-address LDS atomics serialise).
-			rotate7(wy, rotRow);
-			rotate7(wx, rotCol);
-#pragma unroll
-			for (int jr = 0; jr < 7; ++jr)
-			{
-				int j = jr + rotRow;
-				j -= (j >= 7) ? 7 : 0;
-				const int row = rowLo + j;
-				if (row < 0 || row >= srows)
-				{
-					continue;
-				}
-				const int rowBase = row * cols + colLo;
-#pragma unroll
-				for (int ir = 0; ir < 7; ++ir)
-				{
-					int i = ir + rotCol;
-					i -= (i >= 7) ? 7 : 0;
-					const int col = colLo + i;
-					if (col < 0 || col >= cols)
-					{
-						continue;
-					}
-					const double v = wx[ir] * wy[jr];
-					if (FIXED)
-					{
-						const unsigned long long q =
-							static_cast<unsigned long long>(__double_as_longlong(v + c.fix_bias)) - biasBits;
-						atomicAdd(&imgq[rowBase + i], q);
-					}
-					else
-					{
-						atomicAdd(&img[rowBase + i], v);
-					}
-				}
-			}
-		}
-		__syncthreads();
-
-		// ---- pass C: pixel sums (contrast_functor.h:111-121, :129-139) ----
-		for (int p = threadIdx.x; p < npx; p += blockDim.x)
-		{
-			double I;
-			if (FIXED)
-			{
-				const unsigned long long q = imgq[p];
-				I = static_cast<double>(q) * c.fix_scale;
-				img[p] = I;
-			}
-			else
-			{
-				I = img[p];
-			}
-			if (I > 0.0)
-			{
-				S[0] += I;
-				S[1] = fma(I, I, S[1]);
-				S[2] += 1.0;
-			}
-		}
-		if (!wantJac)
-		{
-			continue;
-		}
-		__syncthreads();
-
-		// ---- pass D: gather the derivative sums ----
-		for (uint32_t e = threadIdx.x; e < nEv; e += blockDim.x)
-		{
-			int pxc, pyc;
-			double fx, fy, tau;
-			if (!warp_event(ev[e], rx, ry, rw, rh, m0, m1, c, pxc, pyc, fx, fy, tau))
-			{
-				continue;
-			}
-			const int rowLo = pyc - 3 - sy0;
-			if (rowLo + 6 < 0 || rowLo >= srows)
-			{
-				continue;
-			}
-			double wx[7], wy[7];
-			axis_taps(fx, c.norm, c, wx);
-			axis_taps(fy, 1.0, c, wy);
-			const int colLo = pxc - 3 - x0;
-			const double g = tau * c.inv_sigsq;
-			// columns outside the canvas carry no tap: zero weight, clamped address
-			double ax[7];
-			int ci[7];
-			double sumW = 0.0, sumA = 0.0;
-#pragma unroll
-			for (int i = 0; i < 7; ++i)
-			{
-				const int col = colLo + i;
-				const bool ok = col >= 0 && col < cols;
-				wx[i] = ok ? wx[i] : 0.0;
-				ax[i] = wx[i] * (g * (static_cast<double>(i - 3) - fx));
-				ci[i] = min(max(col, 0), cols - 1);
-				sumW += wx[i];
-				sumA += ax[i];
-			}
-			double sumWy = 0.0, sumAy = 0.0, d2a = 0.0, d2b = 0.0;
-#pragma unroll
-			for (int j = 0; j < 7; ++j)
-			{
-				const int row = rowLo + j;
-				if (row < 0 || row >= srows)
-				{
-					continue;
-				}
-				const double ay = wy[j] * (g * (static_cast<double>(j - 3) - fy));
-				sumWy += wy[j];
-				sumAy += ay;
-				const double* rowp = img + row * cols;
-				double ra = 0.0, rb = 0.0;
-#pragma unroll
-				for (int i = 0; i < 7; ++i)
-				{
-					const double I = rowp[ci[i]];
-					ra = fma(ax[i], I, ra);
-					rb = fma(wx[i], I, rb);
-				}
-				d2a = fma(wy[j], ra, d2a);
-				d2b = fma(ay, rb, d2b);
-			}
-			S[3] = fma(sumA, sumWy, S[3]);
-			S[4] = fma(sumW, sumAy, S[4]);
-			S[5] += d2a;
-			S[6] += d2b;
-		}
-	}
-	block_sum<7>(S, red);
-}
-
-#ifdef EBO_AB  // second-generation evaluation (impl 1 / 2): kept for A/B against k_eval3, not shipped
-template <bool FIXED, bool ROT>
-__global__ void __launch_bounds__(512) k_eval2(const uint64_t* __restrict__ events, const Unit* __restrict__ units,
-						const double* __restrict__ flows, int tiles, int wantJac, int capDoubles,
-						double fdStep, double* __restrict__ partials, double* __restrict__ out,
-						EvalConsts c)
-{
-	extern __shared__ double lds[];
-	const int unit = blockIdx.x / tiles;
-	const int tile = blockIdx.x - unit * tiles;
-	const int set = blockIdx.y;
-	const Unit u = units[unit];
-	double* part = partials + ((static_cast<size_t>(set) * gridDim.x) + blockIdx.x) * kPartialStride;
-	const bool fused = (tiles == 1 && gridDim.y == 1);
-	if (!(u.flags & kUnitActive))
-	{
-		if (!fused && threadIdx.x < 7)
-		{
-			part[threadIdx.x] = 0.0;
-		}
-		if (fused && !(u.flags & kUnitStray) && threadIdx.x < 3)
-		{
-			out[3 * u.flow_idx + threadIdx.x] = 0.0;
-		}
-		return;
-	}
-	double m0 = flows[2 * u.flow_idx];
-	double m1 = flows[2 * u.flow_idx + 1];
-	fd_offset(set, fdStep, m0, m1);
-	double S[7];
-	eval_unit2<FIXED, ROT>(events + u.ev_off, u, m0, m1, wantJac != 0, tile, tiles, capDoubles, c, lds,
-						   S);
-	if (threadIdx.x == 0)
-	{
-		if (fused)
-		{
-			double r, j0 = 0.0, j1 = 0.0;
-			variance_from_sums(S, wantJac != 0, m0, m1, c.max_res, r, j0, j1);
-			out[3 * u.flow_idx + 0] = r;
-			out[3 * u.flow_idx + 1] = j0;
-			out[3 * u.flow_idx + 2] = j1;
-		}
-		else
-		{
-#pragma unroll
-			for (int k = 0; k < 7; ++k)
-			{
-				part[k] = S[k];
-			}
-		}
-	}
-}
-#endif  // EBO_AB
-
-#ifdef EBO_AB
-// ---------------------------------------------------------------------------
-// First-generation batched evaluation (impl 0, kept for A/B): full 3W x 3H canvas,
-// one f64 atomic per tap and channel.  Workgroup = (flow set, unit, row tile).
-// ---------------------------------------------------------------------------
-template <int C>
-__global__ void k_eval_variance(const uint64_t* __restrict__ events,
-								const Unit* __restrict__ units, const double* __restrict__ flows,
-								int tiles, double fdStep, double* __restrict__ partials,
-								double* __restrict__ out, EvalConsts c)
-{
-	extern __shared__ double lds[];
-	const int unit = blockIdx.x / tiles;
-	const int tile = blockIdx.x - unit * tiles;
-	const int set = blockIdx.y;
-	const Unit u = units[unit];
-	double* part = partials + ((static_cast<size_t>(set) * gridDim.x) + blockIdx.x) * kPartialStride;
-	const bool fused = (tiles == 1 && gridDim.y == 1);
-	if (!(u.flags & kUnitActive))
-	{
-		if (threadIdx.x < 7)
-		{
-			part[threadIdx.x] = 0.0;
-		}
-		if (fused && !(u.flags & kUnitStray) && threadIdx.x < 3)
-		{
-			out[3 * u.flow_idx + threadIdx.x] = 0.0;
-		}
-		return;
-	}
-	const int W3 = 3 * u.rw;
-	const int H3 = 3 * u.rh;
-	const int R = (H3 + tiles - 1) / tiles;
-	const int r0 = tile * R;
-	const int rows = min(R, H3 - r0);
-	double S[7] = {0, 0, 0, 0, 0, 0, 0};
-	double m0 = flows[2 * u.flow_idx];
-	double m1 = flows[2 * u.flow_idx + 1];
-	fd_offset(set, fdStep, m0, m1);
-	if (rows > 0)
-	{
-		const int plane = rows * W3;
-		double* red = lds + C * plane;
-		for (int i = threadIdx.x; i < C * plane; i += blockDim.x)
-		{
-			lds[i] = 0.0;
-		}
-		__syncthreads();
-		splat_rows<C>(events + u.ev_off, u.n_ev, u.rx, u.ry, u.rw, u.rh, r0, rows, m0, m1, c,
-					  lds, plane);
-		__syncthreads();
-		tile_sums<C>(lds, plane, red, S);
-	}
-	if (threadIdx.x == 0)
-	{
-#pragma unroll
-		for (int k = 0; k < 7; ++k)
-		{
-			part[k] = S[k];
-		}
-		if (fused)
-		{
-			double r, j0 = 0.0, j1 = 0.0;
-			variance_from_sums(S, C == 3, m0, m1, c.max_res, r, j0, j1);
-			out[3 * u.flow_idx + 0] = r;
-			out[3 * u.flow_idx + 1] = j0;
-			out[3 * u.flow_idx + 2] = j1;
-		}
-	}
-}
-#endif  // EBO_AB
 
 // Adds the row tiles of each unit in tile order and finishes the objective.
 // flow sets: 1 (C = 1 or 3), or 5 value-only sets for central differences.
@@ -965,27 +548,15 @@ __global__ void k_dump_image(const uint64_t* __restrict__ events, const Unit* __
 // ---------------------------------------------------------------------------
 #include "ebo_eval3.inc"
 
-// FIXED: 1 = impl 1 (f64 atomics), 2 = impl 2, 3 = impl 3 with exp_small, 4 = impl 3
-// with the library exp.
-template <int FIXED>
-__device__ __forceinline__ void eval_unit(const uint64_t* __restrict__ ev, const Unit& u,
-										   double m0, double m1, bool wantJac, int capDoubles,
-										   const EvalConsts& c, double* lds, double& r, double& j0,
-										   double& j1, EvalReuse* ru = nullptr)
+// The objective and its Jacobian at (m0, m1) of a unit evaluated as one row band.  (A function of its own: written
+// out inside k_solve_independent, the same statements compile to a different instruction schedule.)
+template <bool SMALL>
+__device__ __forceinline__ void eval_unit(const uint64_t* __restrict__ ev, const Unit& u, double m0, double m1,
+										   bool wantJac, int capDoubles, const EvalConsts& c, double* lds, double& r,
+										   double& j0, double& j1, EvalReuse* ru)
 {
 	double S[7];
-	if (FIXED == 3)
-	{
-		eval_unit3<true>(ev, u, m0, m1, wantJac, 0, 1, capDoubles, c, lds, S, ru);
-	}
-	else if (FIXED == 4)
-	{
-		eval_unit3<false>(ev, u, m0, m1, wantJac, 0, 1, capDoubles, c, lds, S, ru);
-	}
-	else
-	{
-		eval_unit2<FIXED == 2, false>(ev, u, m0, m1, wantJac, 0, 1, capDoubles, c, lds, S);
-	}
+	eval_unit3<SMALL>(ev, u, m0, m1, wantJac, 0, 1, capDoubles, c, lds, S, ru);
 	j0 = 0.0;
 	j1 = 0.0;
 	variance_from_sums(S, wantJac, m0, m1, c.max_res, r, j0, j1);
@@ -1262,7 +833,8 @@ struct LmUnit
 	}
 };
 
-template <int FIXED>
+// SMALL: exp_small (sigma >= 1) instead of the library exp (ebo_eval3.inc)
+template <bool SMALL>
 __global__ void __launch_bounds__(512) k_solve_independent(const uint64_t* __restrict__ events,
 									const Unit* __restrict__ units, int capDoubles,
 									double* __restrict__ flowsOut, int32_t* __restrict__ stats,
@@ -1284,7 +856,7 @@ __global__ void __launch_bounds__(512) k_solve_independent(const uint64_t* __res
 		LmUnit& lm = *reinterpret_cast<LmUnit*>(lds + 64);
 		// the record of the image in LDS (ebo_eval3.inc, EvalReuse): doubles 148..157 of the header, behind the 32
 		// ints the bounding-box reduction uses (at most eight waves)
-		EvalReuse* ru = (FIXED >= 3 && !noReuse) ? reinterpret_cast<EvalReuse*>(lds + kRedDoubles + 20) : nullptr;
+		EvalReuse* ru = !noReuse ? reinterpret_cast<EvalReuse*>(lds + kRedDoubles + 20) : nullptr;
 		static_assert(sizeof(EvalReuse) <= (kLdsHeader - kRedDoubles - 20) * sizeof(double), "EvalReuse must fit the header");
 		if (threadIdx.x == 0)
 		{
@@ -1304,7 +876,7 @@ __global__ void __launch_bounds__(512) k_solve_independent(const uint64_t* __res
 			const double q0 = lm.q0, q1 = lm.q1;
 			const bool qJac = lm.qJac;
 			double r, a, b;
-			eval_unit<FIXED>(ev, u, q0, q1, qJac, capDoubles, c, lds, r, a, b, ru);
+			eval_unit<SMALL>(ev, u, q0, q1, qJac, capDoubles, c, lds, r, a, b, ru);
 			if (threadIdx.x == 0)
 			{
 				lm.more = lm.advance(r, a, b, o) ? 1 : 0;
@@ -2981,57 +2553,25 @@ int launch_eval_variance(const EvalLaunch& L, void* stream)
 		return 0;
 	}
 	const dim3 grid(L.n_units * L.tiles, L.flow_sets);
-#ifdef EBO_AB
-	if (L.impl == 0)
+	auto kern = (L.c.inv_sigsq <= 1.0) ? k_eval3<true> : k_eval3<false>;
+	if (allow_big_lds(kern, L.lds_bytes))
 	{
-		auto kern = (L.channels == 3) ? k_eval_variance<3> : k_eval_variance<1>;
-		if (allow_big_lds(kern, L.lds_bytes))
-		{
-			return -2;
-		}
-		hipLaunchKernelGGL(kern, grid, dim3(L.block), L.lds_bytes, s, L.d_events, L.d_units,
-						   L.d_flows, L.tiles, L.fd_step, L.d_partials, L.d_out, L.c);
+		return -2;
 	}
-	else if (L.impl < 3)
+	const bool fusedPath = L.tiles == 1 && L.flow_sets == 1;
+	LiveWindows live = L.live;
+	if (!fusedPath)
 	{
-		auto kern = (L.impl == 2) ? (L.rotate ? k_eval2<true, true> : k_eval2<true, false>)
-								  : (L.rotate ? k_eval2<false, true> : k_eval2<false, false>);
-		if (allow_big_lds(kern, L.lds_bytes))
-		{
-			return -2;
-		}
-		hipLaunchKernelGGL(kern, grid, dim3(L.block), L.lds_bytes, s, L.d_events, L.d_units,
-						   L.d_flows, L.tiles, L.channels == 3 ? 1 : 0, L.cap_doubles, L.fd_step,
-						   L.d_partials, L.d_out, L.c);
+		live.n = 0;
 	}
-	else
-#endif  // EBO_AB
-	{
-#ifdef EBO_AB
-		auto kern = (L.c.inv_sigsq <= 1.0) ? (L.deal ? k_eval3<true, true> : k_eval3<true, false>)
-										   : (L.deal ? k_eval3<false, true> : k_eval3<false, false>);
-#else
-		auto kern = (L.c.inv_sigsq <= 1.0) ? k_eval3<true, false> : k_eval3<false, false>;
-#endif
-		if (allow_big_lds(kern, L.lds_bytes))
-		{
-			return -2;
-		}
-		const bool fusedPath = L.tiles == 1 && L.flow_sets == 1;
-		LiveWindows live = L.live;
-		if (!fusedPath)
-		{
-			live.n = 0;
-		}
-		hipLaunchKernelGGL(kern, live.n > 0 ? dim3(live.n * live.upw) : grid, dim3(L.block), L.lds_bytes, s, L.d_events, L.d_units,
-						   L.d_flows, L.tiles, L.channels == 3 ? 1 : 0, L.cap_doubles, L.fd_step,
-						   L.d_partials, L.d_out, L.c, fusedPath ? L.d_modes : nullptr, live);
-	}
+	hipLaunchKernelGGL(kern, live.n > 0 ? dim3(live.n * live.upw) : grid, dim3(L.block), L.lds_bytes, s, L.d_events, L.d_units,
+					   L.d_flows, L.tiles, L.channels == 3 ? 1 : 0, L.cap_doubles, L.fd_step,
+					   L.d_partials, L.d_out, L.c, fusedPath ? L.d_modes : nullptr, live);
 	if (check_launch())
 	{
 		return -2;
 	}
-	if (!(L.tiles == 1 && L.flow_sets == 1))
+	if (!fusedPath)
 	{
 		hipLaunchKernelGGL(k_combine_variance, dim3((L.n_units + 127) / 128), dim3(128), 0, s,
 						   L.d_units, L.n_units, L.d_flows, L.tiles, L.flow_sets, L.channels,
@@ -3735,14 +3275,7 @@ int launch_solve_independent(const SolveLaunch& L, void* stream)
 		return 0;
 	}
 	const bool smallExp = L.c.inv_sigsq <= 1.0;
-#ifdef EBO_AB
-	auto kern = (L.impl == 1)   ? k_solve_independent<1>
-				: (L.impl == 2) ? k_solve_independent<2>
-				: smallExp		? k_solve_independent<3>
-								: k_solve_independent<4>;
-#else
-	auto kern = smallExp ? k_solve_independent<3> : k_solve_independent<4>;
-#endif
+	auto kern = smallExp ? k_solve_independent<true> : k_solve_independent<false>;
 	if (allow_big_lds(kern, L.lds_bytes))
 	{
 		return -2;

@@ -15,7 +15,7 @@ os.environ.setdefault("EBO_LIB_PATH", os.path.join(os.path.dirname(os.path.dirna
 ebo = importlib.import_module("event-based-odomety_amd")
 synth = importlib.import_module("event-based-odomety_amd.synth")
 
-KEYS = ("EBO_EVAL_IMPL", "EBO_EVAL_ROT", "EBO_LDS_KB", "EBO_EVAL_TILES", "EBO_EVAL_BLOCK", "EBO_EVAL_DEAL")
+KEYS = ("EBO_LDS_KB", "EBO_EVAL_TILES", "EBO_EVAL_BLOCK")
 
 
 def main():
