@@ -1,7 +1,10 @@
 """CPU restatement of the image front end of include/ebo.h (ebo_image_gradients, ebo_good_features,
 ebo_lk_add_image + ebo_lk_track), written from the rules in that header, plus a reader for the PNG
 fixtures under tests/golden/frontend.  Test infrastructure: the device must agree with this bit for bit
-(gradients, corners) or to the stated tolerance (LK positions)."""
+(gradients, corners, LK positions, status and err).
+
+good_features / greedy and LK.track take an optional `trace`, a collections.Counter that counts the branch each
+candidate or point took (the names are in CORNER_BRANCHES and LK_BRANCHES); results do not depend on it."""
 import math
 import os
 import struct
@@ -13,6 +16,36 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fro
 FRAMES = [os.path.join(GOLDEN, "frame_%08d.png" % i) for i in range(3)]
 
 F32 = np.float32
+
+# the branches a trace counts (what tests/test_front_end_cpu.py requires the GPU sweep to reach)
+LK_BRANCHES = (
+    "skip_bounds_upper",       # floor(p) outside the level at a level > 0: the level is skipped
+    "status0_bounds_l0",       # ... at level 0: status 0 before iterating
+    "skip_mineig_upper",       # minEig < threshold or D < FLT_EPSILON at a level > 0: the level is skipped
+    "status0_mineig_l0",       # ... at level 0: status 0
+    "iter_oob_upper",          # floor(q) outside the level inside the iteration at a level > 0: break, next level
+    "iter_oob_l0",             # ... at level 0: status 0
+    "eps_exit",                # dx^2 + dy^2 <= epsilon^2
+    "half_step_exit",          # |delta + delta_prev| < 0.01: result -= delta / 2
+    "max_count_exhausted",     # max_count iterations without an exit
+    "final_check_fail",        # status 1 until the level-0 position check of the result
+    "err_computed",            # status 1 and err computed
+)
+CORNER_BRANCHES = (
+    "zero_candidates",         # an empty candidate list
+    "sort_lds",                # 1 .. 4096 candidates: the device sorts in LDS
+    "sort_global",             # more than 4096: the global bitonic sort
+    "max_corners_cutoff",      # candidates left over when max_corners were accepted
+    "reject_in_batch",         # too close only to corners accepted in its own batch of 64 sorted candidates
+    "reject_earlier_batch",    # too close to a corner accepted in an earlier batch
+    "accept_near_rejected",    # accepted although closer than min_distance to a rejected candidate
+    "accept_at_min_distance",  # accepted at exactly min_distance ((dx*dx + dy*dy) == min_distance^2) from a corner
+)
+
+
+def _hit(trace, key, n=1):
+    if trace is not None:
+        trace[key] += n
 
 
 # ---- PNG (8-bit grey, not interlaced) ------------------------------------------------------------
@@ -118,37 +151,62 @@ def harris_response(img, block_size=3, k=0.04):
     return det - k * (tr * tr)
 
 
-def good_features(img, mask=None, max_corners=100, quality_level=0.01, min_distance=10.0, block_size=3,
-                  harris_k=0.04):
+def candidates(img, mask=None, quality_level=0.01, block_size=3, harris_k=0.04):
+    """Steps 1-5 of ebo_good_features: the candidates' raster indices y*w + x in selection order."""
     h, w = img.shape
     R = harris_response(img, block_size, harris_k)
     m = np.ones((h, w), dtype=bool) if mask is None else (np.asarray(mask) != 0)
     max_val = R[m].max() if m.any() else 0.0
     thr = quality_level * max_val
     T = np.where(R > thr, R, 0.0)
-    inner = T[1:-1, 1:-1]
-    nb = np.max(np.stack([T[1 + j:h - 1 + j, 1 + i:w - 1 + i] for j in (-1, 0, 1) for i in (-1, 0, 1)]), axis=0)
     keep = np.zeros((h, w), dtype=bool)
-    keep[1:-1, 1:-1] = (inner != 0) & (inner == nb)
+    if h >= 3 and w >= 3:
+        inner = T[1:-1, 1:-1]
+        nb = np.max(np.stack([T[1 + j:h - 1 + j, 1 + i:w - 1 + i] for j in (-1, 0, 1) for i in (-1, 0, 1)]), axis=0)
+        keep[1:-1, 1:-1] = (inner != 0) & (inner == nb)
     keep &= m
     idx = np.flatnonzero(keep)
     r = R.ravel()[idx]
     order = np.lexsort((-idx, -r))  # R descending, ties: larger raster index first
-    return greedy(idx[order], w, max_corners, min_distance)
+    return idx[order]
 
 
-def greedy(sorted_idx, w, max_corners, min_distance):
+def good_features(img, mask=None, max_corners=100, quality_level=0.01, min_distance=10.0, block_size=3,
+                  harris_k=0.04, trace=None):
+    cand = candidates(img, mask, quality_level, block_size, harris_k)
+    return greedy(cand, img.shape[1], max_corners, min_distance, trace)
+
+
+def greedy(sorted_idx, w, max_corners, min_distance, trace=None):
     md2 = min_distance * min_distance
     acc = []
     ax, ay = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
-    for p in sorted_idx:
+    apos = np.zeros(0, dtype=np.int64)  # position of each accepted corner in the sorted list
+    rx, ry = [], []  # rejected candidates (trace only)
+    if trace is not None:
+        _hit(trace, "zero_candidates" if len(sorted_idx) == 0 else
+             ("sort_lds" if len(sorted_idx) <= 4096 else "sort_global"))
+    for pos, p in enumerate(sorted_idx):
         if len(acc) >= max_corners:
+            _hit(trace, "max_corners_cutoff")
             break
         x, y = int(p % w), int(p // w)
-        if len(acc) and np.any(((ax - x) ** 2 + (ay - y) ** 2).astype(np.float64) < md2):
+        d2 = ((ax - x) ** 2 + (ay - y) ** 2).astype(np.float64)
+        close = d2 < md2
+        if len(acc) and np.any(close):
+            if trace is not None:
+                # the device checks the corners of earlier batches first, then the survivors of its own batch
+                _hit(trace, "reject_earlier_batch" if np.any(apos[close] // 64 < pos // 64) else "reject_in_batch")
+                rx.append(x)
+                ry.append(y)
             continue
+        if trace is not None:
+            if np.any(d2 == md2):
+                _hit(trace, "accept_at_min_distance")
+            if rx and np.any((np.subtract(rx, x) ** 2 + np.subtract(ry, y) ** 2).astype(np.float64) < md2):
+                _hit(trace, "accept_near_rejected")
         acc.append((x, y))
-        ax, ay = np.append(ax, x), np.append(ay, y)
+        ax, ay, apos = np.append(ax, x), np.append(ay, y), np.append(apos, pos)
     return np.array(acc, dtype=np.float32).reshape(-1, 2)
 
 
@@ -239,7 +297,8 @@ class LK:
         levels = pyramid(np.asarray(img, dtype=np.uint8))
         self.pyrs = (self.pyrs + [(levels, [scharr(l) for l in levels])])[-2:]
 
-    def track(self, prev_xy, win=(21, 21), max_level=3, max_count=30, epsilon=0.01, min_eig_threshold=1e-4):
+    def track(self, prev_xy, win=(21, 21), max_level=3, max_count=30, epsilon=0.01, min_eig_threshold=1e-4,
+              trace=None):
         if len(self.pyrs) < 2:
             raise RuntimeError("two images are needed")
         (Ilv, Dlv), (Jlv, _) = self.pyrs
@@ -258,11 +317,11 @@ class LK:
         oy, ox = np.divmod(np.arange(ww * wh), ww)
         for k, (px0, py0) in enumerate(pts):
             nxt[k], st[k], err[k] = self._one(Ilv, Dlv, Jlv, n_levels, F32(px0), F32(py0), ox, oy, ww, wh, max_count,
-                                              eps2, F32(min_eig_threshold))
+                                              eps2, F32(min_eig_threshold), trace)
         return nxt, st, err
 
     @staticmethod
-    def _one(Ilv, Dlv, Jlv, n_levels, px0, py0, ox, oy, ww, wh, max_count, eps2, min_eig):
+    def _one(Ilv, Dlv, Jlv, n_levels, px0, py0, ox, oy, ww, wh, max_count, eps2, min_eig, trace=None):
         hx, hy = F32(ww - 1) * F32(0.5), F32(wh - 1) * F32(0.5)
         scale = F32(1.0 / (1 << 20))
         ok = True
@@ -281,6 +340,7 @@ class LK:
             prevX, prevY = prevX - hx, prevY - hy
             ipx, ipy = int(np.floor(prevX)), int(np.floor(prevY))
             if ipx < -ww or ipx >= w or ipy < -wh or ipy >= h:
+                _hit(trace, "status0_bounds_l0" if level == 0 else "skip_bounds_upper")
                 if level == 0:
                     ok = False
                 continue
@@ -296,6 +356,7 @@ class LK:
             disc = dd * dd + (F32(4) * A12) * A12
             minEig = ((A22 + A11) - np.sqrt(disc)) / F32(2 * ww * wh)
             if minEig < min_eig or D < F32(1.19209290e-7):
+                _hit(trace, "status0_mineig_l0" if level == 0 else "skip_mineig_upper")
                 if level == 0:
                     ok = False
                 continue
@@ -305,6 +366,7 @@ class LK:
             for it in range(max_count):
                 iqx, iqy = int(np.floor(qx)), int(np.floor(qy))
                 if iqx < -ww or iqx >= w or iqy < -wh or iqy >= h:
+                    _hit(trace, "iter_oob_l0" if level == 0 else "iter_oob_upper")
                     if level == 0:
                         ok = False
                     break
@@ -317,11 +379,15 @@ class LK:
                 qx, qy = qx + dx, qy + dy
                 resX, resY = qx + hx, qy + hy
                 if float(dx) * float(dx) + float(dy) * float(dy) <= eps2:
+                    _hit(trace, "eps_exit")
                     break
                 if it > 0 and float(abs(dx + pdx)) < 0.01 and float(abs(dy + pdy)) < 0.01:
+                    _hit(trace, "half_step_exit")
                     resX, resY = resX - dx * F32(0.5), resY - dy * F32(0.5)
                     break
                 pdx, pdy = dx, dy
+            else:
+                _hit(trace, "max_count_exhausted")
         e = F32(0)
         if ok:
             I, J = Ilv[0], Jlv[0]
@@ -329,8 +395,10 @@ class LK:
             qx, qy = resX - hx, resY - hy
             iqx, iqy = int(np.floor(qx)), int(np.floor(qy))
             if iqx < -ww or iqx >= w or iqy < -wh or iqy >= h:
+                _hit(trace, "final_check_fail")
                 ok = False
             else:
+                _hit(trace, "err_computed")
                 diff = _sample(J, iqx, iqy, ox, oy, _weights(qx - F32(iqx), qy - F32(iqy))) - Ival
                 e = F32(int(np.sum(np.abs(diff)))) / F32(32 * ww * wh)
         return (resX, resY), int(ok), e

@@ -1,13 +1,18 @@
 """CPU tests of the image front end (include/ebo.h, "image front end"): the ABI and the bindings exist, the
-PNG fixtures read back, and the CPU restatement (tests/frontend_ref.py) the GPU tests compare against behaves
-as the reference's detector and flow estimator are expected to."""
+PNG fixtures read back, the CPU restatement (tests/frontend_ref.py) the GPU tests compare against behaves
+as the reference's detector and flow estimator are expected to and agrees bit for bit with a second, naive
+restatement (per-pixel loops from the text of ebo.h), and the GPU sweep's cases (tests/frontend_cases.py) reach
+every branch of the restatement they are meant to test."""
+import collections
 import ctypes
+import math
 import os
 import zlib
 
 import numpy as np
 import pytest
 
+import frontend_cases as FC
 import frontend_ref as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,3 +105,200 @@ def test_restated_lk_status_zero_on_flat_image_and_outside():
     lk.add_image(b)
     _, st, _ = lk.track(np.array([[-40, 90], [120, 300], [120, 90]], dtype=np.float32))
     assert st.tolist() == [0, 0, 1]
+
+
+# ---- a second, naive restatement: per-pixel loops straight from the text of ebo.h -----------------------------
+def naive_refl(i, n):
+    """BORDER_REFLECT_101 by its definition (..., 2, 1 | 0 .. n-1 | n-2, ...): mirror until inside."""
+    if n == 1:
+        return 0
+    while i < 0 or i >= n:
+        i = -i if i < 0 else 2 * (n - 1) - i
+    return i
+
+
+def naive_gradients(img):
+    h, w = img.shape
+    L = [math.log(v * (1.0 / 255.0) + 10e-2) / 8 for v in range(256)]
+
+    def at(x, y):
+        return L[int(img[naive_refl(y, h), naive_refl(x, w)])]
+
+    gx, gy = np.zeros((h, w)), np.zeros((h, w))
+    for y in range(h):
+        for x in range(w):
+            r = [at(x + 1, y + j) - at(x - 1, y + j) for j in (-1, 0, 1)]
+            s = [(at(x - 1, y + j) + 2 * at(x, y + j)) + at(x + 1, y + j) for j in (-1, 0, 1)]
+            gx[y, x] = (r[0] + 2 * r[1]) + r[2]
+            gy[y, x] = s[2] - s[0]
+    return gx, gy
+
+
+def naive_harris(img, bs, k):
+    h, w = img.shape
+
+    def I(x, y):
+        return int(img[naive_refl(y, h), naive_refl(x, w)])
+
+    def sobel(x, y):
+        dx = (I(x + 1, y - 1) + 2 * I(x + 1, y) + I(x + 1, y + 1)) - \
+            (I(x - 1, y - 1) + 2 * I(x - 1, y) + I(x - 1, y + 1))
+        dy = (I(x - 1, y + 1) + 2 * I(x, y + 1) + I(x + 1, y + 1)) - \
+            (I(x - 1, y - 1) + 2 * I(x, y - 1) + I(x + 1, y - 1))
+        return dx, dy
+
+    D = [[sobel(x, y) for x in range(w)] for y in range(h)]
+    R = np.zeros((h, w))
+    for y in range(h):
+        for x in range(w):
+            A = B = C = 0
+            for yy in range(y - bs // 2, y - bs // 2 + bs):
+                for xx in range(x - bs // 2, x - bs // 2 + bs):
+                    dx, dy = D[naive_refl(yy, h)][naive_refl(xx, w)]
+                    A, B, C = A + dx * dx, B + dx * dy, C + dy * dy
+            R[y, x] = float(A * C - B * B) - k * (float(A + C) * float(A + C))
+    return R
+
+
+def naive_good_features(img, mask, max_corners, quality_level, min_distance, block_size, harris_k):
+    h, w = img.shape
+    R = naive_harris(img, block_size, harris_k)
+    inside = [(x, y) for y in range(h) for x in range(w) if mask is None or mask[y, x] != 0]
+    max_val = max(R[y, x] for x, y in inside) if inside else 0.0
+    thr = quality_level * max_val
+
+    def T(x, y):
+        return R[y, x] if R[y, x] > thr else 0.0
+
+    cand = []
+    for y in range(1, h - 1):
+        for x in range(1, w - 1):
+            if (mask is None or mask[y, x] != 0) and T(x, y) != 0 and \
+                    T(x, y) == max(T(x + i, y + j) for j in (-1, 0, 1) for i in (-1, 0, 1)):
+                cand.append((-R[y, x], -(y * w + x), x, y))
+    acc = []
+    for _, _, x, y in sorted(cand):
+        if len(acc) >= max_corners:
+            break
+        if all(not (float((x - ax) * (x - ax) + (y - ay) * (y - ay)) < min_distance * min_distance) for ax, ay in acc):
+            acc.append((x, y))
+    return np.array(acc, dtype=np.float32).reshape(-1, 2)
+
+
+def naive_pyr_down(img):
+    h, w = img.shape
+    k = (1, 4, 6, 4, 1)
+    out = np.zeros(((h + 1) // 2, (w + 1) // 2), np.uint8)
+    for y in range(out.shape[0]):
+        for x in range(out.shape[1]):
+            s = sum(k[j] * k[i] * int(img[naive_refl(2 * y + j - 2, h), naive_refl(2 * x + i - 2, w)])
+                    for j in range(5) for i in range(5))
+            out[y, x] = (s + 128) >> 8
+    return out
+
+
+def naive_scharr(img):
+    h, w = img.shape
+
+    def I(x, y):
+        return int(img[naive_refl(y, h), naive_refl(x, w)])
+
+    def v0(x, y):
+        return 3 * (I(x, y - 1) + I(x, y + 1)) + 10 * I(x, y)
+
+    def v1(x, y):
+        return I(x, y + 1) - I(x, y - 1)
+
+    ix, iy = np.zeros((h, w), np.int64), np.zeros((h, w), np.int64)
+    for y in range(h):
+        for x in range(w):
+            ix[y, x] = v0(x + 1, y) - v0(x - 1, y)
+            iy[y, x] = 3 * (v1(x - 1, y) + v1(x + 1, y)) + 10 * v1(x, y)
+    return ix, iy
+
+
+TINY = [(1, 1), (1, 5), (5, 1), (2, 3), (3, 2), (7, 7), (13, 9), (9, 13)]  # (h, w)
+
+
+def tiny_images(h, w):
+    rng = np.random.default_rng(h * 100 + w)
+    yield rng.integers(0, 256, size=(h, w), dtype=np.uint8)
+    yield (rng.integers(0, 2, size=(h, w)) * 255).astype(np.uint8)
+
+
+def test_naive_refl_matches_restatement():
+    for n in (1, 2, 3, 5, 16):
+        i = np.arange(-40, 41)
+        assert F.refl(i, n).tolist() == [naive_refl(int(v), n) for v in i], n
+
+
+def test_gradients_pyramid_and_scharr_match_the_naive_restatement():
+    for h, w in TINY:
+        for img in tiny_images(h, w):
+            gx, gy = F.image_gradients(img)
+            nx, ny = naive_gradients(img)
+            assert np.array_equal(gx.view(np.uint64), nx.view(np.uint64)), (h, w)
+            assert np.array_equal(gy.view(np.uint64), ny.view(np.uint64)), (h, w)
+            assert np.array_equal(F.pyr_down(img), naive_pyr_down(img)), (h, w)
+            sx, sy = F.scharr(img)
+            nx, ny = naive_scharr(img)
+            assert np.array_equal(sx, nx) and np.array_equal(sy, ny), (h, w)
+
+
+@pytest.mark.parametrize("block_size", [1, 2, 3, 4, 5, 6, 7])
+def test_harris_and_selection_match_the_naive_restatement(block_size):
+    for h, w in TINY:
+        for img in tiny_images(h, w):
+            for k in (0.04, 0.0, -0.04, 0.25):
+                R = F.harris_response(img, block_size, k)
+                assert np.array_equal(R.view(np.uint64), naive_harris(img, block_size, k).view(np.uint64)), (h, w, k)
+            mask = np.random.default_rng(block_size).choice(np.array([0, 7, 255], np.uint8), size=img.shape)
+            for m in (None, mask):
+                for q, md, mc in ((0.0, 0.0, 100), (0.01, 1.5, 100), (0.0, 2.0, 2), (0.5, math.inf, 3)):
+                    want = naive_good_features(img, m, mc, q, md, block_size, 0.04)
+                    got = F.good_features(img, m, mc, q, md, block_size, 0.04)
+                    assert np.array_equal(got, want), (h, w, q, md, mc)
+
+
+def test_greedy_matches_the_naive_pick_at_distance_ties():
+    # a lattice of equal responses: distances 3, 4, 5 occur; min_distance there and one ulp on either side
+    img = FC.checker(40, 32, 4)
+    for d in (3.0, 4.0, 5.0, math.sqrt(2.0)):
+        for md in (float(np.nextafter(d, 0.0)), d, float(np.nextafter(d, math.inf))):
+            for mc in (5, 1000):
+                want = naive_good_features(img, None, mc, 0.0, md, 3, 0.04)
+                assert np.array_equal(F.good_features(img, None, mc, 0.0, md, 3, 0.04), want), (md, mc)
+
+
+# ---- the GPU sweep reaches every branch it claims to ------------------------------------------------------------
+def test_sweep_reaches_every_lk_branch():
+    trace = collections.Counter()
+    for _, kind, pts, kw in FC.lk_cases():
+        FC.lk_restated(kind).track(pts, trace=trace, **kw)
+    missing = [b for b in F.LK_BRANCHES if trace[b] == 0]
+    assert not missing, (missing, dict(trace))
+
+
+def test_sweep_reaches_every_corner_branch():
+    trace = collections.Counter()
+    for _, img, mask, kw in list(FC.corner_cases()) + list(FC.tie_cases()):
+        F.good_features(img, mask, trace=trace, **kw)
+    missing = [b for b in F.CORNER_BRANCHES if trace[b] == 0]
+    assert not missing, (missing, dict(trace))
+
+
+def test_trace_does_not_change_results():
+    _, kind, pts, kw = next(FC.lk_cases())
+    lk = FC.lk_restated(kind)
+    for a, b in zip(lk.track(pts, **kw), lk.track(pts, trace=collections.Counter(), **kw)):
+        assert np.array_equal(a, b)
+    _, img, mask, kw = next(FC.tie_cases())
+    traced = F.good_features(img, mask, trace=collections.Counter(), **kw)
+    assert np.array_equal(F.good_features(img, mask, **kw), traced)
+
+
+def test_selection_masks_leave_the_requested_candidate_counts():
+    for kind in ("noise", "checker"):
+        for n in FC.SELECT_COUNTS:
+            img, _ = FC.select_base(kind)
+            assert len(F.candidates(img, FC.select_mask(kind, n), 0.0, 3, 0.04)) == n, (kind, n)

@@ -1,5 +1,5 @@
 """The image front end on the MI355X (include/ebo.h, "image front end") against the CPU restatement of its
-rules (tests/frontend_ref.py): gradients and corners bit for bit, LK status exactly and positions to 1e-3 px,
+rules (tests/frontend_ref.py): gradients, corners and LK (positions, status, err) bit for bit,
 the gradients installed for the per-feature objective, and the C++ facade's FeatureDetector::useDeviceFrontEnd
 driven through newImage (tests/cpp/front_end_device_test.cpp)."""
 import os
@@ -95,8 +95,8 @@ def test_lk_fixture_frames_against_restatement(ebo):
             assert np.array_equal(s, rs)
             ok = s == 1
             assert ok.sum() > 5
-            np.testing.assert_allclose(n[ok], rn[ok], atol=1e-3)
-            np.testing.assert_allclose(e[ok], re[ok], atol=1e-3)
+            assert np.array_equal(n.view(np.uint32), rn.view(np.uint32))
+            assert np.array_equal(e.view(np.uint32), re.view(np.uint32))
 
 
 def test_lk_synthetic_shifts_and_status(ebo):
@@ -108,7 +108,7 @@ def test_lk_synthetic_shifts_and_status(ebo):
             (n, s, _), (rn, rs, _) = _lk_pair(c, a, b, pts)
             assert s.all() and np.array_equal(s, rs)
             np.testing.assert_allclose(n - pts, np.tile(np.float32(shift), (len(pts), 1)), atol=0.05)
-            np.testing.assert_allclose(n, rn, atol=1e-3)
+            assert np.array_equal(n.view(np.uint32), rn.view(np.uint32))
         a, b = F.shifted(big, 180, 240, 1, 1)
         edge = np.array([[-40, 90], [120, 300], [239.5, 90], [0, 0], [-5, -5], [120, 90]], dtype=np.float32)
         (n, s, _), (rn, rs, _) = _lk_pair(c, a, b, edge)
