@@ -1008,94 +1008,98 @@ int run_solve_device(ebo_ctx* c, const ebo_solver_opts* o, double* d_flows_out, 
 	return EBO_OK;
 }
 
+// Grows a device buffer to `bytes`; while recording a graph it may not (a recorded call cannot allocate).
+static int grow_count_buffer(ebo_ctx* c, void** buf, size_t& cap, size_t bytes, const char* what)
+{
+	if (bytes <= cap)
+	{
+		return EBO_OK;
+	}
+	if (c->capturing)
+	{
+		return c->fail(EBO_ERR_STATE, "this count image needs a larger buffer than the context holds: count once before recording");
+	}
+	hipFree(*buf);
+	*buf = nullptr;
+	cap = 0;
+	int rc = c->hip(hipMalloc(buf, bytes), what);
+	if (rc == EBO_OK)
+	{
+		cap = bytes;
+	}
+	return rc;
+}
+
 int count_device(ebo_ctx* c, int mode, const void* d_aux, double* d_image)
 {
 	if (c->custom_n)
 	{
 		return c->fail(EBO_ERR_STATE, "count images need a window (ebo_set_window), not ebo_set_patches");
 	}
+	CountShape S;
+	S.mode = mode;
+	S.image_w = c->prm.image_w;
+	S.image_h = c->prm.image_h;
+	S.patch_w = c->prm.patch_w;
+	S.patch_h = c->prm.patch_h;
+	S.npx = c->npx;
+	S.npy = c->npy;
+	S.windows = c->n_windows;
+	S.units = static_cast<int>(c->units.size());
+	for (const WindowInfo& wi : c->windows)
+	{
+		S.max_window_events = std::max<uint64_t>(S.max_window_events, wi.n_events);
+		S.total_events += wi.n_events;  // the windows' events are packed back to back from 0
+	}
+	for (int w = 0; w < c->n_windows && !S.any_stray; ++w)
+	{
+		S.any_stray = c->units[static_cast<size_t>(w) * (c->P + 1) + c->P].n_ev > 0;
+	}
+	{
+		const char* v = ab_env("EBO_COUNT_IMPL");
+		S.impl = (v && *v) ? std::atoi(v) : -1;
+	}
+	S.lds_kb = static_cast<int>(std::min<size_t>(ab_size("EBO_COUNT_LDS_KB", 0), 160));
+	S.tile_w = ab_size("EBO_COUNT_TILE_W", 0);
+	S.tile_h = ab_size("EBO_COUNT_TILE_H", 0);
+	if (const char* be = ab_env("EBO_COUNT_BLOCK"); be && *be)
+	{
+		S.block = std::max(64, std::min(1024, (std::atoi(be) / 64) * 64));
+	}
+	if (const char* v = ab_env("EBO_COUNT_COLTILES"))
+	{
+		S.col_tiles = std::atoi(v);
+	}
 	CountLaunch L;
+	L.plan = plan_count_image(S);
 	L.d_events = c->d_events;
 	L.d_units = c->d_units;
-	L.n_units_total = static_cast<int>(c->units.size());
 	L.n_windows = c->n_windows;
 	L.units_per_window = c->P + 1;
 	L.mode = mode;
-	{
-		const char* v = ab_env("EBO_COUNT_IMPL");
-		L.impl = (v && *v) ? std::atoi(v) : -1;
-	}
-	L.lds_kb = static_cast<int>(std::min<size_t>(ab_size("EBO_COUNT_LDS_KB", 0), 160));
-	L.max_window_events = 0;
-	for (const WindowInfo& wi : c->windows)
-	{
-		L.max_window_events = std::max<uint64_t>(L.max_window_events, wi.n_events);
-	}
-	for (int w = 0; w < c->n_windows && !L.any_stray; ++w)
-	{
-		L.any_stray = c->units[static_cast<size_t>(w) * (c->P + 1) + c->P].n_ev > 0;
-	}
+	L.d_unit_maxdt = c->d_unit_maxdt;
+	L.d_sort_bins = nullptr;
+	L.d_sorted = nullptr;
 	L.d_aux = d_aux;
 	L.d_counts = c->d_counts;
 	L.d_image = d_image;
 	L.c = make_consts(c);
-	L.d_overflow = nullptr;
-	L.d_sort_bins = nullptr;
-	L.sort_bins_cap = 0;
-	L.d_sorted = nullptr;
-	L.sorted_cap = 0;
-	L.d_unit_maxdt = c->d_unit_maxdt;
-	if (L.impl < 0 || L.impl == 2 || L.impl == 3)
+	if (L.plan.kind == kCountSorted)
 	{
-		size_t total = 0;
-		for (const WindowInfo& wi : c->windows)
+		// the destination list in two halves of list_events entries (4 B each); bins: counts, starts, cursors
+		int rc = grow_count_buffer(c, reinterpret_cast<void**>(&c->d_count_sorted), c->count_sorted_cap,
+								   2 * L.plan.list_events * sizeof(unsigned int), "hipMalloc count sorted list");
+		if (rc == EBO_OK)
 		{
-			total += wi.n_events;
+			rc = grow_count_buffer(c, reinterpret_cast<void**>(&c->d_count_bins), c->count_bins_cap,
+								   (3 * static_cast<size_t>(L.plan.bins) + 2) * sizeof(unsigned int), "hipMalloc count bins");
 		}
-		const size_t need = (total + 1) * sizeof(unsigned long long);
-		if (need > c->count_ovf_cap)
+		if (rc)
 		{
-			if (c->d_count_ovf)
-			{
-				hipFree(c->d_count_ovf);
-				c->d_count_ovf = nullptr;
-				c->count_ovf_cap = 0;
-			}
-			const size_t cap = std::max(need, (static_cast<size_t>(c->prm.max_events) + 1) * sizeof(unsigned long long));
-			int rc = c->hip(hipMalloc(reinterpret_cast<void**>(&c->d_count_ovf), cap), "hipMalloc count overflow list");
-			if (rc)
-			{
-				return rc;
-			}
-			c->count_ovf_cap = cap;
+			return rc;
 		}
-		L.d_overflow = c->d_count_ovf;
-		if (mode != EBO_COUNT_INTEGRATED)
-		{
-			// sorted bands: the same buffer holds the 4-byte destination list; bins: at most one
-			// band per image row
-			const size_t bins = static_cast<size_t>(c->n_windows) * c->prm.image_h;
-			if (bins > c->count_bins_cap)
-			{
-				if (c->d_count_bins)
-				{
-					hipFree(c->d_count_bins);
-					c->d_count_bins = nullptr;
-					c->count_bins_cap = 0;
-				}
-				int rc = c->hip(hipMalloc(reinterpret_cast<void**>(&c->d_count_bins), (3 * bins + 2) * sizeof(unsigned int)),
-								"hipMalloc count bins");
-				if (rc)
-				{
-					return rc;
-				}
-				c->count_bins_cap = bins;
-			}
-			L.d_sort_bins = c->d_count_bins;
-			L.sort_bins_cap = static_cast<int>(std::min<size_t>(c->count_bins_cap, 1u << 30));
-			L.d_sorted = reinterpret_cast<unsigned int*>(c->d_count_ovf);
-			L.sorted_cap = c->count_ovf_cap / sizeof(unsigned long long);  // the buffer holds 8 B per event: two 4 B lists
-		}
+		L.d_sort_bins = c->d_count_bins;
+		L.d_sorted = c->d_count_sorted;
 	}
 	if (launch_count_image(L, c->stream))
 	{
@@ -1548,7 +1552,7 @@ void ebo_destroy(ebo_ctx* c)
 	hipFree(c->d_route_xy);
 	hipFree(c->d_partials);
 	hipFree(c->d_counts);
-	hipFree(c->d_count_ovf);
+	hipFree(c->d_count_sorted);
 	hipFree(c->d_count_bins);
 	hipFree(c->d_opt_grid);
 	hipFree(c->d_modes);

@@ -80,10 +80,10 @@ struct ebo_ctx
 	bool opt_grid_valid = false;
 	void* d_opt = nullptr;           // scratch of ebo_optimizer_eval / _solve
 	size_t opt_cap = 0;
-	unsigned long long* d_count_ovf = nullptr;  // k_count_bands' overflow list / k_csort_* sorted list
-	size_t count_ovf_cap = 0;
+	unsigned int* d_count_sorted = nullptr;     // k_csort_*: destination list (two halves); sized by the plan of the largest call
+	size_t count_sorted_cap = 0;                // in bytes
 	unsigned int* d_count_bins = nullptr;       // k_csort_*: counts, starts, cursors per (window, band)
-	size_t count_bins_cap = 0;                  // in bins
+	size_t count_bins_cap = 0;                  // in bytes
 	int32_t* d_stats = nullptr;
 	void* d_scratch = nullptr;  // patch-integrate staging
 	size_t scratch_cap = 0;

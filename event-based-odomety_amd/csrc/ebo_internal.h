@@ -3,6 +3,7 @@
 #pragma once
 
 #include "ab_env.h"
+#include "count_plan.h"
 
 #include <stddef.h>
 #include <stdint.h>
@@ -277,25 +278,18 @@ int launch_solve_independent(const SolveLaunch& L, void* stream);
 
 struct CountLaunch
 {
+	CountPlan plan;                  // plan_count_image (count_plan.h): the kernels, their grids and geometry
 	const uint64_t* d_events;
 	const Unit* d_units;
-	int n_units_total;    // patch units + stray units
 	int n_windows;
-	int units_per_window; // P + 1
-	int mode;             // EBO_COUNT_*
-	int impl;             // -1 auto, 0 global int atomics + convert, 1 whole-window LDS bands, 2 patch-row bands, 3 sorted bands
-	int lds_kb;           // LDS per band workgroup (0 = default of the implementation)
-	unsigned long long* d_overflow;  // impl 2: [1 + total events] count + pixel indices (may be null)
-	unsigned int* d_sort_bins;       // impl 3: [3 * sort_bins_cap + 2] counts, starts, cursors (may be null)
-	int sort_bins_cap;               // bins (windows x bands) the buffer holds
-	unsigned int* d_sorted;          // impl 3: [sorted_cap] destination pixels sorted by band, then [sorted_cap] in event order
-	size_t sorted_cap;               // events either half holds
-	const int32_t* d_unit_maxdt;     // [units] max |t_ref(window) - t| per unit (impl 4's displacement bound)
-	uint64_t max_window_events;
-	int any_stray = 0;    // some window has events outside the sensor (impl 6 counts them in a pass of their own)
-	const void* d_aux;    // flows f64 [Wn][P][2] or field f32 [Wn][H][W][2]
-	int32_t* d_counts;    // [Wn][H][W] scratch, zero on entry, zero on exit
-	double* d_image;      // [Wn][H][W]
+	int units_per_window;            // P + 1
+	int mode;                        // EBO_COUNT_*
+	const int32_t* d_unit_maxdt;     // [units] max |t_ref(window) - t| per unit (the unit kernels' displacement bound)
+	unsigned int* d_sort_bins;       // kCountSorted: [3 * bins + 2] counts, starts, cursors
+	unsigned int* d_sorted;          // kCountSorted: [list_events] destination pixels sorted by band, then [list_events] in event order
+	const void* d_aux;               // flows f64 [Wn][P][2] or field f32 [Wn][H][W][2]
+	int32_t* d_counts;               // [Wn][H][W] scratch, zero on entry, zero on exit
+	double* d_image;                 // [Wn][H][W]
 	EvalConsts c;
 };
 int launch_count_image(const CountLaunch& L, void* stream);

@@ -1,9 +1,8 @@
-"""GPU tests of the count-image implementations (0: global int atomics, 1: whole-window LDS
-bands, 2: patch-row LDS bands with an overflow list for events that leave their band, 3: events
-sorted by destination band, 4: unit waves with a displacement bound per unit, 5: unit waves over
-2-D tiles, 6: a rolling band per window that reads every event once, the default for warped images in
-large launches): all
-bit-exact against the oracle, on single windows and on batches, for all three modes."""
+"""GPU tests of the count-image implementations, forced by EBO_COUNT_IMPL in the A/B build (0: global int atomics,
+1: whole-window LDS bands, warped / field; 2: patch-row LDS bands, un-warped; 3: events sorted by destination band,
+warped / field; 4: unit waves with a displacement bound per unit, warped; 5: unit waves over 2-D tiles, warped; a
+forced path that does not serve a mode falls through to the next in plan order, csrc/count_plan.h): all bit-exact
+against the oracle, on single windows and on batches, for all three modes."""
 import numpy as np
 import pytest
 
@@ -68,15 +67,29 @@ def test_count_image_more_than_65535_events_per_window(ebo_ab, orc, synth, monke
 
 
 @pytest.mark.parametrize("lds_kb", ["12", "24", "150"])
-def test_patch_row_bands_any_band_size_and_large_flows(ebo_ab, orc, synth, monkeypatch, lds_kb):
+def test_patch_row_bands_any_band_size(ebo_ab, orc, synth, monkeypatch, lds_kb):
     ebo = ebo_ab  # libebo_hip_ab.so: the build that reads the EBO_* switches (csrc/ab_env.h)
-    """impl 2 with bands of one patch row up to the whole image, flows large enough that most
-    events leave their band (overflow list) or the image."""
+    """impl 2 (the un-warped image) with bands of one patch row up to the whole image, and stray events."""
     monkeypatch.setenv("EBO_COUNT_IMPL", "2")
     monkeypatch.setenv("EBO_COUNT_LDS_KB", lds_kb)
-    cfg = synth.CONFIGS[2]
     ev, offsets, gt = synth.make_stream(2, 5, n_events=20000)
-    ev["x"][3] = -2  # stray events, warped back inside by the flow of their clamped patch
+    ev["x"][3] = -2
+    ev["y"][3] = 100
+    ev["y"][7] = 185
+    with ebo.Context(image_w=240, image_h=180, patch_w=30, patch_h=22, loss=ebo.LOSS_VARIANCE,
+                     max_windows=5, max_events=len(ev)) as c:
+        c.set_windows(ev, offsets)
+        integ = c.count_image(ebo.COUNT_INTEGRATED)
+        for k in range(5):
+            sub = ev[int(offsets[k]):int(offsets[k + 1])]
+            assert np.array_equal(integ[k], orc.integrate_events(sub, 240, 180))
+
+
+def test_warped_count_image_large_flows(ebo, orc, synth):
+    """The default plan with flows large enough that most events leave their patch row or the image, and stray
+    events warped back inside by the flow of their clamped patch."""
+    ev, offsets, gt = synth.make_stream(2, 5, n_events=20000)
+    ev["x"][3] = -2
     ev["y"][3] = 100
     ev["y"][7] = 185
     with ebo.Context(image_w=240, image_h=180, patch_w=30, patch_h=22, loss=ebo.LOSS_VARIANCE,
@@ -86,11 +99,9 @@ def test_patch_row_bands_any_band_size_and_large_flows(ebo_ab, orc, synth, monke
         rng = np.random.RandomState(3)
         flows = rng.uniform(-8, 8, (5, c.P, 2))
         warped = c.count_image(ebo.COUNT_WARPED, flows)
-        integ = c.count_image(ebo.COUNT_INTEGRATED)
         for k in range(5):
             sub = ev[int(offsets[k]):int(offsets[k + 1])]
             assert np.array_equal(warped[k], orc.final_count_image(sub, prm, flows[k]))
-            assert np.array_equal(integ[k], orc.integrate_events(sub, 240, 180))
 
 
 @pytest.mark.parametrize("impl", ["1", "3", "4"])
@@ -128,11 +139,10 @@ def test_patch_of_an_event_from_its_coordinates(ebo_ab, orc, monkeypatch, impl, 
                                                       (346, 260, 21, 16, 50000, 0), (240, 180, 30, 22, 20000, 40)])
 def test_tiled_count_image_odd_sizes_and_wide_counters(ebo_ab, orc, synth, monkeypatch, impl, w, h, pw, ph, n_events, lds_kb):
     ebo = ebo_ab  # libebo_hip_ab.so: the build that reads the EBO_* switches (csrc/ab_env.h)
-    """k_count_tiles (impl 5) and k_count_sweep (impl 6) on sizes that exercise their edges: odd image
-    widths (no 16-byte row stores, packed counters shared between rows), tiles / strips that do not
-    divide the image, 32-bit counters (>= 65536 events per window), tiny tiles and bands (every unit
-    reaches several; the rolling band falls back to band-by-band counting), flows large enough to
-    leave the image or NaN, stray events."""
+    """k_count_tiles (impl 5) on sizes that exercise its edges: odd image widths (no 16-byte row stores,
+    packed counters shared between rows), tiles that do not divide the image, 32-bit counters (>= 65536
+    events per window), tiny tiles (every unit reaches several), flows large enough to leave the image or
+    NaN, stray events; against impl 0 and the oracle."""
     monkeypatch.setenv("EBO_COUNT_IMPL", impl)
     if lds_kb:
         monkeypatch.setenv("EBO_COUNT_LDS_KB", str(lds_kb))

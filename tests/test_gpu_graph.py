@@ -129,3 +129,23 @@ def test_recorded_solve_and_count_image(ebo, synth):
         g.launch(2)
         c.synchronize()
         assert torch.equal(d_sol, ref[0]) and torch.equal(d_img, ref[1]) and float(d_img.sum()) > 0
+
+
+def test_recorded_warped_count_on_a_fresh_context(ebo, synth):
+    """A warped count image recorded as the first call of a context (no buffer sized by an earlier count) replays to the
+    image of the direct call."""
+    import torch
+    c, ev, offsets, gt = _ctx(ebo, synth, ebo.LOSS_VARIANCE)
+    with c:
+        d_flows = torch.from_numpy(np.ascontiguousarray(gt * 0.7)).to("cuda")
+        d_img = torch.zeros((3, 180, 240), dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        g = c.record(lambda: c.count_image_device(ebo.COUNT_WARPED, d_flows.data_ptr(), d_img.data_ptr()))
+        g.launch(1)
+        c.synchronize()
+        replayed = d_img.clone()
+        d_img.zero_()
+        torch.cuda.synchronize()
+        c.count_image_device(ebo.COUNT_WARPED, d_flows.data_ptr(), d_img.data_ptr())
+        c.synchronize()
+        assert torch.equal(replayed, d_img) and float(d_img.sum()) > 0
