@@ -1390,8 +1390,7 @@ int ebo_create(const ebo_params* p, ebo_ctx** out)
 	*out = nullptr;
 	if (p->image_w <= 0 || p->image_h <= 0 || p->patch_w <= 0 || p->patch_h <= 0 ||
 		p->patch_w > p->image_w || p->patch_h > p->image_h || p->image_w > kCoordMax ||
-		p->image_h > kCoordMax || p->max_events == 0 || p->max_windows <= 0 ||
-		!(p->k.sigma_compensate > 0))
+		p->image_h > kCoordMax || p->max_events == 0 || p->max_windows <= 0)
 	{
 		g_create_error = "bad image/patch geometry or capacity";
 		return EBO_ERR_ARG;
@@ -1411,6 +1410,29 @@ int ebo_create(const ebo_params* p, ebo_ctx** out)
 	{
 		g_create_error = "max_events must be below 2^32 - 2^20";
 		return EBO_ERR_ARG;
+	}
+	// functor constants: finite and positive (the negated comparisons also refuse NaN)
+	const auto positive = [](double v) { return v > 0 && v < HUGE_VAL; };
+	const char* bad = !positive(p->k.sigma_compensate)                           ? "sigma_compensate"
+					  : !positive(p->k.sigma_st)                                 ? "sigma_st"
+					  : !positive(p->k.max_possible_residual)                    ? "max_possible_residual"
+					  : (p->grad == EBO_GRAD_CENTRAL && !positive(p->fd_step))   ? "fd_step"
+					  : !(std::fabs(p->scale) < HUGE_VAL)                        ? "scale"
+																				 : nullptr;
+	if (bad)
+	{
+		g_create_error = std::string(bad) + " must be finite" + (std::strcmp(bad, "scale") ? " and > 0" : "");
+		return EBO_ERR_ARG;
+	}
+	if (!(p->k.sigma_compensate >= kSigmaMin && p->k.sigma_compensate <= kSigmaMax))
+	{
+		g_create_error = "sigma_compensate outside [0.25, 1e3], the range the kernels are tested on";
+		return EBO_ERR_UNSUPPORTED;
+	}
+	if (!(p->k.sigma_st >= kSigmaStMin && p->k.sigma_st <= kSigmaStMax))
+	{
+		g_create_error = "sigma_st outside [1, 10], the range the kernels are tested on";
+		return EBO_ERR_UNSUPPORTED;
 	}
 	int cnt = 0;
 	if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0)

@@ -391,6 +391,8 @@ __device__ __forceinline__ void edge_unit(const uint64_t* __restrict__ ev, const
 	const int rx = u.rx, ry = u.ry, rw = u.rw, rh = u.rh;
 	const int W3 = 3 * rw, H3 = 3 * rh;
 	const uint32_t nEv = u.n_ev;
+	double fixBias, fixScale;
+	unit_fix_grid(c, nEv, fixBias, fixScale);
 	const int npx = bc * br;
 	const int nI = bc * iRows;           // I's stored pixels: rows iy0 .. iy1 of the box's columns (nI <= npx)
 	const int iy1 = iy0 + iRows - 1;
@@ -514,8 +516,8 @@ __device__ __forceinline__ void edge_unit(const uint64_t* __restrict__ ev, const
 	if (!reuseFwd)
 #endif
 	{
-		const double biasV = vgpr_pin(c.fix_bias);  // low dword 0 (1.5 * 2^k): removing it is a 32-bit subtract
-		const int biasHi = __double2hiint(c.fix_bias);
+		const double biasV = vgpr_pin(fixBias);  // low dword 0 (1.5 * 2^k): removing it is a 32-bit subtract
+		const int biasHi = __double2hiint(fixBias);
 		for (uint32_t e = threadIdx.x; e < ((ec.ablate & 16) ? 0u : nEv); e += blockDim.x)
 		{
 			int pxc, pyc;
@@ -592,7 +594,7 @@ __device__ __forceinline__ void edge_unit(const uint64_t* __restrict__ ev, const
 		double iMax = 0.0;
 		for (int p = threadIdx.x; p < nI; p += blockDim.x)
 		{
-			const double v = refOrder ? I[p] : static_cast<double>(Iq[p]) * c.fix_scale;
+			const double v = refOrder ? I[p] : static_cast<double>(Iq[p]) * fixScale;
 			I[p] = v;
 			s1[0] += v;
 			iMax = fmax(iMax, v);

@@ -69,13 +69,18 @@ __device__ __forceinline__ void axis_taps3(double f, double pre, const EvalConst
 	w[0] = e3 * (q2 * q);
 }
 
+// SMALL = false: a tap below half a grid step is stored as one step, not 0.  The reference counts every pixel
+// with a value > 0 (contrast_functor.h:113) and the gather sums the derivatives of every tap; for sigma < ~0.6
+// the outer taps fall below the grid (at sigma >= 1 the smallest tap, norm e^-16, is 1e8 steps).
+template <bool SMALL>
 __device__ __forceinline__ unsigned long long fix_tap(double wx, double wy, double bias, int biasHi)
 {
 	const double b = fma(wx, wy, bias);
 	unsigned int hi = static_cast<unsigned int>(__double2hiint(b) - biasHi);
 	keep32(hi);  // ONE 32-bit subtract (ebo_kernels.hip)
 	const unsigned int lo = static_cast<unsigned int>(__double2loint(b));
-	return (static_cast<unsigned long long>(hi) << 32) | lo;
+	const unsigned long long q = (static_cast<unsigned long long>(hi) << 32) | lo;
+	return (!SMALL && q == 0ull && wx * wy > 0.0) ? 1ull : q;
 }
 
 // What a device-resident solve keeps of an evaluation for the NEXT one (k_solve_independent; in LDS behind the
@@ -219,7 +224,9 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 	const int ty0 = y0 + tile * R;
 	const int ty1 = min(ty0 + R, y1 + 1);
 	const int maxRows = max(capDoubles / cols, 1);
-	const int biasHi = __double2hiint(c.fix_bias);
+	double fixBias, fixScale;
+	unit_fix_grid(c, nEv, fixBias, fixScale);
+	const int biasHi = __double2hiint(fixBias);
 
 	for (int sy0 = ty0; sy0 < ty1; sy0 += maxRows)
 	{
@@ -264,7 +271,7 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 #pragma unroll
 					for (int i = 0; i < 7; ++i)
 					{
-						atomicAdd(p + i, fix_tap(wx[i], wy[j], c.fix_bias, biasHi));
+						atomicAdd(p + i, fix_tap<SMALL>(wx[i], wy[j], fixBias, biasHi));
 					}
 					p += cols;
 				}
@@ -285,7 +292,7 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 						const int col = colLo + i;
 						if (col >= 0 && col < bw)
 						{
-							atomicAdd(&imgq[row * cols + col], fix_tap(wx[i], wy[j], c.fix_bias, biasHi));
+							atomicAdd(&imgq[row * cols + col], fix_tap<SMALL>(wx[i], wy[j], fixBias, biasHi));
 						}
 					}
 				}
@@ -300,7 +307,7 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 			for (int p = threadIdx.x; p < npx; p += blockDim.x)
 			{
 				const unsigned long long q = imgq[p];
-				const double I = static_cast<double>(q) * c.fix_scale;
+				const double I = static_cast<double>(q) * fixScale;
 				img[p] = I;
 				if (q != 0ull)
 				{
@@ -492,7 +499,9 @@ template <bool SMALL>
 // What fits the kernel into 128 registers: the seven sums live in per-wave LDS slots instead of registers
 // across the passes, the box and everything derived from it are scalars (readfirstlane), and the gather
 // forms the x-derivative row sum from two accumulators instead of a table of seven derivative weights.
-__global__ void __launch_bounds__(512, 4) k_eval3(const uint64_t* __restrict__ events,
+// The sigma < 1 instantiation (library exp, the one-step floor of fix_tap) is
+// given three waves per SIMD: at four it spills a register.  It is not the reference's sigma.
+__global__ void __launch_bounds__(512, SMALL ? 4 : 3) k_eval3(const uint64_t* __restrict__ events,
 												const Unit* __restrict__ units,
 												const double* __restrict__ flows, int tiles, int wantJac,
 												int capDoubles, double fdStep, double* __restrict__ partials,

@@ -96,6 +96,15 @@ inline __host__ __device__ uint32_t order_inverse(uint32_t st, uint32_t n)
 	return static_cast<uint32_t>(t0 < 0 ? t0 + static_cast<int>(n) : t0) % (n ? n : 1);
 }
 
+// sigma_compensate range ebo_create admits (include/ebo.h): what tests/test_gpu_eval_sweep.py covers
+static const double kSigmaMin = 0.25;
+static const double kSigmaMax = 1e3;  // (at 1e4 the fixed-point grid step is 1.4e-7 of a tap: the variance fails 1e-9)
+// sigma_st range admitted: what the sweep covers (at 0.3 the edge Jacobian turns NaN where the reference's is finite)
+static const double kSigmaStMin = 1.0;
+static const double kSigmaStMax = 10.0;
+// (below 0.25 the variance objective disagrees with the reference: taps underflow, and the three-exp
+// factorisation of a tap gives inf * 0 = NaN below sigma 0.065)
+
 static const uint32_t kUnitActive = 1u;
 static const uint32_t kUnitStray = 2u;
 
@@ -108,8 +117,8 @@ struct EvalConsts
 	double hs;            // -0.5 / sigma^2
 	double inv_sigsq;     // 1 / sigma^2
 	double ck1, ck2, ck3; // exp(hs * k^2), k = 1..3 (factored 1-D Gaussian taps)
-	double fix_bias;      // 1.5 * 2^k: adding it aligns a tap value to the fixed-point grid
-	double fix_scale;     // 2^(k-52): value of one fixed-point unit
+	double fix_bias;      // 1.5 * 2^k: adding it aligns a tap value to the fixed-point grid (k of norm alone;
+	double fix_scale;     // 2^(k-52): value of one fixed-point unit              a unit raises it: unit_fix_grid)
 	int32_t image_w, image_h;
 	int32_t patch_w, patch_h;
 	int32_t npx, npy;

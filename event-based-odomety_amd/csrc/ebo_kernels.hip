@@ -393,6 +393,21 @@ __device__ __forceinline__ bool warp_event(uint64_t rec, int rx, int ry, int rw,
 	return true;
 }
 
+// The fixed-point grid of one unit's value image: make_consts' exponent k (from norm alone) raised until the
+// unit's events cannot fill a pixel, n_ev * norm < 2^(11 + k) (a pixel wraps at 2^(12 + k)).  Units below that
+// keep make_consts' grid, and its bits.
+__device__ __forceinline__ void unit_fix_grid(const EvalConsts& c, uint32_t nEv, double& bias, double& scale)
+{
+	bias = c.fix_bias;  // 1.5 * 2^k
+	scale = c.fix_scale;
+	const double top = static_cast<double>(nEv) * c.norm * (1.5 / 2048.0);  // n_ev * norm >= 2^(11 + k) <=> top >= bias
+	while (top >= bias)
+	{
+		bias *= 2.0;
+		scale *= 2.0;
+	}
+}
+
 // w[k] = pre * exp(hs (k-3-f)^2), k = 0..6, from three exps.
 __device__ __forceinline__ void axis_taps(double f, double pre, const EvalConsts& c, double (&w)[7])
 {

@@ -71,14 +71,16 @@ typedef struct ebo_event
 	int64_t t_us;
 } ebo_event;
 
-/* contrastFunctor's hard-coded members, contrast_functor.h:282-291. */
+/* contrastFunctor's hard-coded members, contrast_functor.h:282-291.  ebo_create returns EBO_ERR_ARG unless
+ * max_possible_residual, sigma_compensate and sigma_st are finite and > 0 (and, with EBO_GRAD_CENTRAL, fd_step;
+ * scale must be finite). */
 typedef struct ebo_functor_consts
 {
 	double max_possible_residual; /* 1e3 */
-	double sigma_compensate;      /* 1   */
+	double sigma_compensate;      /* 1; ebo_create: EBO_ERR_UNSUPPORTED outside [0.25, 1e3], the range tested */
 	int32_t kernel_compensate;    /* 3 (only 3 is built)  */
 	int32_t kernel_st;            /* 3 (only 3 is built)  */
-	double sigma_st;              /* 1.5 */
+	double sigma_st;              /* 1.5; ebo_create: EBO_ERR_UNSUPPORTED outside [1, 10], the range tested */
 	int32_t kernel_nms;           /* 2 (only 2 is built)  */
 	int32_t reserved;
 } ebo_functor_consts;
