@@ -309,6 +309,23 @@ def read_events_txt(path, cap=1 << 22):
     return out[: n.value].copy()
 
 
+def cut_windows(ev, time_us=300000, count=15000, max_store=15000, last_compensation_us=0):
+    """ebo_cut_windows: the reference's window rule (tools::Evaluator::eventCallback after
+    FeatureDetector::addEvent) on a time-ordered stream -> (begin, end, last_compensation_us, pending_begin);
+    window w is ev[begin[w]:end[w]]."""
+    ev = np.ascontiguousarray(ev, dtype=EVENT_DTYPE)
+    cap = len(ev)
+    begin = np.zeros(max(cap, 1), dtype=np.uint64)
+    end = np.zeros(max(cap, 1), dtype=np.uint64)
+    nw, last, pending = C.c_size_t(), C.c_int64(), C.c_size_t()
+    rc = lib().ebo_cut_windows(_vp(ev), C.c_size_t(len(ev)), C.c_int64(int(last_compensation_us)),
+                               C.c_uint32(int(time_us)), C.c_uint32(int(count)), C.c_uint64(int(max_store)),
+                               _vp(begin), _vp(end), C.c_size_t(cap), C.byref(nw), C.byref(last), C.byref(pending))
+    if rc:
+        raise EboError(rc, "cannot cut windows (max_store must be > 0)")
+    return begin[: nw.value].copy(), end[: nw.value].copy(), last.value, pending.value
+
+
 def read_events_txt_threads(path, cap, threads=0, offset=None, out=None):
     """ebo_read_events_txt_threads: at most cap events with `threads` host threads (0: EBO_HOST_THREADS or the
     machine's) -> (events, next offset or None, threads that parsed).  `out`: a caller-owned array to fill (timing)."""
@@ -657,6 +674,30 @@ class Context:
         self.n_windows = 1
         self._custom = None
         return flows, img, s
+
+    def compensate_windows(self, ev, offsets, opts=None, images=True):
+        """ebo_compensate_windows: window w = ev[offsets[w]:offsets[w+1]], in chunks of what the context holds.
+        -> (flows [Wn][P][2], warped [Wn][H][W], integrated [Wn][H][W] (both None without images), summaries,
+        status int32 [Wn]).  A refused window has its EBO_ERR_* in status and zeros in its outputs; only an error
+        of the call itself (bad arguments, recording a graph) raises."""
+        ev = np.ascontiguousarray(ev, dtype=EVENT_DTYPE)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        opts = opts if opts is not None else default_solver()
+        flows = np.zeros((n, self.P, 2))
+        shape = (n, self.params.image_h, self.params.image_w)
+        warped = np.zeros(shape) if images else None
+        integrated = np.zeros(shape) if images else None
+        summ = (Summary * max(n, 1))()
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        rc = lib().ebo_compensate_windows(
+            self._h, _vp(ev), _vp(offsets), int(n), C.byref(opts), _dp(flows),
+            _dp(warped) if images else None, _dp(integrated) if images else None, summ, _vp(status))
+        if rc and not status[:n].any():
+            self._check(rc)
+        self.n_windows = 0  # the context holds the last chunk, not these windows
+        self._custom = None
+        return flows, warped, integrated, list(summ)[:n], status[:n]
 
     def init_motion_field(self, timestamp, trajectories, use_average=True):
         """FeatureDetector::initMotionField. trajectories: list of [(x, y, t_us), ...] per patch.

@@ -136,6 +136,10 @@ class FeatureDetector
 	{
 		pending_.clear();  // events nobody asked the result of
 		tracked_.reset();
+		if (batchCtx_)
+		{
+			ebo_destroy(batchCtx_);
+		}
 		if (ctx_)
 		{
 			ebo_destroy(ctx_);
@@ -466,18 +470,7 @@ class FeatureDetector
 		{
 			return;
 		}
-		// :418-431 the reference stores the flows at the patch corners of its motion field
-		for (int y = 0; y < numPatchesY_; ++y)
-		{
-			for (int x = 0; x < numPatchesX_; ++x)
-			{
-				const size_t px = static_cast<size_t>(y) * params_.patchCompensateSize.height *
-									  params_.imageSize.width +
-								  static_cast<size_t>(x) * params_.patchCompensateSize.width;
-				motionField_[2 * px] = static_cast<float>(patchFlows_[2 * (y * numPatchesX_ + x)]);
-				motionField_[2 * px + 1] = static_cast<float>(patchFlows_[2 * (y * numPatchesX_ + x) + 1]);
-			}
-		}
+		storeFlowsInMotionField();
 	}
 
 	// feature_detector.cpp:466-482
@@ -586,6 +579,101 @@ class FeatureDetector
 	Mat64 const& getCompensatedEventImage() { return compensatedEventImage_; }
 	Mat64 const& getIntegratedEventImage() { return integratedEventImage_; }
 	common::timestamp_t const& getLastCompensation() { return lastCompensation; }
+	// tools::EventPump's batched mode queues a window and advances lastCompensation at once, as the compensation
+	// would have, so that the window rule and a caller's getLastCompensation() see what they see unbatched
+	void setLastCompensation(const common::timestamp_t& t) { lastCompensation = t; }
+
+	// compensateEventsContrast + integrateEvents for a batch of whole windows (the queue of tools::EventPump with
+	// EvaluatorParams::windowBatch > 1): window w = events[offsets[w] .. offsets[w+1]).  ONE ebo_compensate_windows
+	// call on a second context of this detector (created on first use: max_windows = min(batchWindows,
+	// kMaxBatchWindows), max_events = that x maxNumEventsToStore; the chunk size of the call), then, per window in
+	// order, the window's results are installed as compensateEventsContrast + integrateEvents would have left them
+	// (patch flows, motion field corners, both images, summary, lastCompensation = its last timestamp, status) and
+	// each(w) is called.  A window the device path refuses is reported through the error policy exactly as the
+	// unbatched calls report it: ERRORS_THROW throws at that window (the windows before it have had their each();
+	// the rest of the batch is dropped), ERRORS_STATUS leaves the previous window's results in place, sets status()
+	// and still calls each(w).
+	static constexpr size_t kMaxBatchWindows = 256;
+	void compensateWindows(const std::vector<ebo_event>& events, const std::vector<size_t>& offsets,
+						   size_t batchWindows, const std::function<void(size_t)>& each)
+	{
+		const size_t nw = offsets.empty() ? 0 : offsets.size() - 1;
+		if (nw == 0)
+		{
+			return;
+		}
+		const size_t P = patchFlows_.size() / 2;
+		const size_t npix = static_cast<size_t>(params_.imageSize.height) * params_.imageSize.width;
+		batchFlows_.resize(nw * P * 2);
+		batchWarped_.resize(nw * npix);
+		batchIntegrated_.resize(nw * npix);
+		batchSummary_.assign(nw, ebo_summary{});
+		batchStatus_.assign(nw, EBO_OK);
+		int rc = ctx_ ? EBO_OK : EBO_ERR_NO_DEVICE;
+		std::string callError = ctx_ ? "" : "no device context (construction failed)";
+		if (rc == EBO_OK && !batchCtx_)
+		{
+			ebo_params p = contextParams();
+			const size_t cap = std::max<size_t>(1, std::min(batchWindows, kMaxBatchWindows));
+			p.max_windows = static_cast<int32_t>(cap);
+			p.max_events *= cap;
+			rc = ebo_create(&p, &batchCtx_);
+			if (rc != EBO_OK)
+			{
+				batchCtx_ = nullptr;
+				callError = ebo_last_error(nullptr);
+			}
+		}
+		if (rc == EBO_OK)
+		{
+			ebo_solver_opts o;
+			ebo_default_solver(&o);
+			o.mode = params_.solveMode;
+			rc = ebo_compensate_windows(batchCtx_, events.data(), offsets.data(), static_cast<int>(nw), &o,
+										batchFlows_.data(), batchWarped_.data(), batchIntegrated_.data(),
+										batchSummary_.data(), batchStatus_.data());
+			const std::string msg = ebo_last_error(batchCtx_);
+			const bool perWindow = std::any_of(batchStatus_.begin(), batchStatus_.end(), [](int32_t s) { return s != EBO_OK; });
+			if (rc != EBO_OK && !perWindow)
+			{
+				callError = msg;  // the call itself failed: every window reports it
+			}
+			else
+			{
+				firstBatchError_ = msg;
+			}
+		}
+		if (rc != EBO_OK && std::all_of(batchStatus_.begin(), batchStatus_.end(), [](int32_t s) { return s == EBO_OK; }))
+		{
+			batchStatus_.assign(nw, rc);
+			firstBatchError_ = callError;
+		}
+		bool first = true;
+		for (size_t w = 0; w < nw; ++w)
+		{
+			lastCompensation = common::timestamp_t(events[offsets[w + 1] - 1].t_us);
+			if (batchStatus_[w] != EBO_OK)
+			{
+				fail(batchStatus_[w], first ? firstBatchError_.c_str() : "a window of the batch was refused");
+				first = false;
+			}
+			else
+			{
+				std::copy(batchFlows_.begin() + w * P * 2, batchFlows_.begin() + (w + 1) * P * 2, patchFlows_.begin());
+				storeFlowsInMotionField();
+				std::copy(batchWarped_.begin() + w * npix, batchWarped_.begin() + (w + 1) * npix, compensatedEventImage_.ptr());
+				std::copy(batchIntegrated_.begin() + w * npix, batchIntegrated_.begin() + (w + 1) * npix,
+						  integratedEventImage_.ptr());
+				lastSummary_ = batchSummary_[w];
+				status_ = EBO_OK;
+				lastError_.clear();
+			}
+			if (each)
+			{
+				each(w);
+			}
+		}
+	}
 
 	// The solved per-patch flows mf[P][2] (leaked by the reference, :318) and the
 	// solver's summary (the reference logs summary.BriefReport(), :416).
@@ -624,6 +712,11 @@ class FeatureDetector
 				ebo_destroy(ctx_);
 				ctx_ = nullptr;
 			}
+			if (batchCtx_)
+			{
+				ebo_destroy(batchCtx_);  // made again from the new parameters by the next compensateWindows
+				batchCtx_ = nullptr;
+			}
 			createContext();
 			tracked_->rebind(ctx_, params_.imageSize);
 		}
@@ -638,7 +731,23 @@ class FeatureDetector
 	const std::string& lastError() const { return lastError_; }
 
    private:
-	void createContext()
+	// :418-431 the reference stores the flows at the patch corners of its motion field
+	void storeFlowsInMotionField()
+	{
+		for (int y = 0; y < numPatchesY_; ++y)
+		{
+			for (int x = 0; x < numPatchesX_; ++x)
+			{
+				const size_t px = static_cast<size_t>(y) * params_.patchCompensateSize.height *
+									  params_.imageSize.width +
+								  static_cast<size_t>(x) * params_.patchCompensateSize.width;
+				motionField_[2 * px] = static_cast<float>(patchFlows_[2 * (y * numPatchesX_ + x)]);
+				motionField_[2 * px + 1] = static_cast<float>(patchFlows_[2 * (y * numPatchesX_ + x) + 1]);
+			}
+		}
+	}
+
+	ebo_params contextParams() const
 	{
 		ebo_params p;
 		ebo_default_params(&p);
@@ -655,6 +764,11 @@ class FeatureDetector
 		p.grad = params_.grad;
 		p.max_events = params_.maxNumEventsToStore > 0 ? params_.maxNumEventsToStore : 1;
 		p.max_windows = 1;
+		return p;
+	}
+	void createContext()
+	{
+		ebo_params p = contextParams();
 		const int rc = ebo_create(&p, &ctx_);
 		if (rc != EBO_OK)
 		{
@@ -890,6 +1004,12 @@ class FeatureDetector
 	std::list<common::EventSample> lastEvents_;
 	common::timestamp_t lastCompensation;
 	ebo_summary lastSummary_ = {};
+	// compensateWindows: the second context and the batch's results (kept between batches: no reallocation)
+	ebo_ctx* batchCtx_ = nullptr;
+	std::vector<double> batchFlows_, batchWarped_, batchIntegrated_;
+	std::vector<ebo_summary> batchSummary_;
+	std::vector<int32_t> batchStatus_;
+	std::string firstBatchError_;
 };
 
 }  // namespace tracker

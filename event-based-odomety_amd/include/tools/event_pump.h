@@ -28,6 +28,12 @@ struct EvaluatorParams
 	// compensate whole image each k microseconds
 	uint32_t compensationFrequencyTime = 300000;
 	uint32_t compensationFrequencyEvents = 15000;
+	// Windows compensated together (EventPump, not in the reference).  1: every window is compensated when it fires,
+	// as in the reference.  > 1: a window that fires is queued; when windowBatch are queued (and at the end of
+	// replay() / on flush()) ONE batched device call compensates them all (FeatureDetector::compensateWindows), then
+	// the callback runs for every window in order with the detector holding that window's results.  Use it when
+	// nothing has to read a window's results before the next event arrives ("Recordings").
+	size_t windowBatch = 1;
 };
 
 class EventPump
@@ -51,6 +57,11 @@ class EventPump
 				static_cast<long long>(params_.compensationFrequencyTime) ||
 			tracker_.getEvents().size() >= params_.compensationFrequencyEvents)
 		{
+			if (params_.windowBatch > 1)
+			{
+				queueWindow(sample);
+				return;
+			}
 			const size_t n = tracker_.getEvents().size();
 			tracker_.compensateEventsContrast(tracker_.getEvents());
 			tracker_.integrateEvents(tracker_.getEvents());
@@ -63,14 +74,40 @@ class EventPump
 		}
 	}
 
-	// Replayer: deliver every event of a recording in order.
+	// Replayer: deliver every event of a recording in order (and, batched, compensate what is queued at the end).
 	void replay(const std::vector<common::EventSample>& events)
 	{
 		for (const auto& e : events)
 		{
 			eventCallback(e);
 		}
+		flush();
 	}
+
+	// windowBatch > 1: compensate the queued windows now and run their callbacks in order.  The queue is emptied
+	// first: under DetectorParams::ERRORS_THROW a refused window throws from here after the callbacks of the windows
+	// before it, and the windows after it in the batch are dropped.  Nothing to do with windowBatch = 1.
+	void flush()
+	{
+		if (queueOffsets_.size() < 2)
+		{
+			return;
+		}
+		std::vector<ebo_event> events;
+		std::vector<size_t> offsets;
+		events.swap(queueEvents_);
+		offsets.swap(queueOffsets_);
+		queueOffsets_.assign(1, 0);
+		queueEvents_.reserve(events.capacity());
+		tracker_.compensateWindows(events, offsets, params_.windowBatch, [&](size_t w) {
+			if (onWindow_)
+			{
+				onWindow_(tracker_, offsets[w + 1] - offsets[w]);
+			}
+			++windows_;
+		});
+	}
+	size_t queuedWindows() const { return queueOffsets_.size() - 1; }
 
 	size_t windows() const { return windows_; }
 
@@ -122,10 +159,30 @@ class EventPump
 	}
 
    private:
+	// the batched form of the compensation branch: the held events join the queue, the detector's list is
+	// cleared and lastCompensation moves to the window's last timestamp as compensateEventsContrast would move it
+	void queueWindow(const common::EventSample& sample)
+	{
+		for (const auto& e : tracker_.getEvents())
+		{
+			queueEvents_.push_back(ebo_event{e.value.point.x, e.value.point.y, static_cast<int32_t>(e.value.sign), 0,
+											 e.timestamp.count()});  // common::toEboEvents
+		}
+		queueOffsets_.push_back(queueEvents_.size());
+		tracker_.clearEvents();
+		tracker_.setLastCompensation(sample.timestamp);
+		if (queuedWindows() >= params_.windowBatch)
+		{
+			flush();
+		}
+	}
+
 	tracker::FeatureDetector& tracker_;
 	EvaluatorParams params_;
 	WindowCallback onWindow_;
 	size_t windows_ = 0;
+	std::vector<ebo_event> queueEvents_;
+	std::vector<size_t> queueOffsets_ = std::vector<size_t>(1, 0);
 };
 
 // tools::Replayer (tools/replayer/src/replayer.cpp:42-131) for the two streams that decide WHEN the

@@ -475,6 +475,36 @@ int ebo_compensate_events_contrast(ebo_ctx* ctx, const ebo_event* ev, size_t n,
 								   const ebo_solver_opts* o, double* flows_out,
 								   double* image_out, ebo_summary* summary);
 
+/* ---- recordings: many windows per call ------------------------------------------------------
+ * tools::Evaluator::eventCallback's window rule (evaluator.cpp:32-45) together with FeatureDetector::addEvent's
+ * truncation (feature_detector.cpp:621-628), applied to a time-ordered stream.  Window w is ev[begin[w] .. end[w]).
+ * Host only.  Event by event: the event joins the held ones, the oldest are dropped while more than max_store
+ * (maxNumEventsToStore) are held, THEN the window fires when ts - lastCompensation >= time_us
+ * (compensationFrequencyTime) or when count (compensationFrequencyEvents) are held; the triggering event is the
+ * window's last, and lastCompensation becomes its timestamp.  lastCompensation starts at last_compensation_us (0 in a
+ * fresh detector, so the first event of a recording usually fires a one-event window); with count > max_store only
+ * the time rule can fire.  *last_compensation_out: lastCompensation after the stream; *pending_begin: the first event
+ * no window took (the events held at the end, which a streaming caller carries into its next call).
+ * EBO_ERR_RANGE when cap is too small: *n_windows is then the number of windows needed, nothing else is valid.
+ * EBO_ERR_ARG for max_store == 0 or a null pointer. */
+int ebo_cut_windows(const ebo_event* ev, size_t n, int64_t last_compensation_us, uint32_t time_us, uint32_t count,
+					uint64_t max_store, size_t* begin, size_t* end, size_t cap, size_t* n_windows,
+					int64_t* last_compensation_out, size_t* pending_begin);
+
+/* R2 + R3 for many windows: window w = ev[offsets[w] .. offsets[w+1]) (host memory), each solved from flow 0 like
+ * ebo_compensate_events_contrast on that window alone.  The windows go through in chunks that fit the context's
+ * max_windows / max_events; per chunk: ebo_set_windows, ebo_solve with o (either mode), ebo_count_image(WARPED) at the
+ * chunk's flows and ebo_count_image(INTEGRATED) on the same loaded events -- each event is uploaded once.
+ * Outputs per window: flows_out [Wn][P][2], warped_out [Wn][image_h][image_w] (R2's final image),
+ * integrated_out [Wn][image_h][image_w] (R3), summary [Wn], status [Wn]; all but flows_out may be NULL.
+ * A window the one-window path refuses (empty; a coordinate or a time outside the packed range, found by the loader;
+ * more events than max_events) fails ALONE: status[w] = EBO_ERR_*, its outputs are left as they were, and the other
+ * windows of its chunk are loaded again without it.  Returns EBO_OK when every window succeeded, else the code of the
+ * first window that failed (ebo_last_error names it).  EBO_ERR_STATE while a graph is being recorded. */
+int ebo_compensate_windows(ebo_ctx* ctx, const ebo_event* ev, const size_t* offsets, int n_windows,
+						   const ebo_solver_opts* o, double* flows_out, double* warped_out, double* integrated_out,
+						   ebo_summary* summary, int32_t* status);
+
 /* R5/R6 batched over tracked feature patches.  Patch i owns events
  * ev[offsets[i]..offsets[i+1]) in deque order (front = newest), a cv::Rect2d
  * rects[i][4] = (x,y,w,h), and writes a [int(h)][int(w)] signed count image at
