@@ -385,6 +385,36 @@ def read_events_bin(path, cap=1 << 24):
     return out[: n.value].copy()
 
 
+def _png8(call):
+    w, h = C.c_int32(), C.c_int32()
+    rc = call(C.byref(w), C.byref(h), None, C.c_size_t(0))
+    if rc:
+        raise EboError(rc, lib().ebo_last_error(None).decode(errors="replace"))
+    out = np.zeros((h.value, w.value), dtype=np.uint8)
+    rc = call(C.byref(w), C.byref(h), _vp(out), C.c_size_t(out.size))
+    if rc:
+        raise EboError(rc, lib().ebo_last_error(None).decode(errors="replace"))
+    return out
+
+
+def decode_png8(data):
+    """ebo_decode_png8: the bytes of an 8-bit greyscale, non-interlaced PNG -> uint8 [h][w] (a DAVIS frame as
+    cv::imread(path, CV_8U) returns it).  EboError with EBO_ERR_UNSUPPORTED / EBO_ERR_ARG otherwise."""
+    data = bytes(data)
+    buf = C.create_string_buffer(data, len(data))
+    f = lib().ebo_decode_png8
+    f.restype = C.c_int
+    return _png8(lambda w, h, px, cap: f(buf, C.c_size_t(len(data)), w, h, px, cap))
+
+
+def read_png8(path):
+    """ebo_read_png8: decode_png8 of a file."""
+    f = lib().ebo_read_png8
+    f.restype = C.c_int
+    p = str(path).encode()
+    return _png8(lambda w, h, px, cap: f(p, w, h, px, cap))
+
+
 def write_tracks_txt(path, pts):
     """trajectory.txt as tools::Evaluator::saveFeaturesTrajectory writes it (evaluator.cpp:125-150)."""
     pts = np.ascontiguousarray(pts, dtype=TRACK_DTYPE)

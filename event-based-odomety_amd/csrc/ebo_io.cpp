@@ -1,5 +1,7 @@
-// ebo_io.cpp — DAVIS events.txt reader and the packed binary sidecar (include/ebo.h).
+// ebo_io.cpp — DAVIS events.txt reader, the packed binary sidecar (include/ebo.h) and the
+// frames' PNG decoder (csrc/png8.h).
 #include "ebo_ctx.h"
+#include "png8.h"
 #include "txt_events.h"
 
 using namespace ebo;
@@ -271,6 +273,50 @@ int ebo_read_tracks_txt(const char* path, ebo_track_point* out, size_t cap, size
 		return EBO_ERR_ARG;
 	}
 	*n = count;
+	return rc;
+}
+
+// ---- DAVIS frames: 8-bit greyscale PNG (csrc/png8.h) ----------------------------------------------------
+int ebo_decode_png8(const void* bytes, size_t n, int32_t* w, int32_t* h, uint8_t* pixels, size_t capacity)
+{
+	std::string err;
+	const int rc = ebo::png::decode(static_cast<const uint8_t*>(bytes), n, w, h, pixels, capacity, err);
+	ebo_host::g_create_error = rc == EBO_OK ? std::string() : "png: " + err;
+	return rc;
+}
+
+int ebo_read_png8(const char* path, int32_t* w, int32_t* h, uint8_t* pixels, size_t capacity)
+{
+	if (!path)
+	{
+		ebo_host::g_create_error = "png: null path";
+		return EBO_ERR_ARG;
+	}
+	FILE* fp = std::fopen(path, "rb");
+	if (!fp)
+	{
+		ebo_host::g_create_error = std::string("png: cannot open ") + path;
+		return EBO_ERR_ARG;
+	}
+	std::vector<uint8_t> bytes;
+	uint8_t buf[1 << 16];
+	size_t got = 0;
+	while ((got = std::fread(buf, 1, sizeof(buf), fp)) > 0)
+	{
+		bytes.insert(bytes.end(), buf, buf + got);
+	}
+	const bool readError = std::ferror(fp) != 0;
+	std::fclose(fp);
+	if (readError)
+	{
+		ebo_host::g_create_error = std::string("png: cannot read ") + path;
+		return EBO_ERR_ARG;
+	}
+	const int rc = ebo_decode_png8(bytes.data(), bytes.size(), w, h, pixels, capacity);
+	if (rc != EBO_OK)
+	{
+		ebo_host::g_create_error += std::string(" (") + path + ")";
+	}
 	return rc;
 }
 

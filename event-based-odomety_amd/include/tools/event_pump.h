@@ -25,9 +25,16 @@ namespace tools
 struct EvaluatorParams
 {
 	tracker::Size imageSize = {240, 180};
+	// where tools::Evaluator writes trajectory.txt and final_cost.txt (tools/recording_evaluator.h)
+	std::string outputDir = "/tmp";
+	bool drawImages = false;
 	// compensate whole image each k microseconds
 	uint32_t compensationFrequencyTime = 300000;
 	uint32_t compensationFrequencyEvents = 15000;
+	// tools::Evaluator::imageCallback: trackerExperiment = only the first two images reach the detector;
+	// visOdometryExperiment = the patches come from Evaluator::setPatches, not from the detector
+	bool trackerExperiment = false;
+	bool visOdometryExperiment = false;
 	// Windows compensated together (EventPump, not in the reference).  1: every window is compensated when it fires,
 	// as in the reference.  > 1: a window that fires is queued; when windowBatch are queued (and at the end of
 	// replay() / on flush()) ONE batched device call compensates them all (FeatureDetector::compensateWindows), then
@@ -53,6 +60,13 @@ class EventPump
 	void eventCallback(const common::EventSample& sample)
 	{
 		tracker_.addEvent(sample);
+		closeWindowIfDue(sample);
+	}
+
+	// the window rule alone, for a caller that has handed `sample` to addEvent itself (tools::Evaluator calls
+	// updatePatches in between, as the reference's eventCallback does)
+	void closeWindowIfDue(const common::EventSample& sample)
+	{
 		if ((sample.timestamp - tracker_.getLastCompensation()).count() >=
 				static_cast<long long>(params_.compensationFrequencyTime) ||
 			tracker_.getEvents().size() >= params_.compensationFrequencyEvents)

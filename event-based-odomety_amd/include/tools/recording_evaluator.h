@@ -1,0 +1,264 @@
+// tools/recording_evaluator.h — tools::Evaluator, the tracker side of the reference's evaluator
+// (tools/evaluator/src/evaluator.cpp:10-124,125-150,209-225): a DAVIS recording goes in through tools::Replayer,
+// trajectory.txt and final_cost.txt come out.
+//
+//   tools::EvaluatorParams p;  p.outputDir = out;  p.trackerExperiment = true;
+//   tools::Evaluator evaluator(p);
+//   tools::Replayer replayer(std::make_shared<tools::Davis240cRecording>(dir));
+//   replayer.addEventCallback([&](const common::EventSample& s) { evaluator.eventCallback(s); });
+//   replayer.addImageCallback([&](const common::ImageSample& s) { evaluator.imageCallback(s); });
+//   while (!replayer.finished()) replayer.next();      // or evaluator.replay(replayer): the same files
+//   // ~Evaluator: preExit, <outputDir>/trajectory.txt and <outputDir>/final_cost.txt
+//
+// The detector is ONE tracker::FeatureDetector built from imageSize / drawImages with the device front end installed
+// (useDeviceFrontEnd: ebo_good_features, ebo_image_gradients, ebo_lk_*).  eventCallback is addEvent -> updatePatches ->
+// the window rule of tools::EventPump (compensateEventsContrast + integrateEvents + clearEvents, or, with windowBatch
+// > 1, queued and compensated in batches; queued windows are flushed before an image is handled, so every call runs in
+// the unbatched order).  The visual odometry is not owned here (it stays the user's front end): where the reference
+// calls visualOdometry_->newKeyframeCandidate, the keyframe hook receives the patches and the image's timestamp, and
+// savePoses / setGroundTruthSamples belong to the VO's owner.  EvaluatorParams has the reference's fields except
+// cameraModelParams (a VO parameter), plus windowBatch.
+#pragma once
+
+#include <cstdio>
+#include <fstream>
+#include <functional>
+#include <iomanip>
+#include <memory>
+#include <optional>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "../feature_tracker/feature_detector.h"
+#include "evaluator.h"
+#include "event_pump.h"
+#include "replayer.h"
+
+namespace tools
+{
+class Evaluator
+{
+   public:
+	// where the reference builds a visual_odometry::Keyframe and calls newKeyframeCandidate (evaluator.cpp:79-103)
+	using KeyframeHook = std::function<void(const tracker::Patches&, const common::timestamp_t&)>;
+
+	explicit Evaluator(const EvaluatorParams& params, KeyframeHook onKeyframe = nullptr)
+		: params_(params), onKeyframe_(std::move(onKeyframe))
+	{
+		reset();
+	}
+
+	// evaluator.cpp:15-21 without savePoses: the archived patches and the final costs of the oldest optimizer in use.
+	// A failure here is reported on stderr (a destructor does not throw); call finish() to have it thrown.
+	~Evaluator()
+	{
+		if (finished_)
+		{
+			return;
+		}
+		try
+		{
+			finish();
+		}
+		catch (const std::exception& e)
+		{
+			std::fprintf(stderr, "tools::Evaluator: %s\n", e.what());
+		}
+	}
+	Evaluator(const Evaluator&) = delete;
+	Evaluator& operator=(const Evaluator&) = delete;
+
+	// what the destructor does, once: queued windows compensated, preExit, the two files written
+	void finish()
+	{
+		if (finished_)
+		{
+			return;
+		}
+		finished_ = true;
+		pump_->flush();
+		tracker_->preExit();
+		saveFeaturesTrajectory(tracker_->getArchivedPatches());
+		saveFinalCosts(tracker_->getOptimizedFinalCosts());
+	}
+
+	// evaluator.cpp:32-45
+	void eventCallback(const common::EventSample& sample)
+	{
+		++events_;
+		tracker_->addEvent(sample);
+		tracker_->updatePatches(sample);
+		pump_->closeWindowIfDue(sample);
+	}
+
+	void groundTruthCallback(const common::GroundTruthSample& /*sample*/) {}
+
+	// evaluator.cpp:51-104
+	void imageCallback(const common::ImageSample& sample)
+	{
+		pump_->flush();
+		imageNum_++;
+		if (params_.trackerExperiment && imageNum_ > 2)
+		{
+			return;
+		}
+		if (!params_.visOdometryExperiment)
+		{
+			tracker_->newImage(sample);
+			corners_ = tracker_->getFeatures();
+		}
+		else
+		{
+			const auto it = keyframes_.find(sample.timestamp.count());
+			if (it != keyframes_.end())
+			{
+				patches_ = it->second;
+			}
+		}
+		if (imageNum_ > 2 && onKeyframe_)
+		{
+			if (!params_.visOdometryExperiment)
+			{
+				onKeyframe_(tracker_->getPatches(), sample.timestamp);
+			}
+			else
+			{
+				const auto it = keyframes_.find(sample.timestamp.count());
+				if (it != keyframes_.end())
+				{
+					onKeyframe_(it->second, sample.timestamp);
+				}
+			}
+		}
+	}
+
+	// Not in the reference: the whole recording.  The replayer hands over the events up to each frame as one chunk
+	// (Replayer::nextChunk: no callback per event, each frame decoded once) and every event goes through eventCallback.
+	// The tracker itself already advances all patches in lock-step rounds over DetectorParams::eventBatch events at a
+	// time (updatePatches(event) queues; tracked_patches.h).  Those rounds are deliberately NOT widened to the whole
+	// frame interval here: a round appends the final costs of its patches in patch order, so a different grouping
+	// reorders the lines of final_cost.txt (each patch's own costs, rects and trajectory stay the same).  Kept at the
+	// per-event grouping, both files are byte-identical to those of `while (!replayer.finished()) replayer.next();`.
+	void replay(Replayer& replayer)
+	{
+		std::vector<common::EventSample> chunk;
+		std::optional<common::ImageSample> image;
+		while (!replayer.finished())
+		{
+			chunk.clear();
+			replayer.nextChunk(chunk, image);
+			for (const common::EventSample& e : chunk)
+			{
+				eventCallback(e);
+			}
+			if (image)
+			{
+				imageCallback(*image);
+			}
+		}
+	}
+
+	// evaluator.cpp:106-118 (the VO is the hook's owner's)
+	void reset()
+	{
+		corners_.clear();
+		patches_.clear();
+		keyframes_.clear();
+		tracker::DetectorParams dp;
+		dp.drawImages = params_.drawImages;
+		dp.imageSize = params_.imageSize;
+		pump_.reset();
+		tracker_ = std::make_unique<tracker::FeatureDetector>(dp);
+		tracker_->useDeviceFrontEnd();
+		pump_ = std::make_unique<EventPump>(*tracker_, params_);
+		imageNum_ = 0;
+		events_ = 0;
+		finished_ = false;
+	}
+
+	// evaluator.cpp:120-123
+	void setTrackerParams(const tracker::DetectorParams& params)
+	{
+		pump_->flush();
+		tracker_->setParams(params);
+	}
+	void setParams(const EvaluatorParams& params)
+	{
+		params_ = params;
+		pump_->flush();
+		pump_ = std::make_unique<EventPump>(*tracker_, params_);
+	}
+	void setKeyframeHook(KeyframeHook onKeyframe) { onKeyframe_ = std::move(onKeyframe); }
+
+	// evaluator.cpp:125-150: <outputDir>/trajectory.txt, "feature_id timestamp x y"
+	void saveFeaturesTrajectory(const tracker::Patches& patches) const
+	{
+		tools::saveFeaturesTrajectory(patches, params_.outputDir + "/trajectory.txt");
+	}
+	// evaluator.cpp:209-225: <outputDir>/final_cost.txt, "trackId loss timeStampMicrosecond" (loss fixed, 8 digits)
+	void saveFinalCosts(const std::vector<tracker::OptimizerFinalLoss>& vectorFinalCosts) const
+	{
+		const std::string file = params_.outputDir + "/final_cost.txt";
+		std::ofstream costFile(file);
+		if (!costFile)
+		{
+			throw std::runtime_error("tools::Evaluator: cannot write " + file);
+		}
+		for (const auto& v : vectorFinalCosts)
+		{
+			costFile << v.trackId << " " << std::fixed << std::setprecision(8) << v.lossValue << " "
+					 << v.timeStampMicrosecond << std::endl;
+		}
+	}
+
+	// evaluator.cpp:165-171: the patches of a VO run, keyed by their current timestamp
+	void setPatches(const tracker::Patches& patches)
+	{
+		for (const auto& patch : patches)
+		{
+			keyframes_[patch.getCurrentTimestamp().count()].push_back(patch);
+		}
+	}
+
+	// evaluator.cpp:23-30
+	tracker::Patches const& getPatches() const
+	{
+		if (params_.visOdometryExperiment)
+		{
+			return patches_;
+		}
+		return tracker_->getPatches();
+	}
+	tracker::Mat64 const& getCompensatedEventImage()
+	{
+		pump_->flush();
+		return tracker_->getCompensatedEventImage();
+	}
+	tracker::Mat64 const& getIntegratedEventImage()
+	{
+		pump_->flush();
+		return tracker_->getIntegratedEventImage();
+	}
+
+	// not in the reference
+	tracker::FeatureDetector& detector() { return *tracker_; }
+	size_t windows() const { return pump_->windows(); }
+	size_t images() const { return imageNum_; }
+	size_t events() const { return events_; }
+	const EvaluatorParams& params() const { return params_; }
+
+   private:
+	EvaluatorParams params_;
+	KeyframeHook onKeyframe_;
+	std::unique_ptr<tracker::FeatureDetector> tracker_;
+	std::unique_ptr<EventPump> pump_;
+	std::unordered_map<size_t, tracker::Patches> keyframes_;
+	tracker::Corners corners_;
+	tracker::Patches patches_;
+	size_t imageNum_ = 0;
+	size_t events_ = 0;
+	bool finished_ = false;
+};
+
+}  // namespace tools

@@ -10,6 +10,8 @@ drawn for that patch lie on one of its 1-3 straight edges translating at v_p
 patch.  Timestamps are uniform over the 50 ms window and sorted; polarity is a
 fair coin; coordinates are clamped into the sensor.
 """
+import os
+
 import numpy as np
 
 GOLDEN = np.uint64(0x9E3779B97F4A7C15)
@@ -127,3 +129,140 @@ def write_events_txt(path, ev):
     with open(path, "w") as fp:
         for e in ev:
             fp.write("%.9f %d %d %d\n" % (int(e["t_us"]) * 1e-6, e["x"], e["y"], 1 if e["sign"] > 0 else 0))
+
+
+# ---- a DAVIS recording directory: frames, events, ground truth, calibration --------------------------------------
+def png8_bytes(img, filters=0, level=6, strategy=None, idat_split=None):
+    """An 8-bit greyscale, non-interlaced PNG of `img` (uint8 [h][w]) written with Python's zlib.  `filters`: one row
+    filter type 0-4 for every row, or a sequence of one per row; `level` 0-9 and `strategy` (zlib.Z_FILTERED,
+    Z_HUFFMAN_ONLY, Z_RLE, Z_FIXED; None = Z_DEFAULT_STRATEGY) choose the deflate blocks; `idat_split` cuts the
+    stream into IDAT chunks of that many bytes (None: one chunk)."""
+    import struct
+    import zlib
+
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    h, w = img.shape
+    kinds = [int(filters)] * h if np.isscalar(filters) else [int(f) for f in filters]
+    raw = bytearray()
+    prev = np.zeros(w, dtype=np.int32)
+    for y in range(h):
+        cur = img[y].astype(np.int32)
+        left = np.concatenate(([0], cur[:-1]))
+        upleft = np.concatenate(([0], prev[:-1]))
+        f = kinds[y]
+        if f == 0:
+            pred = np.zeros(w, dtype=np.int32)
+        elif f == 1:
+            pred = left
+        elif f == 2:
+            pred = prev
+        elif f == 3:
+            pred = (left + prev) >> 1
+        elif f == 4:
+            p = left + prev - upleft
+            pa, pb, pc = np.abs(p - left), np.abs(p - prev), np.abs(p - upleft)
+            pred = np.where((pa <= pb) & (pa <= pc), left, np.where(pb <= pc, prev, upleft))
+        else:
+            raise ValueError("row filter %d" % f)
+        raw.append(f)
+        raw += ((cur - pred) & 255).astype(np.uint8).tobytes()
+        prev = cur
+    co = zlib.compressobj(level, zlib.DEFLATED, 15, 9, zlib.Z_DEFAULT_STRATEGY if strategy is None else strategy)
+    stream = co.compress(bytes(raw)) + co.flush()
+
+    def chunk(kind, body):
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
+
+    step = len(stream) if not idat_split else int(idat_split)
+    idats = b"".join(chunk(b"IDAT", stream[i:i + step]) for i in range(0, max(len(stream), 1), max(step, 1)))
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 0, 0, 0, 0)) + idats +
+            chunk(b"IEND", b""))
+
+
+def _smooth_texture(rng, h, w, sigma=2.0):
+    big = rng.uniform(0.0, 1.0, size=(h, w))
+    r = int(3 * sigma)
+    k = np.exp(-0.5 * (np.arange(-r, r + 1) / sigma) ** 2)
+    k /= k.sum()
+    big = np.apply_along_axis(lambda v: np.convolve(v, k, mode="same"), 1, big)
+    big = np.apply_along_axis(lambda v: np.convolve(v, k, mode="same"), 0, big)
+    big = (big - big.mean()) / (big.std() + 1e-12)
+    return np.clip(128.0 + 45.0 * big, 8.0, 247.0)
+
+
+def _bilinear(tex, x, y):
+    x0, y0 = np.floor(x).astype(np.int64), np.floor(y).astype(np.int64)
+    ax, ay = x - x0, y - y0
+    return ((1 - ay) * ((1 - ax) * tex[y0, x0] + ax * tex[y0, x0 + 1]) +
+            ay * ((1 - ax) * tex[y0 + 1, x0] + ax * tex[y0 + 1, x0 + 1]))
+
+
+def make_recording(path, seed=0, size=(240, 180), duration_s=0.8, fps=24.0, velocity=(40.0, -25.0), threshold=0.25,
+                   step_us=1000, focal=200.0):
+    """Writes a DAVIS240C recording directory at `path`: events.txt, images.txt + images/frame_<i>.png,
+    groundtruth.txt and calib.txt.
+
+    The scene is a seeded smooth random texture translating across the sensor at `velocity` (px/s): the frame at time
+    t is the texture sampled (bilinear) at x - vx t, y - vy t.  Events are ESIM-style: every `step_us` the log
+    intensity of each pixel is compared with its last reference level, and every crossing of `threshold` emits an
+    event (+1 up, -1 down) at a time spread evenly inside the step; the reference moves by the crossings.  Frames
+    (8-bit grey PNG, written with Python's zlib) every 1/fps s from t = 1/fps.  Ground truth: the camera translating
+    parallel to a plane at depth 1, t = (-vx, -vy, 0) * t / focal, identity rotation; calib.txt: focal, focal, the
+    sensor centre, no distortion.  Returns dict(events=n, frames=n, velocity=(vx, vy))."""
+    w, h = size
+    rng = np.random.default_rng(20240601 + seed)
+    vx, vy = velocity
+    margin = int(np.ceil(max(abs(vx), abs(vy)) * duration_s)) + 4
+    tex = _smooth_texture(rng, h + 2 * margin, w + 2 * margin)
+    gx, gy = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+
+    def render(t_us):
+        t = t_us * 1e-6
+        return _bilinear(tex, gx + margin - vx * t, gy + margin - vy * t)
+
+    os.makedirs(os.path.join(path, "images"), exist_ok=True)
+    # events
+    ref = np.log(render(0))
+    chunks = []
+    n_steps = int(duration_s * 1e6) // step_us
+    for k in range(1, n_steps + 1):
+        t1 = k * step_us
+        L = np.log(render(t1))
+        d = L - ref
+        n = np.floor(np.abs(d) / threshold).astype(np.int64)
+        ys, xs = np.nonzero(n)
+        if len(ys):
+            cnt = n[ys, xs]
+            sgn = np.sign(d[ys, xs]).astype(np.int64)
+            ref[ys, xs] += sgn * cnt * threshold
+            rep = np.repeat(np.arange(len(ys)), cnt)
+            j = np.arange(len(rep)) - np.repeat(np.cumsum(cnt) - cnt, cnt)  # 0..cnt-1 inside each pixel
+            t = (t1 - step_us) + ((j + 1) * step_us) // (cnt[rep] + 1)
+            chunks.append(np.stack([t, xs[rep], ys[rep], (sgn[rep] > 0).astype(np.int64)], axis=1))
+    ev = np.concatenate(chunks) if chunks else np.zeros((0, 4), dtype=np.int64)
+    ev = ev[np.argsort(ev[:, 0], kind="stable")]
+    with open(os.path.join(path, "events.txt"), "w") as f:
+        f.write("".join("%d.%06d000 %d %d %d\n" % (t // 1000000, t % 1000000, x, y, p) for t, x, y, p in ev))
+    # frames
+    lines = []
+    period_us = int(round(1e6 / fps))
+    t = period_us
+    i = 0
+    while t <= n_steps * step_us:
+        img = np.clip(np.rint(render(t)), 0, 255).astype(np.uint8)
+        name = "images/frame_%08d.png" % i
+        with open(os.path.join(path, name), "wb") as f:
+            f.write(png8_bytes(img, filters=4, level=6))
+        lines.append("%d.%06d000 %s\n" % (t // 1000000, t % 1000000, name))
+        t += period_us
+        i += 1
+    with open(os.path.join(path, "images.txt"), "w") as f:
+        f.write("".join(lines))
+    with open(os.path.join(path, "groundtruth.txt"), "w") as f:
+        for k in range(0, n_steps + 1, 10):
+            ts = k * step_us
+            f.write("%d.%06d000 %.9f %.9f 0.0 0.0 0.0 0.0 1.0\n" % (ts // 1000000, ts % 1000000,
+                                                                   -vx * ts * 1e-6 / focal, -vy * ts * 1e-6 / focal))
+    with open(os.path.join(path, "calib.txt"), "w") as f:
+        f.write("%g %g %g %g 0 0 0 0 0\n" % (focal, focal, w / 2.0, h / 2.0))
+    return dict(events=len(ev), frames=i, velocity=(vx, vy))

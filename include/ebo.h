@@ -312,6 +312,18 @@ int ebo_interpolate_motion_field(ebo_ctx* ctx, int use_l1, const ebo_solver_opts
 int ebo_write_events_bin(const char* path, const ebo_event* ev, size_t n);
 int ebo_read_events_bin(const char* path, ebo_event* out, size_t cap, size_t* n);
 
+/* DAVIS frames without OpenCV (cv::imread(path, CV_8U) in Davis240cReader::getImageSample,
+ * davis240c_reader.cpp:93-107): a PNG of 8-bit greyscale, not interlaced -> *w, *h and the [h][w] pixels
+ * (row-major, one byte each).  Host only, HIP-free (csrc/png8.h): own inflate (stored, fixed and dynamic
+ * blocks), Adler-32 of the zlib stream and CRC-32 of the critical chunks checked, ancillary chunks skipped,
+ * the five row filters.  pixels == NULL: only the size (IHDR read and checked).  Errors, with the message
+ * in ebo_last_error(NULL): EBO_ERR_UNSUPPORTED for any other bit depth or colour type, Adam7 interlacing
+ * or a preset dictionary; EBO_ERR_ARG for malformed input (truncation, a bad checksum, a stream short of
+ * h * (w + 1) bytes, a side outside 1..16384, ...) or a file that cannot be read; EBO_ERR_RANGE when
+ * capacity < w * h (*w, *h set).  Never reads outside [bytes, bytes + n). */
+int ebo_decode_png8(const void* bytes, size_t n, int32_t* w, int32_t* h, uint8_t* pixels, size_t capacity);
+int ebo_read_png8(const char* path, int32_t* w, int32_t* h, uint8_t* pixels, size_t capacity);
+
 /* ---- per-feature tracker objective --------------------------------------
  * tracker::Optimizer::setGrad (optimizer.cpp:15-31): the image-gradient grid the tracker samples
  * with ceres::BiCubicInterpolator.  grad_x, grad_y: host [image_h][image_w] (CV_64F). */
