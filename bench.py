@@ -36,6 +36,12 @@ over gloo) and says so in the JSON line — never a scaling measurement.
 
 Prints ONE JSON line on rank 0; `ms_per_step` in it is the wall time of one of the K timed steps.
 `--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
+
+A plain run does only what the headline needs: set-up, preheat, W warm-up steps, the K timed steps, the dump, the line.
+`--full` adds everything else the benchmark measures or checks: the CPU baselines (`cpu_baseline`, and for N = 1 the
+all-cores one), the dominant kernel's roofline (its own timed launches and the LDS rates of this GPU), the untimed checks
+of the N > 1 steps and, at N = 1 without `--no-extras`, the single-GPU extras (other sizes, losses, solves, set-up
+paths, count images, the c4 step on one GPU).
 """
 import argparse
 import importlib
@@ -539,8 +545,11 @@ def main():
     ap.add_argument("--strong", action="store_true", help="c4: keep the batch at --c4-windows windows in total")
     ap.add_argument("--no-c4-image", action="store_true", help="c4: stop the step at solve + all-gather (no final count image)")
     ap.add_argument("--replicas", action="store_true", help="same as --workload replicas (BASELINE configs[4])")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: CPU baselines, the roofline of the dominant kernel, "
+                         "the N > 1 steps' untimed checks and the N = 1 extras (see the module docstring)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: time budget of the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: leave out the N = 1 extras")
     ap.add_argument("--comm", choices=("auto", "ebo", "torch"), default="torch",
                     help="N > 1 transport: torch = torch.distributed (backend nccl = RCCL; the default since round 5: the "
                          "library's grouped ncclSend / ncclRecv have never run between two ranks -- no box with two GPUs was "
@@ -582,12 +591,12 @@ def main():
         raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.windows is None:
         args.windows = 128 if args.config >= 3 else 256  # (C3: 64 / 128 / 256 windows per launch = 26.1 / 27.2 / 27.3 Gev/s)
-    extras_on = rank == 0 and world == 1 and not args.no_extras and workload == "eval"
+    extras_on = args.full and rank == 0 and world == 1 and not args.no_extras and workload == "eval"
 
     # N > 1: the CPU baseline of rank 0 runs BEFORE anything touches the GPU or the process group (the
     # other ranks wait in the rendezvous), so that no rank sits in a collective while one computes
     base_early = None
-    if world > 1 and rank == 0:
+    if args.full and world > 1 and rank == 0:
         try:
             synth_early = importlib.import_module("event-based-odomety_amd.synth")
             base_early = cpu_baseline(synth_early, 3 if workload == "c4" else args.config, args.cpu_seconds)
@@ -675,11 +684,14 @@ def main():
     def setup_eval(cfg_idx, Wn, seq):
         """`Wn` windows of BASELINE config cfg_idx (sequence `seq`: distinct events per rank)."""
         cfg = synth.CONFIGS[cfg_idx]
-        evs, gts = [], []
-        for w in range(Wn):
-            e, g = synth.make_window(cfg_idx, window=seq * Wn + w)
-            evs.append(e)
-            gts.append(g)
+        # the windows are independent and numpy's array operations release the GIL: a few threads make the same
+        # arrays in the same order several times faster than one (128 C3 windows: ~10 s on one host core)
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0)), Wn))) as pool:
+            made = list(pool.map(lambda w: synth.make_window(cfg_idx, window=seq * Wn + w), range(Wn)))
+        evs = [e for e, _ in made]
+        gts = [g for _, g in made]
+        del made
         offsets = np.zeros(Wn + 1, dtype=np.uint64)
         offsets[1:] = np.cumsum([len(e) for e in evs])
         ev = np.concatenate(evs)
@@ -957,9 +969,10 @@ def main():
                 outs["tracks_gathered"] = np.stack([tr[f].astype(np.float64) for f in ("id", "t_us", "x", "y")], 1)
         dumped = dump_outputs(args.dump_outputs, outs, rank, world, torch)
     total_units = comm.reduce(units_per_step, "SUM")
-    comm_total_events = comm.reduce(float(S["n_events"]), "SUM") if workload == "c4" else None
+    # everything below up to the line is --full only (the same flag on every rank: the collectives stay matched)
+    comm_total_events = comm.reduce(float(S["n_events"]), "SUM") if args.full and workload == "c4" else None
     band_counted, band_full = None, None
-    if workload == "c4" and S.get("band") is not None:
+    if args.full and workload == "c4" and S.get("band") is not None:
         # untimed checks of the band image: every rank's own rows sum to the events counted; on the library's
         # communicator the whole image is also assembled once on rank 0 (ebo_band_gather_device: owned rows only)
         band_counted = comm.reduce(float(S["B"]["img_own"].sum().item()), "SUM")
@@ -975,19 +988,20 @@ def main():
                              "sum_equals_own_rows_sum": bool(full.sum() == band_counted)}
 
     # ---- dominant kernel: average launch duration by HIP events on ITS stream -----------------
-    kern_ms = timed(kernel_fn, max(3, args.steps))
-    lds_rates = None
-    if rank == 0 and workload != "c4":
-        try:
-            lds_rates = ctx.lds_rates()  # the LDS rates the kernel is priced against, measured in this run
-        except Exception:
-            lds_rates = None
-    achieved = BYTES_PER_EVENT_EVAL * units_per_step / (kern_ms * 1e-3) / 1e9
+    kern_ms, lds_rates, achieved = None, None, None
+    if args.full:
+        kern_ms = timed(kernel_fn, max(3, args.steps))
+        if rank == 0 and workload != "c4":
+            try:
+                lds_rates = ctx.lds_rates()  # the LDS rates the kernel is priced against, measured in this run
+            except Exception:
+                lds_rates = None
+        achieved = BYTES_PER_EVENT_EVAL * units_per_step / (kern_ms * 1e-3) / 1e9
 
-    if workload == "replicas" and rank == 0:
+    if args.full and workload == "replicas" and rank == 0:
         T = tracks_state
         extras["track_gather"] = {"records_per_step_all_ranks": T["gathered"], "per_rank": T["counts"]}
-    if workload == "c4" and rank == 0:
+    if args.full and workload == "c4" and rank == 0:
         # the gathered buffer holds every window's flows: rank q's block = its rows of every window
         got = S["d_all"].cpu().numpy()
         mine = S["d_sol"].cpu().numpy()
@@ -1302,17 +1316,6 @@ def main():
         co.close()
 
     if rank == 0:
-        base = cpu_baseline(synth, args.config if workload != "c4" else 3, args.cpu_seconds) if world == 1 else base_early
-        # HBM traffic of the dominant kernel per launch, from the committed PMC profile of
-        # this same workload (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes)
-        traffic, traffic_src = None, None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tpath):
-            for t in json.load(open(tpath)).get("kernels", []):
-                same = (t.get("c4_windows_per_gpu") == args.c4_windows) if workload == "c4" else (
-                    t.get("windows") == config.get("windows_per_gpu_per_step"))
-                if t.get("kernel") == roof_kernel and t.get("workload") == cfg["name"] and same:
-                    traffic, traffic_src = t.get("hbm_bytes_per_launch"), t.get("source")
         value = total_units * args.steps / HEADLINE_DT / 1e6
         line = {
             "metric": "Mevents/s warped+scored (value+Jacobian of the variance-contrast objective)"
@@ -1320,19 +1323,31 @@ def main():
             "value": value, "unit": "Mevents/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "preheat_steps_untimed": args.preheat, "ms_per_step": HEADLINE_DT / args.steps * 1e3, "higher_is_better": True,
             "scaling": "strong" if (workload == "c4" and args.strong) else "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic", "config": config,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": roof_kernel, "kernel_ms": kern_ms,
-                         "note": "algorithmic 8 B/event-evaluation; the kernel is bound by LDS "
-                                 "atomics + f64 VALU, not HBM (DESIGN.md section 4)",
-                         # what does bind it: 49 64-bit LDS atomics + 49 64-bit LDS reads per event-evaluation
-                         # against the chip-wide rates of tools/microbench/lds_atomics.hip on this GPU
-                         # (ds_add_u64 and ds_read_b64 at random addresses)
-                         "lds": lds_roofline(units_per_step, kern_ms, lds_rates) if workload != "c4" else None},
-            "cpu_baseline": base,
-            "extras": extras,
+            "dtype": "f64", "data": "synthetic", "config": config, "full": args.full,
         }
+        if args.full:
+            base = cpu_baseline(synth, args.config if workload != "c4" else 3, args.cpu_seconds) if world == 1 else base_early
+            # HBM traffic of the dominant kernel per launch, from the committed PMC profile of
+            # this same workload (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes)
+            traffic, traffic_src = None, None
+            tpath = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tpath):
+                for t in json.load(open(tpath)).get("kernels", []):
+                    same = (t.get("c4_windows_per_gpu") == args.c4_windows) if workload == "c4" else (
+                        t.get("windows") == config.get("windows_per_gpu_per_step"))
+                    if t.get("kernel") == roof_kernel and t.get("workload") == cfg["name"] and same:
+                        traffic, traffic_src = t.get("hbm_bytes_per_launch"), t.get("source")
+            line["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                                "kernel": roof_kernel, "kernel_ms": kern_ms,
+                                "note": "algorithmic 8 B/event-evaluation; the kernel is bound by LDS "
+                                        "atomics + f64 VALU, not HBM (DESIGN.md section 4)",
+                                # what does bind it: 49 64-bit LDS atomics + 49 64-bit LDS reads per event-evaluation
+                                # against the chip-wide rates of tools/microbench/lds_atomics.hip on this GPU
+                                # (ds_add_u64 and ds_read_b64 at random addresses)
+                                "lds": lds_roofline(units_per_step, kern_ms, lds_rates) if workload != "c4" else None}
+            line["cpu_baseline"] = base
+            line["extras"] = extras
         if dumped is not None:
             line["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": dumped}
         if rehearse or (comm.active and world == 1):

@@ -8,7 +8,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 PY=python3
 S="$PY $R/event-based-odomety_amd/tools/pmc_summary.py"
-C4="$PY $R/bench.py --workload c4 --steps 5 --warmup 1 --cpu-seconds 1"
+C4="$PY $R/bench.py --full --workload c4 --steps 5 --warmup 1 --cpu-seconds 1"
 rocprofv3 --kernel-trace --stats -d $O/ks_c4 --output-format csv -- $C4 > $O/bench_c4_1gpu.json 2> $O/bench_c4.err
 cp $O/ks_c4/*/*kernel_stats.csv $O/${TAG}_bench_c4_1gpu_kernel_stats.csv 2>/dev/null
 rocprofv3 --pmc FETCH_SIZE -d $O/c4f --output-format csv -- $C4 > /dev/null 2>&1

@@ -86,7 +86,7 @@ def test_bench_runs_at_two_ranks_without_a_launcher(extra):
     ranks before touching the GPU and prints ONE JSON line naming the N > 1 workload."""
     env = dict(os.environ, EBO_BENCH_REHEARSE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--c4-windows", "1"] + extra
+           "--c4-windows", "1", "--full"] + extra
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -109,7 +109,7 @@ def test_bench_on_the_librarys_own_communicator(extra):
     ebo_band_exchange_device + ebo_band_gather_device, the tracks through ebo_allgather_tracks -- no process group."""
     env = dict(os.environ, EBO_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--comm", "ebo",
-           "--no-extras", "--cpu-seconds", "0.5"] + extra
+           "--full", "--no-extras", "--cpu-seconds", "0.5"] + extra
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
@@ -131,7 +131,7 @@ def test_band_and_dense_final_images_count_the_same_events_at_two_ranks():
     counted = {}
     for mode in ("band", "dense"):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--preheat", "0",
-               "--c4-windows", "1", "--c4-image", mode, "--cpu-seconds", "0.2"]
+               "--c4-windows", "1", "--c4-image", mode, "--full", "--cpu-seconds", "0.2"]
         res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
         assert res.returncode == 0, res.stderr[-3000:]
         line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
