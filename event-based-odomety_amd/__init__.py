@@ -111,6 +111,20 @@ class Summary(C.Structure):
     ]
 
 
+class Camera(C.Structure):
+    """ebo_camera: common::CameraModelParams<double>, in its field order."""
+    _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "k3", "p1", "p2")]
+
+
+def camera(v):
+    """A Camera from a Camera, a mapping of field names or nine numbers in the struct's order."""
+    if isinstance(v, Camera):
+        return v
+    if isinstance(v, dict):
+        return Camera(**{k: float(x) for k, x in v.items()})
+    return Camera(*[float(x) for x in v])
+
+
 class EboError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("ebo error %d: %s" % (code, msg))
@@ -1007,6 +1021,37 @@ class Context:
                                        int(max_level), int(max_count), C.c_double(epsilon),
                                        C.c_double(min_eig_threshold)))
         return nxt[:n], st[:n], err[:n]
+
+    # -- camera model (common::CameraModel) -----------------------------------
+    def camera_unproject(self, cam, uv):
+        """CameraModel::unproject for many points: float64 [n][2] pixels -> float64 [n][3] unit bearing vectors."""
+        cam = camera(cam)
+        uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(-1, 2)
+        out = np.zeros((len(uv), 3))
+        self._check(lib().ebo_camera_unproject(self._h, C.byref(cam), len(uv), _dp(uv), _dp(out)))
+        return out
+
+    def camera_unproject_device(self, cam, n, d_uv, d_bearing):
+        """The same on device arrays (pointers as int), asynchronous on the context's stream."""
+        cam = camera(cam)
+        self._check(lib().ebo_camera_unproject_device(self._h, C.byref(cam), int(n), C.c_void_p(int(d_uv)),
+                                                      C.c_void_p(int(d_bearing))))
+
+    def set_rectification(self, cam):
+        """Every later window load reads its events through the camera's rectification table."""
+        cam = camera(cam)
+        self._check(lib().ebo_set_rectification(self._h, C.byref(cam)))
+
+    def clear_rectification(self):
+        self._check(lib().ebo_clear_rectification(self._h))
+
+    def rectification_map(self):
+        """-> (map float64 [h][w][2] = (u, v), table int16 [h][w][2] = (round(u), round(v)))."""
+        h, w = self.params.image_h, self.params.image_w
+        m = np.zeros((h, w, 2))
+        lut = np.zeros((h, w, 2), dtype=np.int16)
+        self._check(lib().ebo_rectification_map(self._h, _dp(m), _vp(lut)))
+        return m, lut
 
     # -- timing --------------------------------------------------------------
     def timer_begin(self):

@@ -1593,6 +1593,9 @@ void ebo_destroy(ebo_ctx* c)
 	hipFree(c->d_field);
 	hipFree(c->d_tvf);
 	hipFree(c->d_fe_lut);
+	hipFree(c->d_rect_lut);
+	hipFree(c->d_rect_map);
+	hipFree(c->d_rect_bad);
 	hipFree(c->d_fe);
 	hipFree(c->d_fe_pyr[0]);
 	hipFree(c->d_fe_pyr[1]);

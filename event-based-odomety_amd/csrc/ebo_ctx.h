@@ -130,6 +130,13 @@ struct ebo_ctx
 	unsigned int* d_chunk_hist = nullptr;  // per-chunk bucket histograms / first ranks of the stable scatter
 	size_t chunk_hist_cap = 0;       // in entries
 	size_t bucket_cap = 0;
+	// ebo_set_rectification (ebo_camera.cpp): the sensor's rectification table and map; rect_set selects the
+	// Rectified<> bucketing kernels for the NEXT load
+	void* d_rect_lut = nullptr;      // int16 [image_h][image_w][2]
+	double* d_rect_map = nullptr;    // double [image_h][image_w][2]
+	int* d_rect_bad = nullptr;       // k_rectify_map's error bits
+	std::vector<int16_t> rect_lut;   // host copy for the host counting sort, fetched on its first use
+	bool rect_set = false;
 
 	std::vector<Unit> units;       // [Wn][P+1], stray unit last in each window
 	std::vector<int64_t> unit_tref;

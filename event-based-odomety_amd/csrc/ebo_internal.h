@@ -326,6 +326,7 @@ struct BucketLaunch
 	long long* d_win_tref;             // out [n_windows]
 	uint64_t* d_packed;                // out packed events
 	int* d_flag;                       // out error bits
+	const void* d_rectify = nullptr;   // short2 [image_h][image_w] rectification table (ebo_camera.inc), or null: raw coordinates
 	EvalConsts c;
 };
 int launch_bucket(const BucketLaunch& L, void* stream);
@@ -498,5 +499,14 @@ int launch_fe_pyramid(char* d_pyr, const FeLevel* lv, int n_levels, void* stream
 int launch_fe_lk(const char* d_prev, const char* d_next, const FeLevel* d_lv, int n_levels, int n, const float* d_prev_xy,
 				 float* d_next_xy, uint8_t* d_status, float* d_err, int win_w, int win_h, int max_count, double eps2,
 				 float min_eig, void* stream);
+
+// common::CameraModel (ebo_camera.inc, ebo_camera.cpp): the nine parameters in ebo_camera's order.
+struct CameraConsts
+{
+	double fx, fy, cx, cy, k1, k2, k3, p1, p2;
+};
+int launch_camera_unproject(const CameraConsts& k, int n, const double* d_uv, double* d_bearing, void* stream);
+// d_map: double [h][w][2], d_lut: int16 [h][w][2], *d_bad: error bits (zeroed here)
+int launch_rectify_map(const CameraConsts& k, int w, int h, double* d_map, void* d_lut, int* d_bad, void* stream);
 
 }  // namespace ebo

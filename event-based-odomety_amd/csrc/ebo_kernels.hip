@@ -1266,6 +1266,7 @@ __global__ void __launch_bounds__(64) k_route(const uint32_t* __restrict__ xy, u
 
 #include "ebo_edge.inc"
 #include "ebo_bucket.inc"
+#include "ebo_camera.inc"
 #include "ebo_field.inc"
 #include "ebo_fieldtv.inc"
 #include "ebo_optimizer.inc"
@@ -1767,6 +1768,18 @@ static int launch_bucket_t(const BucketLaunch& L, Rec raw, hipStream_t s)
 	return check_launch();
 }
 
+// the same record read through the rectification table (ebo_camera.inc)
+template <class Rec>
+static int launch_bucket_rectified(const BucketLaunch& L, Rec raw, hipStream_t s)
+{
+	Rectified<Rec> r;
+	r.inner = raw;
+	r.lut = static_cast<const short2*>(L.d_rectify);
+	r.w = L.c.image_w;
+	r.h = L.c.image_h;
+	return launch_bucket_t(L, r, s);
+}
+
 int launch_bucket(const BucketLaunch& L, void* stream)
 {
 	hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1775,11 +1788,34 @@ int launch_bucket(const BucketLaunch& L, void* stream)
 		Rec8 r;
 		r.p = static_cast<const uint2*>(L.d_raw);
 		r.tbase = L.d_tbase;
-		return launch_bucket_t(L, r, s);
+		return L.d_rectify ? launch_bucket_rectified(L, r, s) : launch_bucket_t(L, r, s);
 	}
 	Rec24 r;
 	r.p = static_cast<const RawEvent*>(L.d_raw);
-	return launch_bucket_t(L, r, s);
+	return L.d_rectify ? launch_bucket_rectified(L, r, s) : launch_bucket_t(L, r, s);
+}
+
+int launch_camera_unproject(const CameraConsts& k, int n, const double* d_uv, double* d_bearing, void* stream)
+{
+	if (n <= 0)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_camera_unproject, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), k, n, d_uv,
+					   d_bearing);
+	return check_launch();
+}
+
+int launch_rectify_map(const CameraConsts& k, int w, int h, double* d_map, void* d_lut, int* d_bad, void* stream)
+{
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	if (hipMemsetAsync(d_bad, 0, sizeof(int), s) != hipSuccess)
+	{
+		return -2;
+	}
+	hipLaunchKernelGGL(k_rectify_map, dim3((w * h + 255) / 256), dim3(256), 0, s, k, w, h, d_map, static_cast<short2*>(d_lut),
+					   d_bad);
+	return check_launch();
 }
 
 int launch_lds_rate(int atomic, int blocks, int iters, double* d_sink, void* stream)

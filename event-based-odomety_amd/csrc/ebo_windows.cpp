@@ -119,6 +119,7 @@ static int set_windows_on_device(ebo_ctx* c, const void* d_raw, const size_t* of
 	L.d_unit_maxdt = c->d_unit_maxdt;
 	L.d_packed = c->d_events;
 	L.c = make_consts(c);
+	L.d_rectify = c->rect_set ? c->d_rect_lut : nullptr;  // ebo_set_rectification: the Rectified<> kernels
 	// pinned mirror: offsets go up and (units | unit tref, window tref, flag) come back as three
 	// truly asynchronous copies and ONE synchronisation (copies from/to pageable memory are
 	// staged one by one by the runtime: 0.176 -> 0.131 ms for a 15 k-event window)
@@ -484,6 +485,42 @@ static int set_windows_host(ebo_ctx* c, const ebo_event* ev, const size_t* offse
 	{
 		return c->fail(EBO_ERR_ARG, "more events than max_events");
 	}
+	// ebo_set_rectification: this path sorts a rectified copy of the events (the rule of Rectified<>::load, ebo_camera.inc)
+	std::vector<ebo_event> rectified;
+	std::vector<size_t> rectOffsets;
+	if (c->rect_set && total > 0)
+	{
+		const size_t npx = static_cast<size_t>(c->prm.image_w) * c->prm.image_h;
+		if (c->rect_lut.size() != 2 * npx)
+		{
+			c->rect_lut.resize(2 * npx);
+			(void)hipSetDevice(c->prm.device);
+			int rcl = c->hip(hipMemcpy(c->rect_lut.data(), c->d_rect_lut, 2 * npx * sizeof(int16_t), hipMemcpyDeviceToHost),
+							 "D2H rectification table");
+			if (rcl)
+			{
+				c->rect_lut.clear();
+				return rcl;
+			}
+		}
+		rectified.assign(ev + offsets[0], ev + offsets[n_windows]);
+		for (ebo_event& e : rectified)
+		{
+			if (e.x >= 0 && e.x < c->prm.image_w && e.y >= 0 && e.y < c->prm.image_h)
+			{
+				const size_t i = static_cast<size_t>(e.y) * c->prm.image_w + e.x;
+				e.x = c->rect_lut[2 * i];
+				e.y = c->rect_lut[2 * i + 1];
+			}
+		}
+		rectOffsets.resize(n_windows + 1);
+		for (int w = 0; w <= n_windows; ++w)
+		{
+			rectOffsets[w] = offsets[w] - offsets[0];
+		}
+		ev = rectified.data();
+		offsets = rectOffsets.data();
+	}
 	const int P = c->P;
 	const int pw = c->prm.patch_w, ph = c->prm.patch_h;
 	std::vector<Unit> units(static_cast<size_t>(n_windows) * (P + 1));
@@ -666,6 +703,11 @@ int ebo_set_patches(ebo_ctx* c, const ebo_event* ev, const size_t* offsets, cons
 	if (!ev || !offsets || !rects || n_patches <= 0)
 	{
 		return c->fail(EBO_ERR_ARG, "null argument or no patch");
+	}
+	if (c->rect_set)
+	{
+		return c->fail(EBO_ERR_UNSUPPORTED,
+					   "ebo_set_patches does not rectify (host-sorted patches): ebo_clear_rectification first, or load windows");
 	}
 	if (static_cast<size_t>(n_patches) > static_cast<size_t>(c->cap_windows) * c->P)
 	{

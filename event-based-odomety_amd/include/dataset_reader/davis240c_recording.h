@@ -16,8 +16,8 @@
 //
 // Without Sophus and OpenCV on the include path the value types are stand-ins with the members the tracker side uses:
 // common::Pose3d (unit quaternion + translation: matrix(), rotationMatrix(), translation()), common::GroundTruthSample,
-// common::GroundTruth and common::CameraModelParams<Scalar> (the nine fields; CameraModel itself belongs to the visual
-// odometry).  With Sophus, common::Pose3d is Sophus::SE3d as in the reference (common/geometry.h:14).
+// and common::GroundTruth (common::CameraModelParams<Scalar> and CameraModel are in common/camera_model.h).  With
+// Sophus, common::Pose3d is Sophus::SE3d as in the reference (common/geometry.h:14).
 #pragma once
 
 #include <chrono>
@@ -28,6 +28,7 @@
 #include <string>
 #include <vector>
 
+#include "../common/camera_model.h"  // common::CameraModelParams<Scalar>
 #include "davis240c_reader.h"
 
 #if defined(__has_include)
@@ -125,21 +126,6 @@ inline Pose3d makePose3d(double qw, double qx, double qy, double qz, double tx, 
 
 using GroundTruthSample = Sample<Pose3d>;
 using GroundTruth = std::vector<GroundTruthSample>;
-
-// common/camera_model.h:13-24 (field order of the struct; calib.txt orders them fx fy cx cy k1 k2 p1 p2 k3)
-template <typename Scalar = double>
-struct CameraModelParams
-{
-	Scalar fx = 0;
-	Scalar fy = 0;
-	Scalar cx = 0;
-	Scalar cy = 0;
-	Scalar k1 = 0;
-	Scalar k2 = 0;
-	Scalar k3 = 0;
-	Scalar p1 = 0;
-	Scalar p2 = 0;
-};
 
 // an 8-bit single-channel image of the given pixels (a cv::Mat of CV_8U with OpenCV on the include path)
 inline Image8 makeImage8(int rows, int cols, const uint8_t* pixels)

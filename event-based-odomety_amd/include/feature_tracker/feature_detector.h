@@ -38,6 +38,7 @@
 #include <string>
 #include <vector>
 
+#include "../common/camera_model.h"
 #include "../common/data_types.h"
 #include "optimizer.h"
 #include "patch.h"
@@ -623,6 +624,12 @@ class FeatureDetector
 				batchCtx_ = nullptr;
 				callError = ebo_last_error(nullptr);
 			}
+			else if (rectify_ && (rc = ebo_set_rectification(batchCtx_, &rectifyCamera_)) != EBO_OK)
+			{
+				callError = ebo_last_error(batchCtx_);
+				ebo_destroy(batchCtx_);
+				batchCtx_ = nullptr;
+			}
 		}
 		if (rc == EBO_OK)
 		{
@@ -719,10 +726,37 @@ class FeatureDetector
 			}
 			createContext();
 			tracked_->rebind(ctx_, params_.imageSize);
+			if (rectify_ && ctx_)
+			{
+				rectify_ = false;
+				rectify_ = applyRectification();
+			}
 		}
 		reset();
 	}
 	ebo_ctx* handle() { return ctx_; }
+
+	// Rectify events at load (include/ebo.h: ebo_set_rectification): every window this detector compensates or
+	// integrates afterwards -- compensateEventsContrast, integrateEvents, compensateWindows -- is bucketed through the
+	// camera's rectification table, on the detector's own context and on the batch context.  The tracked patches and the
+	// image front end stay in raw coordinates (frames are not rectified).  A calibration the library refuses (fx or
+	// fy zero, a map outside the record range) is reported through the error policy and leaves no rectification set.
+	void setRectification(const common::CameraModelParams<double>& camera)
+	{
+		rectifyCamera_ = common::toEboCamera(camera);
+		rectify_ = false;  // (stays false when the error policy throws from here)
+		rectify_ = applyRectification();
+	}
+	void clearRectification()
+	{
+		rectify_ = false;
+		if (batchCtx_)
+		{
+			ebo_clear_rectification(batchCtx_);
+		}
+		check(ctx_ ? ebo_clear_rectification(ctx_) : EBO_OK);
+	}
+	bool rectifying() const { return rectify_; }
 
 	// DetectorParams::ERRORS_STATUS: the EBO_* code and message of the LAST call (EBO_OK / "" after
 	// a call that succeeded).
@@ -731,6 +765,17 @@ class FeatureDetector
 	const std::string& lastError() const { return lastError_; }
 
    private:
+	// the rectification of setRectification on the contexts that exist now (the batch context is made on first use)
+	bool applyRectification()
+	{
+		if (batchCtx_ && ebo_set_rectification(batchCtx_, &rectifyCamera_) != EBO_OK)
+		{
+			fail(EBO_ERR_RANGE, ebo_last_error(batchCtx_));
+			return false;
+		}
+		return check(ctx_ ? ebo_set_rectification(ctx_, &rectifyCamera_) : EBO_OK);
+	}
+
 	// :418-431 the reference stores the flows at the patch corners of its motion field
 	void storeFlowsInMotionField()
 	{
@@ -1010,6 +1055,8 @@ class FeatureDetector
 	std::vector<ebo_summary> batchSummary_;
 	std::vector<int32_t> batchStatus_;
 	std::string firstBatchError_;
+	bool rectify_ = false;        // setRectification: re-applied to every context made afterwards
+	ebo_camera rectifyCamera_{};
 };
 
 }  // namespace tracker

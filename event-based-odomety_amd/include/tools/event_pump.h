@@ -41,6 +41,12 @@ struct EvaluatorParams
 	// the callback runs for every window in order with the detector holding that window's results.  Use it when
 	// nothing has to read a window's results before the next event arrives ("Recordings").
 	size_t windowBatch = 1;
+	// the recording's calibration (tools/evaluator/include/evaluator/evaluator.h:18); all zero = none given
+	common::CameraModelParams<double> cameraModelParams;
+	// true: EventPump / Evaluator install cameraModelParams as the detector's rectification on construction
+	// (FeatureDetector::setRectification: events are undistorted as they are loaded).  With all-zero parameters
+	// that is an error through the detector's error policy, not a silent no-op.
+	bool rectifyEvents = false;
 };
 
 class EventPump
@@ -52,6 +58,10 @@ class EventPump
 	EventPump(tracker::FeatureDetector& tracker, const EvaluatorParams& params = EvaluatorParams())
 		: tracker_(tracker), params_(params)
 	{
+		if (params_.rectifyEvents)
+		{
+			tracker_.setRectification(params_.cameraModelParams);
+		}
 	}
 
 	void onWindow(WindowCallback cb) { onWindow_ = std::move(cb); }

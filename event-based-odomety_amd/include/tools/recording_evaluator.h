@@ -16,8 +16,8 @@
 // > 1, queued and compensated in batches; queued windows are flushed before an image is handled, so every call runs in
 // the unbatched order).  The visual odometry is not owned here (it stays the user's front end): where the reference
 // calls visualOdometry_->newKeyframeCandidate, the keyframe hook receives the patches and the image's timestamp, and
-// savePoses / setGroundTruthSamples belong to the VO's owner.  EvaluatorParams has the reference's fields except
-// cameraModelParams (a VO parameter), plus windowBatch.
+// savePoses / setGroundTruthSamples belong to the VO's owner.  EvaluatorParams has the reference's fields, plus
+// windowBatch and rectifyEvents (the events of every window are undistorted with cameraModelParams as they are loaded).
 #pragma once
 
 #include <cstdio>

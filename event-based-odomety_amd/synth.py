@@ -197,8 +197,25 @@ def _bilinear(tex, x, y):
             ay * ((1 - ax) * tex[y0 + 1, x0] + ax * tex[y0 + 1, x0 + 1]))
 
 
+def _undistorted_grid(px, py, focal, cx, cy, k1, k2, p1, p2, iterations=60):
+    """The undistorted pixel position of every distorted pixel (px, py): the fixed point of the radial-tangential
+    model, iterated until it no longer moves (60 steps are far beyond convergence for a lens that is invertible over
+    the sensor)."""
+    xd = (px - cx) / focal
+    yd = (py - cy) / focal
+    x, y = xd.copy(), yd.copy()
+    for _ in range(iterations):
+        r2 = x * x + y * y
+        radial = 1.0 + k1 * r2 + k2 * r2 * r2
+        dx = 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)
+        dy = 2.0 * p2 * x * y + p1 * (r2 + 2.0 * y * y)
+        x = (xd - dx) / radial
+        y = (yd - dy) / radial
+    return focal * x + cx, focal * y + cy
+
+
 def make_recording(path, seed=0, size=(240, 180), duration_s=0.8, fps=24.0, velocity=(40.0, -25.0), threshold=0.25,
-                   step_us=1000, focal=200.0):
+                   step_us=1000, focal=200.0, distortion=None):
     """Writes a DAVIS240C recording directory at `path`: events.txt, images.txt + images/frame_<i>.png,
     groundtruth.txt and calib.txt.
 
@@ -208,13 +225,22 @@ def make_recording(path, seed=0, size=(240, 180), duration_s=0.8, fps=24.0, velo
     event (+1 up, -1 down) at a time spread evenly inside the step; the reference moves by the crossings.  Frames
     (8-bit grey PNG, written with Python's zlib) every 1/fps s from t = 1/fps.  Ground truth: the camera translating
     parallel to a plane at depth 1, t = (-vx, -vy, 0) * t / focal, identity rotation; calib.txt: focal, focal, the
-    sensor centre, no distortion.  Returns dict(events=n, frames=n, velocity=(vx, vy))."""
+    sensor centre, no distortion.  Returns dict(events=n, frames=n, velocity=(vx, vy)).
+
+    distortion=(k1, k2, p1, p2): the sensor sits behind a lens with these radial-tangential coefficients (the camera
+    model of include/ebo.h with fx = fy = focal and the sensor centre).  A point of the ideal pinhole image appears at
+    `project` of its position: sensor pixel (x, y) shows the scene at its undistorted position, found by iterating the
+    model's fixed point to convergence.  calib.txt then carries the coefficients (k3 = 0).  The default (None) writes
+    exactly what this function wrote before the keyword existed."""
     w, h = size
     rng = np.random.default_rng(20240601 + seed)
     vx, vy = velocity
     margin = int(np.ceil(max(abs(vx), abs(vy)) * duration_s)) + 4
-    tex = _smooth_texture(rng, h + 2 * margin, w + 2 * margin)
     gx, gy = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+    if distortion is not None:
+        gx, gy = _undistorted_grid(gx, gy, focal, w / 2.0, h / 2.0, *[float(v) for v in distortion])
+        margin += int(np.ceil(max(-gx.min(), gx.max() - (w - 1), -gy.min(), gy.max() - (h - 1), 0.0)))
+    tex = _smooth_texture(rng, h + 2 * margin, w + 2 * margin)
 
     def render(t_us):
         t = t_us * 1e-6
@@ -264,5 +290,8 @@ def make_recording(path, seed=0, size=(240, 180), duration_s=0.8, fps=24.0, velo
             f.write("%d.%06d000 %.9f %.9f 0.0 0.0 0.0 0.0 1.0\n" % (ts // 1000000, ts % 1000000,
                                                                    -vx * ts * 1e-6 / focal, -vy * ts * 1e-6 / focal))
     with open(os.path.join(path, "calib.txt"), "w") as f:
-        f.write("%g %g %g %g 0 0 0 0 0\n" % (focal, focal, w / 2.0, h / 2.0))
+        if distortion is None:
+            f.write("%g %g %g %g 0 0 0 0 0\n" % (focal, focal, w / 2.0, h / 2.0))
+        else:  # calib.txt's order: fx fy cx cy k1 k2 p1 p2 k3
+            f.write("%g %g %g %g %s 0\n" % (focal, focal, w / 2.0, h / 2.0, " ".join(repr(float(v)) for v in distortion)))
     return dict(events=len(ev), frames=i, velocity=(vx, vy))

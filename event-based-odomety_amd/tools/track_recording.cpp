@@ -1,8 +1,10 @@
 // track_recording — the reference's feature-tracking experiment on a DAVIS240C recording directory, without OpenCV:
 //
-//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N]
+//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify]
 //
-// DIR holds events.txt, images.txt + the frames (8-bit grey PNG), optionally groundtruth.txt / calib.txt.  The
+// DIR holds events.txt, images.txt + the frames (8-bit grey PNG), optionally groundtruth.txt / calib.txt.
+// --rectify: the events of every compensation window are undistorted with the recording's calib.txt as they are
+// loaded (tools::EvaluatorParams::rectifyEvents); frames and tracked patches stay in raw coordinates.  The
 // recording is played through tools::Replayer into tools::Evaluator::replay (tools/recording_evaluator.h; the files
 // equal those of per-event callbacks).
 // Writes OUT/trajectory.txt and OUT/final_cost.txt and prints one JSON line: frames, events, tracks (archived patches),
@@ -20,7 +22,7 @@
 
 static int usage(const char* argv0)
 {
-	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N]\n", argv0);
+	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify]\n", argv0);
 	return 2;
 }
 
@@ -29,6 +31,7 @@ int main(int argc, char** argv)
 	std::string dataset, out;
 	bool trackerExperiment = false;
 	size_t windowBatch = 1;
+	bool rectify = false;
 	for (int i = 1; i < argc; ++i)
 	{
 		const std::string a = argv[i];
@@ -43,6 +46,10 @@ int main(int argc, char** argv)
 		else if (a == "--tracker-experiment")
 		{
 			trackerExperiment = true;
+		}
+		else if (a == "--rectify")
+		{
+			rectify = true;
 		}
 		else if (a == "--window-batch" && i + 1 < argc)
 		{
@@ -70,10 +77,16 @@ int main(int argc, char** argv)
 		p.outputDir = out;
 		p.trackerExperiment = trackerExperiment;
 		p.windowBatch = windowBatch;
+		const auto recording = std::make_shared<tools::Davis240cRecording>(dataset);
+		if (rectify)
+		{
+			p.cameraModelParams = recording->getCalibration();
+			p.rectifyEvents = true;
+		}
 		size_t events = 0, frames = 0, tracks = 0, windows = 0;
 		{
 			tools::Evaluator evaluator(p);
-			tools::Replayer replayer(std::make_shared<tools::Davis240cRecording>(dataset));
+			tools::Replayer replayer(recording);
 			evaluator.replay(replayer);
 			evaluator.finish();
 			frames = evaluator.images();
@@ -84,10 +97,10 @@ int main(int argc, char** argv)
 		const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 		std::printf("{\"frames\": %zu, \"events\": %zu, \"tracks\": %zu, \"windows\": %zu, \"total_ms\": %.3f, "
 					"\"ms_per_frame_interval\": %.4f, \"mevents_per_s\": %.4f, \"tracker_experiment\": %s, "
-					"\"window_batch\": %zu}\n",
+					"\"window_batch\": %zu, \"rectify\": %s}\n",
 					frames, events, tracks, windows, ms, frames > 1 ? ms / static_cast<double>(frames - 1) : 0.0,
 					ms > 0 ? static_cast<double>(events) / (ms * 1e3) : 0.0, trackerExperiment ? "true" : "false",
-					windowBatch);
+					windowBatch, rectify ? "true" : "false");
 	}
 	catch (const std::exception& e)
 	{

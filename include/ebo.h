@@ -692,6 +692,63 @@ int ebo_lk_add_image(ebo_ctx* ctx, const uint8_t* image);
 int ebo_lk_track(ebo_ctx* ctx, int n, const float* prev_xy, float* next_xy, uint8_t* status, float* err, int win_w,
 				 int win_h, int max_level, int max_count, double epsilon, double min_eig_threshold);
 
+/* ---- camera model (common::CameraModel, camera_model.h:27-126) --------------------------------
+ * Pinhole + radial-tangential distortion.  ebo_camera is common::CameraModelParams<double> (camera_model.h:13-24)
+ * in ITS field order -- fx fy cx cy k1 k2 k3 p1 p2 -- not calib.txt's (fx fy cx cy k1 k2 p1 p2 k3; the recording
+ * reader untangles that).  All arithmetic is float64, one rounding per operation in exactly the association written
+ * here (no contraction); tests/camera_ref.py restates it.
+ *   tangential(pa, pb, a, b, r2) = ((2 * pa) * a) * b + pb * (r2 + (2 * a) * a)      (getTangentialDistortion, :35-40)
+ *   radial(r2)                   = (1 + k1 * r2) + (k2 * r2) * r2                     (getRadialDistortion, :42-47;
+ *                                  k3 is carried in the struct and never used, as there)
+ *   undistort(u, v) (:91-106):   xD = (u - cx) / fx, yD = (v - cy) / fy; (xOpt, yOpt) = (xD, yD); TEN times:
+ *                                  r2 = xOpt * xOpt + yOpt * yOpt; rad = radial(r2);
+ *                                  dX = tangential(p1, p2, xOpt, yOpt, r2); dY = tangential(p2, p1, yOpt, xOpt, r2);
+ *                                  xOpt = (xD - dX) / rad; yOpt = (yD - dY) / rad
+ *                                ten fixed-point steps, not an inverse to convergence, as there.
+ *   unproject(u, v) (:79-114):   (xOpt, yOpt) = undistort(u, v); norm = sqrt((xOpt * xOpt + yOpt * yOpt) + 1);
+ *                                bearing = (xOpt / norm, yOpt / norm, 1 / norm)
+ *   project(x, y, z) (:49-77):   xP = x / z, yP = y / z; r2 = xP * xP + yP * yP; rad = radial(r2);
+ *                                xDist = xP * rad + tangential(p1, p2, xP, yP, r2);
+ *                                yDist = yP * rad + tangential(p2, p1, yP, xP, r2); (fx * xDist + cx, fy * yDist + cy)
+ *                                (host only: common::CameraModel in the C++ facade; nothing on the device calls it yet)
+ *
+ * ebo_camera_unproject: n points uv [n][2] -> unit bearing vectors bearing_out [n][3], host float64 arrays
+ *   (replaces the per-corner cameraModel_->unproject calls of visual_odometry.cpp:234,367,369,516,518);
+ *   synchronous.  The _device form takes device pointers and runs asynchronously on the context's stream.  The
+ *   parameters are not validated (fx == 0 gives the infinities the rule gives).  Both return EBO_ERR_STATE
+ *   while a graph is being recorded.
+ *
+ * ebo_set_rectification: builds, for every sensor pixel (x, y) of the context's image size, the map
+ *     (xOpt, yOpt) = undistort(x, y); u = fx * xOpt + cx; v = fy * yOpt + cy          (float64 [image_h][image_w][2])
+ *   and the lookup table (round(u), round(v)), half away from zero (the rounding of the reference's count images,
+ *   feature_detector.cpp:446-453), int16 [image_h][image_w][2].  The rectified camera keeps fx fy cx cy.
+ *   Refused with EBO_ERR_RANGE, so that the loaders need no new error path: fx or fy not finite or zero, a pixel
+ *   whose map is not finite, a rounded coordinate outside [-16384, 16383] (what an event record holds).  A refused
+ *   call leaves NO rectification set.  EBO_ERR_STATE while a graph is being recorded.
+ *   While a rectification is set, every loader that buckets events by the patch grid reads them through the table:
+ *   ebo_set_window, ebo_set_windows, ebo_set_windows_device, ebo_set_windows8, ebo_set_windows8_device, and through
+ *   them ebo_compensate_events_contrast and ebo_compensate_windows.  The caller's events are not modified.  An event
+ *   whose RAW coordinate lies outside the sensor is left as it is (a stray stays a stray); an in-sensor event whose
+ *   table entry lies outside the sensor goes to its window's stray unit.  The result is bit for bit that of loading
+ *   the events with their coordinates replaced on the host, with no rectification set; everything after the load
+ *   (objective, solves, count images) then works in rectified geometry.
+ *   It affects the NEXT load, never the windows already resident.
+ *   NOT rectified: ebo_route_set_events and the tracker objective (they align events with frame gradients, and
+ *   frames stay raw), ebo_patch_integrate*, the float32 motion field of EBO_COUNT_FIELD, and ebo_set_patches,
+ *   which returns EBO_ERR_UNSUPPORTED while a rectification is set instead of silently ignoring it.
+ * ebo_clear_rectification: later loads read raw coordinates again, exactly as a context that never had one.
+ * ebo_rectification_map: copies out the map and / or the table of the rectification that is set (either pointer may
+ *   be NULL); EBO_ERR_STATE when none is set. */
+typedef struct ebo_camera
+{
+	double fx, fy, cx, cy, k1, k2, k3, p1, p2;
+} ebo_camera;
+int ebo_camera_unproject(ebo_ctx* ctx, const ebo_camera* cam, int n, const double* uv, double* bearing_out);
+int ebo_camera_unproject_device(ebo_ctx* ctx, const ebo_camera* cam, int n, const double* d_uv, double* d_bearing_out);
+int ebo_set_rectification(ebo_ctx* ctx, const ebo_camera* cam);
+int ebo_clear_rectification(ebo_ctx* ctx);
+int ebo_rectification_map(ebo_ctx* ctx, double* map_xy_f64_out, int16_t* lut_i16_out);
+
 /* Device-side timing of everything enqueued between begin and end on the
  * context's stream (hipEvent based). */
 int ebo_timer_begin(ebo_ctx* ctx);
