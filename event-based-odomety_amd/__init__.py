@@ -125,6 +125,29 @@ def camera(v):
     return Camera(*[float(x) for x in v])
 
 
+class TwoViewParams(C.Structure):
+    """ebo_two_view_params: threshold, probability, max_iterations, seed of ebo_relative_pose_ransac."""
+    _fields_ = [("threshold", C.c_double), ("probability", C.c_double), ("max_iterations", C.c_int),
+                ("reserved", C.c_int), ("seed", C.c_uint64)]
+
+
+class TwoViewResult(C.Structure):
+    """ebo_two_view_result: one keyframe pair's RANSAC answer."""
+    _fields_ = [("found", C.c_int), ("winner", C.c_int), ("iterations", C.c_int), ("n_inliers", C.c_int),
+                ("inlier_offset", C.c_int), ("reserved", C.c_int), ("model", C.c_double * 12)]
+
+
+def two_view_params(**kw):
+    """The defaults of ebo_default_two_view_params (5e-5, 0.99, 1000 hypotheses, seed 0), with overrides."""
+    p = TwoViewParams()
+    lib().ebo_default_two_view_params(C.byref(p))
+    for key, val in kw.items():
+        if not hasattr(p, key):
+            raise AttributeError(key)
+        setattr(p, key, val)
+    return p
+
+
 class EboError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("ebo error %d: %s" % (code, msg))
@@ -166,6 +189,19 @@ def lib():
         _lib.ebo_lm_request.argtypes = [C.c_void_p, C.c_void_p]
         _lib.ebo_lm_supply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.ebo_lm_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ebo_default_two_view_params.restype = None
+        _lib.ebo_two_view_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _tv = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+               C.c_void_p, C.c_void_p]
+        _lib.ebo_relative_pose_ransac.argtypes = _tv
+        _lib.ebo_relative_pose_ransac_device.argtypes = _tv
+        _sc = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+        _lib.ebo_relative_pose_scores.argtypes = _sc
+        _lib.ebo_relative_pose_scores_device.argtypes = _sc
+        _tr = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ebo_triangulate.argtypes = _tr
+        _lib.ebo_triangulate_device.argtypes = _tr
+        _lib.ebo_epipolar_inliers.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
     return _lib
 
 
@@ -1052,6 +1088,95 @@ class Context:
         lut = np.zeros((h, w, 2), dtype=np.int16)
         self._check(lib().ebo_rectification_map(self._h, _dp(m), _vp(lut)))
         return m, lut
+
+    # -- two-view geometry (eight-point RANSAC, triangulation, the epipolar test) ---------------------
+    def relative_pose_ransac(self, offsets, f1, f2, params=None, diagnostics=False, device=False):
+        """ebo_relative_pose_ransac over len(offsets) - 1 keyframe pairs.  f1, f2: float64 [total][3] unit bearing
+        vectors (device=True: device pointers as int, and the _device entry).  -> list of dicts (found, model [3][4],
+        winner, iterations, n_inliers, inliers int32 [n_inliers]); with diagnostics=True also a dict of every
+        hypothesis's counts [pairs][H], models [pairs][H][3][4] and samples [pairs][H][8]."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        n_pairs = len(offsets) - 1
+        prm = params if params is not None else two_view_params()
+        total = int(offsets[-1]) if n_pairs >= 0 and len(offsets) else 0
+        if device:
+            p1, p2 = C.c_void_p(int(f1)), C.c_void_p(int(f2))
+            fn = lib().ebo_relative_pose_ransac_device
+        else:
+            f1 = np.ascontiguousarray(f1, dtype=np.float64).reshape(-1, 3)
+            f2 = np.ascontiguousarray(f2, dtype=np.float64).reshape(-1, 3)
+            if len(f1) != total or len(f2) != total:
+                raise ValueError("f1 / f2 must hold offsets[-1] bearing vectors")
+            p1, p2 = _vp(f1), _vp(f2)
+            fn = lib().ebo_relative_pose_ransac
+        res = (TwoViewResult * max(n_pairs, 1))()
+        idx = np.zeros(max(total, 1), dtype=np.int32)
+        H = max(int(prm.max_iterations), 1)
+        diag = None
+        if diagnostics:
+            diag = dict(counts=np.zeros((max(n_pairs, 0), H), dtype=np.int32), models=np.zeros((max(n_pairs, 0), H, 3, 4)),
+                        samples=np.zeros((max(n_pairs, 0), H, 8), dtype=np.int32))
+        self._check(fn(self._h, n_pairs, _vp(offsets), p1, p2, C.byref(prm), res, _vp(idx),
+                       _vp(diag["counts"]) if diag else None, _vp(diag["models"]) if diag else None,
+                       _vp(diag["samples"]) if diag else None))
+        out = []
+        for p in range(n_pairs):
+            r = res[p]
+            out.append(dict(found=bool(r.found), model=np.array(r.model[:]).reshape(3, 4), winner=r.winner,
+                            iterations=r.iterations, n_inliers=r.n_inliers,
+                            inliers=idx[r.inlier_offset:r.inlier_offset + r.n_inliers].copy()))
+        return (out, diag) if diagnostics else out
+
+    def two_view_timing(self, enable=True):
+        """ebo_two_view_timing: -> the last timed RANSAC call's (hypotheses, counting, host walk, inlier list, whole call)
+        in ms, and switches the timing on or off for the calls that follow."""
+        ms = (C.c_float * 5)()
+        self._check(lib().ebo_two_view_timing(self._h, 1 if enable else 0, ms))
+        return tuple(ms)
+
+    def relative_pose_scores(self, model, f1, f2, threshold=5e-5):
+        """ebo_relative_pose_scores: -> (scores float64 [n], inlier flags bool [n]) of a given model [3][4]."""
+        model = np.ascontiguousarray(model, dtype=np.float64).reshape(3, 4)
+        f1 = np.ascontiguousarray(f1, dtype=np.float64).reshape(-1, 3)
+        f2 = np.ascontiguousarray(f2, dtype=np.float64).reshape(-1, 3)
+        n = len(f1)
+        sc = np.zeros(n)
+        fl = np.zeros(n, dtype=np.uint8)
+        self._check(lib().ebo_relative_pose_scores(self._h, _vp(model), n, _vp(f1), _vp(f2), C.c_double(threshold), _vp(sc),
+                                                   _vp(fl)))
+        return sc, fl.astype(bool)
+
+    def relative_pose_scores_device(self, model, n, d_f1, d_f2, threshold, d_scores=0, d_flags=0):
+        """The same on device arrays (pointers as int; either output may be 0), asynchronous on the context's stream."""
+        model = np.ascontiguousarray(model, dtype=np.float64).reshape(3, 4)
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        self._check(lib().ebo_relative_pose_scores_device(self._h, _vp(model), int(n), p(d_f1), p(d_f2), C.c_double(threshold),
+                                                          p(d_scores), p(d_flags)))
+
+    def triangulate(self, poses, pose_pair, f1, f2):
+        """ebo_triangulate: poses float64 [n_poses][3][4] camera-to-world, pose_pair int [n][2] -> world points [n][3]."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3, 4)
+        pose_pair = np.ascontiguousarray(pose_pair, dtype=np.int32).reshape(-1, 2)
+        f1 = np.ascontiguousarray(f1, dtype=np.float64).reshape(-1, 3)
+        f2 = np.ascontiguousarray(f2, dtype=np.float64).reshape(-1, 3)
+        n = len(f1)
+        out = np.zeros((n, 3))
+        self._check(lib().ebo_triangulate(self._h, len(poses), _vp(poses), n, _vp(pose_pair), _vp(f1), _vp(f2), _vp(out)))
+        return out
+
+    def triangulate_device(self, n_poses, d_poses, n, d_pose_pair, d_f1, d_f2, d_points):
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        self._check(lib().ebo_triangulate_device(self._h, int(n_poses), p(d_poses), int(n), p(d_pose_pair), p(d_f1), p(d_f2),
+                                                 p(d_points)))
+
+    def epipolar_inliers(self, model, f1, f2, threshold):
+        """ebo_epipolar_inliers: |f1^T E f2| < threshold with E = hat(t / |t|) R -> bool [n]."""
+        model = np.ascontiguousarray(model, dtype=np.float64).reshape(3, 4)
+        f1 = np.ascontiguousarray(f1, dtype=np.float64).reshape(-1, 3)
+        f2 = np.ascontiguousarray(f2, dtype=np.float64).reshape(-1, 3)
+        fl = np.zeros(len(f1), dtype=np.uint8)
+        self._check(lib().ebo_epipolar_inliers(self._h, _vp(model), len(f1), _vp(f1), _vp(f2), C.c_double(threshold), _vp(fl)))
+        return fl.astype(bool)
 
     # -- timing --------------------------------------------------------------
     def timer_begin(self):

@@ -1603,6 +1603,10 @@ void ebo_destroy(ebo_ctx* c)
 	hipFree(c->d_fe_pts);
 	if (c->ev0) hipEventDestroy(c->ev0);
 	if (c->ev1) hipEventDestroy(c->ev1);
+	for (hipEvent_t e : c->tv_ev)
+	{
+		if (e) hipEventDestroy(e);
+	}
 	if (c->own_stream && c->stream)
 	{
 		hipStreamDestroy(c->stream);

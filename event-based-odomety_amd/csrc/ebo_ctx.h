@@ -167,6 +167,10 @@ struct ebo_ctx
 	size_t pin_cap = 0;
 
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
+	// ebo_two_view_timing (ebo_twoview.cpp): events around the phases of ebo_relative_pose_ransac, created on first use
+	hipEvent_t tv_ev[5] = {};
+	bool tv_timing = false;
+	float tv_ms[5] = {};  // hypothesis kernel, counting kernel, host walk, winner upload + inlier-list kernel, whole call (wall clock)
 	int max_rw = 0, max_rh = 0;
 	int grid_max_rw = 0, grid_max_rh = 0;
 	// the REGULAR patch of the loaded units (the grid's patch size; of patches loaded by ebo_set_patches the

@@ -509,4 +509,21 @@ int launch_camera_unproject(const CameraConsts& k, int n, const double* d_uv, do
 // d_map: double [h][w][2], d_lut: int16 [h][w][2], *d_bad: error bits (zeroed here)
 int launch_rectify_map(const CameraConsts& k, int w, int h, double* d_map, void* d_lut, int* d_bad, void* stream);
 
+// two-view geometry (ebo_twoview.inc, ebo_twoview.cpp).  models: [n_pairs * H][3][4]; d_samples may be null.
+int launch_tv_hypotheses(int n_pairs, int H, const int* d_offsets, const double* d_f1, const double* d_f2, uint64_t seed,
+						 double* d_models, int* d_valid, int* d_samples, void* stream);
+// d_counts [n_pairs * H] must be zero on entry; max_n: correspondences of the largest pair
+int launch_tv_count(int n_pairs, int H, int max_n, const int* d_offsets, const double* d_f1, const double* d_f2,
+					const double* d_models, const int* d_valid, double threshold, int* d_counts, void* stream);
+int launch_tv_winner_flags(int n_pairs, int H, int max_n, const int* d_offsets, const double* d_f1, const double* d_f2,
+						   const double* d_models, const int* d_valid, const int* d_winner, double threshold,
+						   unsigned char* d_flags, double* d_win_models, void* stream);
+// model12: HOST pointer to a [3][4] model (travels as a kernel argument); either output may be null
+int launch_tv_scores(const double* model12, int n, const double* d_f1, const double* d_f2, double threshold, double* d_scores,
+					 unsigned char* d_flags, void* stream);
+int launch_tv_triangulate(int n_poses, const double* d_poses, int n, const int* d_pose_pair, const double* d_f1,
+						  const double* d_f2, double* d_points, void* stream);
+int launch_tv_epipolar(const double* model12, int n, const double* d_f1, const double* d_f2, double threshold,
+					   unsigned char* d_flags, void* stream);
+
 }  // namespace ebo

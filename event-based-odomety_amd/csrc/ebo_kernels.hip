@@ -1267,6 +1267,7 @@ __global__ void __launch_bounds__(64) k_route(const uint32_t* __restrict__ xy, u
 #include "ebo_edge.inc"
 #include "ebo_bucket.inc"
 #include "ebo_camera.inc"
+#include "ebo_twoview.inc"
 #include "ebo_field.inc"
 #include "ebo_fieldtv.inc"
 #include "ebo_optimizer.inc"
@@ -1815,6 +1816,87 @@ int launch_rectify_map(const CameraConsts& k, int w, int h, double* d_map, void*
 	}
 	hipLaunchKernelGGL(k_rectify_map, dim3((w * h + 255) / 256), dim3(256), 0, s, k, w, h, d_map, static_cast<short2*>(d_lut),
 					   d_bad);
+	return check_launch();
+}
+
+// two-view geometry (ebo_twoview.inc)
+int launch_tv_hypotheses(int n_pairs, int H, const int* d_offsets, const double* d_f1, const double* d_f2, uint64_t seed,
+						 double* d_models, int* d_valid, int* d_samples, void* stream)
+{
+	const long long total = static_cast<long long>(n_pairs) * H;
+	if (total <= 0)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_tv_hypotheses, dim3(static_cast<unsigned int>((total + kTvGroups - 1) / kTvGroups)), dim3(256), 0,
+					   static_cast<hipStream_t>(stream), n_pairs, H, d_offsets, d_f1, d_f2, static_cast<unsigned long long>(seed),
+					   d_models, d_valid, d_samples);
+	return check_launch();
+}
+
+int launch_tv_count(int n_pairs, int H, int max_n, const int* d_offsets, const double* d_f1, const double* d_f2,
+					const double* d_models, const int* d_valid, double threshold, int* d_counts, void* stream)
+{
+	if (n_pairs <= 0 || H <= 0 || max_n < 8)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_tv_count, dim3((H + kTvHypChunk - 1) / kTvHypChunk, n_pairs, (max_n + kTvTile - 1) / kTvTile), dim3(256), 0,
+					   static_cast<hipStream_t>(stream), H, d_offsets, d_f1, d_f2, d_models, d_valid, threshold, d_counts);
+	return check_launch();
+}
+
+int launch_tv_winner_flags(int n_pairs, int H, int max_n, const int* d_offsets, const double* d_f1, const double* d_f2,
+						   const double* d_models, const int* d_valid, const int* d_winner, double threshold,
+						   unsigned char* d_flags, double* d_win_models, void* stream)
+{
+	if (n_pairs <= 0)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_tv_winner_flags, dim3(max_n > 0 ? (max_n + 255) / 256 : 1, n_pairs), dim3(256), 0,
+					   static_cast<hipStream_t>(stream), H, d_offsets, d_f1, d_f2, d_models, d_valid, d_winner, threshold, d_flags,
+					   d_win_models);
+	return check_launch();
+}
+
+int launch_tv_scores(const double* model12, int n, const double* d_f1, const double* d_f2, double threshold, double* d_scores,
+					 unsigned char* d_flags, void* stream)
+{
+	if (n <= 0)
+	{
+		return 0;
+	}
+	TvModelArg m;
+	std::copy(model12, model12 + 12, m.m);
+	hipLaunchKernelGGL(k_tv_scores, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), m, n, d_f1, d_f2,
+					   threshold, d_scores, d_flags);
+	return check_launch();
+}
+
+int launch_tv_triangulate(int n_poses, const double* d_poses, int n, const int* d_pose_pair, const double* d_f1,
+						  const double* d_f2, double* d_points, void* stream)
+{
+	if (n <= 0)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_tv_triangulate, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), n_poses, d_poses, n,
+					   d_pose_pair, d_f1, d_f2, d_points);
+	return check_launch();
+}
+
+int launch_tv_epipolar(const double* model12, int n, const double* d_f1, const double* d_f2, double threshold,
+					   unsigned char* d_flags, void* stream)
+{
+	if (n <= 0)
+	{
+		return 0;
+	}
+	TvModelArg m;
+	std::copy(model12, model12 + 12, m.m);
+	hipLaunchKernelGGL(k_tv_epipolar, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), m, n, d_f1, d_f2,
+					   threshold, d_flags);
 	return check_launch();
 }
 

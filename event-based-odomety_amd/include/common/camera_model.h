@@ -73,6 +73,13 @@ struct FixedVec
 	const Scalar& operator()(int i) const { return v[i]; }
 	Scalar* data() { return v; }
 	const Scalar* data() const { return v; }
+	const Scalar& x() const { return v[0]; }
+	const Scalar& y() const { return v[1]; }
+	const Scalar& z() const
+	{
+		static_assert(N >= 3, "three components");
+		return v[2];
+	}
 };
 
 template <typename Scalar = double>

@@ -15,7 +15,7 @@
 // (cv::imread would hand back an empty cv::Mat and the tracker would run on it).
 //
 // Without Sophus and OpenCV on the include path the value types are stand-ins with the members the tracker side uses:
-// common::Pose3d (unit quaternion + translation: matrix(), rotationMatrix(), translation()), common::GroundTruthSample,
+// common::Pose3d (common/data_types.h: matrix(), rotationMatrix(), translation()), common::GroundTruthSample,
 // and common::GroundTruth (common::CameraModelParams<Scalar> and CameraModel are in common/camera_model.h).  With
 // Sophus, common::Pose3d is Sophus::SE3d as in the reference (common/geometry.h:14).
 #pragma once
@@ -31,93 +31,15 @@
 #include "../common/camera_model.h"  // common::CameraModelParams<Scalar>
 #include "davis240c_reader.h"
 
-#if defined(__has_include)
-#if __has_include(<sophus/se3.hpp>)
-#include <sophus/se3.hpp>
-#define EBO_HAVE_SOPHUS 1
-#endif
-#endif
-
 namespace common
 {
+// common::Pose3d is in common/data_types.h: Sophus::SE3d with Sophus on the include path, the stand-in without
 #ifdef EBO_HAVE_SOPHUS
-using Pose3d = Sophus::SE3d;
 inline Pose3d makePose3d(double qw, double qx, double qy, double qz, double tx, double ty, double tz)
 {
 	return Sophus::SE3d(Eigen::Quaterniond(qw, qx, qy, qz), Sophus::SE3d::Point(tx, ty, tz));  // (SO3 normalises)
 }
 #else
-// Sophus::SE3d stand-in: a unit quaternion (stored x, y, z, w as Eigen does) and a translation.
-struct Pose3d
-{
-	struct Matrix3
-	{
-		double m[3][3];
-		double operator()(int r, int c) const { return m[r][c]; }
-	};
-	struct Matrix4
-	{
-		double m[4][4];
-		double operator()(int r, int c) const { return m[r][c]; }
-	};
-	struct Vector3
-	{
-		double v[3];
-		double operator()(int i) const { return v[i]; }
-		double x() const { return v[0]; }
-		double y() const { return v[1]; }
-		double z() const { return v[2]; }
-	};
-
-	double q[4] = {0.0, 0.0, 0.0, 1.0};
-	double t[3] = {0.0, 0.0, 0.0};
-
-	Pose3d() = default;
-	// Sophus::SE3d(Eigen::Quaterniond(qw, qx, qy, qz), t): the quaternion is normalised (Eigen's normalize())
-	Pose3d(double qw, double qx, double qy, double qz, double tx, double ty, double tz)
-	{
-		const double n = std::sqrt(qx * qx + qy * qy + qz * qz + qw * qw);
-		if (!(n > 0.0) || !std::isfinite(n))
-		{
-			throw std::runtime_error("common::Pose3d: the quaternion has no direction");
-		}
-		q[0] = qx / n;
-		q[1] = qy / n;
-		q[2] = qz / n;
-		q[3] = qw / n;
-		t[0] = tx;
-		t[1] = ty;
-		t[2] = tz;
-	}
-	// Eigen::Quaterniond::toRotationMatrix
-	Matrix3 rotationMatrix() const
-	{
-		const double x = q[0], y = q[1], z = q[2], w = q[3];
-		const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-		const double twx = tx * w, twy = ty * w, twz = tz * w;
-		const double txx = tx * x, txy = ty * x, txz = tz * x;
-		const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-		return Matrix3{{{1 - (tyy + tzz), txy - twz, txz + twy},
-						{txy + twz, 1 - (txx + tzz), tyz - twx},
-						{txz - twy, tyz + twx, 1 - (txx + tyy)}}};
-	}
-	Matrix4 matrix() const
-	{
-		const Matrix3 r = rotationMatrix();
-		Matrix4 out{};
-		for (int i = 0; i < 3; ++i)
-		{
-			for (int j = 0; j < 3; ++j)
-			{
-				out.m[i][j] = r.m[i][j];
-			}
-			out.m[i][3] = t[i];
-		}
-		out.m[3][3] = 1.0;
-		return out;
-	}
-	Vector3 translation() const { return Vector3{{t[0], t[1], t[2]}}; }
-};
 inline Pose3d makePose3d(double qw, double qx, double qy, double qz, double tx, double ty, double tz)
 {
 	return Pose3d(qw, qx, qy, qz, tx, ty, tz);

@@ -749,6 +749,150 @@ int ebo_set_rectification(ebo_ctx* ctx, const ebo_camera* cam);
 int ebo_clear_rectification(ebo_ctx* ctx);
 int ebo_rectification_map(ebo_ctx* ctx, double* map_xy_f64_out, int16_t* lut_i16_out);
 
+/* ---- two-view geometry: eight-point RANSAC, triangulation, the epipolar test -------------------
+ * What VisualOdometryFrontEnd::initCameras / findInliersRansac (visual_odometry.cpp:176-210, 288-341) and
+ * triangulation.cpp:7-63 do through OpenGV, stated here as this project's own rules (OpenGV's source is not part of
+ * the reference tree, so parity with it is NOT claimed).  tests/twoview_ref.py restates every rule in numpy.
+ * Float64 throughout, one rounding per operation in exactly the association written here, no contraction.
+ * A *model* is (R12, t12), double [3][4] row-major = [R | t], taking camera-2 coordinates to camera-1 coordinates;
+ * f1[i], f2[i] are the unit bearing vectors of correspondence i in cameras 1 and 2.
+ *   dot(a, b) = (a0 * b0 + a1 * b1) + a2 * b2.   cross(a, b) = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0).
+ *
+ * 1. triangulate2(R, t, f1, f2) (midpoint; what triangulateLandmarks calls, triangulation.cpp:26):
+ *      g_i = dot(R[i][:], f2);  b0 = dot(t, f1);  b1 = dot(t, g);
+ *      a00 = dot(f1, f1);  a01 = -dot(f1, g);  a10 = dot(f1, g);  a11 = -dot(g, g);
+ *      det = a00 * a11 - a01 * a10;  l0 = (a11 * b0 - a01 * b1) / det;  l1 = (a00 * b1 - a10 * b0) / det;
+ *      p_i = (l0 * f1_i + (t_i + l1 * g_i)) / 2                                 (camera-1 coordinates)
+ *    Poses: inverse(R, t) = (R^T, -(R^T t)) with (R^T t)_i = dot(R[:][i], t);
+ *           (Ra, ta)(Rb, tb) = (Ra Rb, Ra tb + ta) with (Ra Rb)[i][j] = dot(Ra[i][:], Rb[:][j]),
+ *           (Ra tb + ta)_i = dot(Ra[i][:], tb) + ta_i;  (R, t) * p = (dot(R[i][:], p) + t_i)_i.
+ *    triangulateLandmarks(pose1, pose2, ..) = pose1 * triangulate2(inverse(pose1) * pose2, f1, f2).
+ * 2. score(model, i) (the bearing-vector reprojection criterion):
+ *      p = triangulate2(R, t, f1, f2);  r1 = p / sqrt(dot(p, p));  d = p - t;
+ *      q_j = (R[0][j] * d0 + R[1][j] * d1) + R[2][j] * d2;  r2 = q / sqrt(dot(q, q));
+ *      score = (1 - dot(f1, r1)) + (1 - dot(f2, r2)).
+ *    Correspondence i is an inlier when score < threshold; a NaN score is not an inlier.  The reference's default
+ *    threshold is VisualOdometryParams::ransacThreshold = 5e-5.
+ * 3. Sampling.  mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *    return z ^ (z >> 31) (splitmix64's finaliser; uint64 arithmetic, wrapping).  G = 0x9E3779B97F4A7C15.
+ *      hash(seed, p, h, d) = mix((mix((mix((mix(seed + G) ^ p) + G) ^ h) + G) ^ d) + G)
+ *    Hypothesis h of pair p draws 8 distinct indices of 0 .. n-1 by the first 8 steps of a Fisher-Yates shuffle of
+ *    the identity permutation: for d = 0 .. 7, j = d + (hash(seed, p, h, d) >> 32) mod (n - d); sample[d] = perm[j];
+ *    perm[j] = perm[d].  Integers only: device, host and restatement agree exactly, and a hypothesis does not
+ *    depend on which others are evaluated.
+ * 4. Eight-point solve.  Row i (i = 0 .. 7, in sample order) of the 8 x 9 matrix A is (f2x * f1, f2y * f1, f2z * f1),
+ *    A[i][3a + b] = f2[i]_a * f1[i]_b.  e = the eigenvector of A^T A for its smallest eigenvalue, from a ONE-SIDED
+ *    (Hestenes) Jacobi iteration on the columns of A, which never forms A^T A and so does not square A's condition
+ *    number.  col(p, q) = sum over the rows i, left to right, of A[i][p] * A[i][q].  V = identity (9 x 9); TEN
+ *    times, for p = 0 .. 7, for q = p+1 .. 8:
+ *      app = col(p, p); aqq = col(q, q); apq = col(p, q); skipped when apq == 0 exactly;
+ *      rotation(app, aqq, apq): theta = (aqq - app) / (2 * apq);  sgn = -1 if theta < 0 else +1;
+ *        t = sgn / (|theta| + sqrt(theta * theta + 1));  c = 1 / sqrt(t * t + 1);  s = t * c;
+ *      for every row i of A and of V, from the old pair: X[i][p] = c * X[i][p] - s * X[i][q];
+ *                                                        X[i][q] = s * X[i][p] + c * X[i][q].
+ *    Then d[j] = col(j, j); e = the column of V of the smallest d[j] (the FIRST of equals: j replaces the current
+ *    minimum only when d[j] < it).  F[b][a] = e[3a + b], so that f1^T F f2 = 0.
+ *    jacobi(M, sweeps), M symmetric 3 x 3, V = identity: `sweeps` times, for (p, q) = (0,1) (0,2) (1,2):
+ *      apq = M[p][q]; skipped when apq == 0 exactly; app = M[p][p]; aqq = M[q][q]; (t, c, s) = rotation(app, aqq, apq);
+ *      for the k that is neither p nor q, from the old pair: M[k][p] = M[p][k] = c * M[k][p] - s * M[k][q];
+ *                                                            M[k][q] = M[q][k] = s * M[k][p] + c * M[k][q];
+ *      M[p][p] = app - t * apq;  M[q][q] = aqq + t * apq;  M[p][q] = M[q][p] = 0;
+ *      for every k, from the old pair: V[k][p] = c * V[k][p] - s * V[k][q];  V[k][q] = s * V[k][p] + c * V[k][q].
+ *    Eigenvalues are the diagonal, eigenvectors the columns of V.
+ *    3 x 3 SVD of F: G = F^T F, G[j][k] = dot(F[:][j], F[:][k]); (d, V) = jacobi(G, 8); the three (d_c, column c)
+ *    are put in descending order by the compare-exchanges (0,1) (1,2) (0,1), each swapping only when
+ *    d_a < d_b (stable; a NaN never swaps); s0 = sqrt(d_0), s1 = sqrt(d_1); NO MODEL unless s0 > 0 and s1 > 0.
+ *      u0_i = dot(F[i][:], v0) / s0;  u0 = u0 / sqrt(dot(u0, u0));
+ *      u1_i = dot(F[i][:], v1) / s1;  u1 = u1 - dot(u0, u1) * u0;  u1 = u1 / sqrt(dot(u1, u1));
+ *      u2 = cross(u0, u1);  v2 = cross(v0, v1).
+ *    (The essential matrix itself, U diag(1,1,0) V^T, is never formed: rule 5 needs only U and V.)
+ * 5. Disambiguation.  With W = [[0,-1,0],[1,0,0],[0,0,1]]: Ra = U W V^T, Rb = U W^T V^T, entry by entry
+ *      Ra[i][j] = (u1_i * v0_j - u0_i * v1_j) + u2_i * v2_j;   Rb[i][j] = (u0_i * v1_j - u1_i * v0_j) + u2_i * v2_j;
+ *    each negated when det < 0, det(R) = (R00 * (R11*R22 - R12*R21) - R01 * (R10*R22 - R12*R20)) + R02 * (R10*R21 - R11*R20);
+ *    t = +u2 or -u2.  Of the four (R, t) in the fixed order (Ra,+) (Ra,-) (Rb,+) (Rb,-) the model is the FIRST with
+ *    the smallest sum, left to right in sample order, of the 8 sample scores; a sum that is not finite counts as
+ *    +infinity; if all four are, the hypothesis has no model and zero inliers.  A hypothesis without a model is
+ *    written out as an all-zero [3][4].
+ * 6. Selection = the serial loop's answer.  count[h] = inliers of hypothesis h.  best = -1, k = max_iterations; for
+ *    h = 0, 1, ..: when count[h] > best (strictly: the earliest of equals wins) best = count[h], winner = h,
+ *    w = best / n, k = log(1 - probability) / log(clamp(1 - w^8, 1e-15, 1 - 1e-15)) with w^8 by three squarings;
+ *    stop after hypothesis h when h + 1 >= k or h + 1 == max_iterations; iterations = h + 1.  Runs on the host, in
+ *    double, with the C library's log.  FOUND when best >= 8.
+ * 7. computeEssential(T) (triangulation.cpp:31-37) = hat(t / |t|) R:  u = t / sqrt(dot(t, t));
+ *      E[0][j] = uy * R[2][j] - uz * R[1][j];  E[1][j] = uz * R[0][j] - ux * R[2][j];  E[2][j] = ux * R[1][j] - uy * R[0][j].
+ *    findInliersEssential (triangulation.cpp:39-63): w_i = dot(E[i][:], f2); flag = |dot(f1, w)| < threshold.
+ *
+ * ebo_relative_pose_ransac (replaces opengv::sac::Ransac::computeModel over CentralRelativePoseSacProblem(EIGHTPT),
+ *   visual_odometry.cpp:298-314, for MANY keyframe pairs in one call): pair p owns correspondences
+ *   offsets[p] .. offsets[p+1]-1 of f1 / f2 (double [offsets[n_pairs]][3]; offsets[0] = 0).  ALL
+ *   n_pairs x max_iterations hypotheses are sampled, solved (rules 3-5) and scored against every correspondence of
+ *   their pair (rule 2) on the device in one pass; the counts come back once, rule 6 runs on the host, and one more
+ *   launch lists the winners' inliers.  result[p]: found, winner (-1: no hypothesis), iterations, n_inliers,
+ *   inlier_offset (= offsets[p]) and the winner's model; inlier_idx[inlier_offset .. + n_inliers) are the winner's
+ *   inliers as indices WITHIN the pair, ascending (inlier_idx has room for offsets[n_pairs] ints).  A pair with
+ *   fewer than 8 correspondences is not found (winner -1, iterations 0), not an error.  Optional outputs, NULL to
+ *   skip at no cost: hyp_counts int [n_pairs][max_iterations], hyp_models double [n_pairs][max_iterations][3][4],
+ *   hyp_samples int [n_pairs][max_iterations][8] (all zero for a pair with fewer than 8 correspondences).
+ *   A pair's result does not depend on the other pairs of the call.
+ *   EBO_ERR_ARG: max_iterations outside [1, 4096], probability outside (0, 1), threshold not positive (or NaN),
+ *   a pair with more than 65535 correspondences, more than 65535 pairs, decreasing offsets, a needed pointer NULL.
+ *   Synchronous.  EBO_ERR_STATE while a graph is being recorded (all entries of this section).
+ * ebo_relative_pose_scores: rule 2 for a GIVEN model and n correspondences: scores double [n] and / or inlier flags
+ *   uint8 [n] (either may be NULL).  The re-selection after a refinement (visual_odometry.cpp:325-328,
+ *   ransac.sac_model_->selectWithinDistance).
+ * ebo_triangulate (triangulateLandmarks, triangulation.cpp:7-29, with a pose pair PER POINT, which is how
+ *   addNewLandmarks calls it, visual_odometry.cpp:343-377): poses double [n_poses][3][4] camera-to-world;
+ *   point i is seen along f1[i] from poses[pose_pair[i][0]] and along f2[i] from poses[pose_pair[i][1]];
+ *   points_out[i] = the world point of rule 1.  A pose index outside [0, n_poses) is EBO_ERR_ARG (the _device form,
+ *   which cannot look, writes NaN for that point).
+ * ebo_epipolar_inliers (findInliersEssential): rule 7, flags uint8 [n].
+ * The _device forms take device pointers for the bearing vectors (and, for scores and triangulate, for every other
+ *   array except `model`), so that the output of ebo_camera_unproject_device never visits the host; the scores and
+ *   triangulate forms are asynchronous on the context's stream; the RANSAC form still returns its results to host
+ *   arrays and is synchronous.
+ * ebo_two_view_timing: with `enable` non-zero every later ebo_relative_pose_ransac brackets its phases with events
+ *   on the context's stream; ms5_or_null receives the LAST such call's times in milliseconds: [0] hypothesis kernel,
+ *   [1] counting kernel, [2] host walk of rule 6 (wall clock), [3] upload of the winners' indices + inlier-list kernel,
+ *   [4] the whole call (wall clock).  [4] - ([0] + [1] + [2] + [3]) is everything else: the uploads of the bearing
+ *   vectors and offsets, the copy of the counts to the host and the copies of the results.  Zeros before the first
+ *   timed call.  For tools/time_two_view.py; off by default, when nothing is recorded. */
+typedef struct ebo_two_view_params
+{
+	double threshold;    /* rule 2; default 5e-5 */
+	double probability;  /* rule 6; default 0.99 */
+	int max_iterations;  /* hypotheses per pair, 1 .. 4096; default 1000 */
+	int reserved;        /* 0 */
+	uint64_t seed;       /* rule 3; default 0 */
+} ebo_two_view_params;
+typedef struct ebo_two_view_result
+{
+	int found;
+	int winner;
+	int iterations;
+	int n_inliers;
+	int inlier_offset;
+	int reserved;
+	double model[3][4];
+} ebo_two_view_result;
+void ebo_default_two_view_params(ebo_two_view_params* params);
+int ebo_two_view_timing(ebo_ctx* ctx, int enable, float* ms5_or_null);
+int ebo_relative_pose_ransac(ebo_ctx* ctx, int n_pairs, const int* offsets, const double* f1, const double* f2,
+							 const ebo_two_view_params* params, ebo_two_view_result* result, int* inlier_idx,
+							 int* hyp_counts_or_null, double* hyp_models_or_null, int* hyp_samples_or_null);
+int ebo_relative_pose_ransac_device(ebo_ctx* ctx, int n_pairs, const int* offsets, const double* d_f1, const double* d_f2,
+									const ebo_two_view_params* params, ebo_two_view_result* result, int* inlier_idx,
+									int* hyp_counts_or_null, double* hyp_models_or_null, int* hyp_samples_or_null);
+int ebo_relative_pose_scores(ebo_ctx* ctx, const double* model, int n, const double* f1, const double* f2, double threshold,
+							 double* scores_or_null, uint8_t* inlier_flags_or_null);
+int ebo_relative_pose_scores_device(ebo_ctx* ctx, const double* model, int n, const double* d_f1, const double* d_f2,
+									double threshold, double* d_scores_or_null, uint8_t* d_inlier_flags_or_null);
+int ebo_triangulate(ebo_ctx* ctx, int n_poses, const double* poses, int n, const int* pose_pair, const double* f1,
+					const double* f2, double* points_out);
+int ebo_triangulate_device(ebo_ctx* ctx, int n_poses, const double* d_poses, int n, const int* d_pose_pair, const double* d_f1,
+						   const double* d_f2, double* d_points_out);
+int ebo_epipolar_inliers(ebo_ctx* ctx, const double* model, int n, const double* f1, const double* f2, double threshold,
+						 uint8_t* flags);
+
 /* Device-side timing of everything enqueued between begin and end on the
  * context's stream (hipEvent based). */
 int ebo_timer_begin(ebo_ctx* ctx);
