@@ -72,9 +72,6 @@ bool mid_timestamp(int64_t a, int64_t b, int64_t& out)
 }
 
 extern const size_t kLdsBudget = 160 * 1024;
-// host memory that kernels read and write directly: mapped into the device's address space and
-// coherent (fine-grained), whatever HIP_HOST_COHERENT says
-extern const unsigned int kZeroCopyFlags = hipHostMallocMapped | hipHostMallocCoherent;
 const size_t kRedBytes = 16 * 8 * sizeof(double);
 
 size_t lds_for(int channels, int tiles, int rw, int rh)
@@ -93,66 +90,6 @@ int min_tiles(int channels, int rw, int rh, size_t budget)
 		}
 	}
 	return -1;
-}
-
-int ensure_partials(ebo_ctx* c, size_t n)
-{
-	if (n <= c->partials_cap)
-	{
-		return EBO_OK;
-	}
-	if (c->d_partials)
-	{
-		hipFree(c->d_partials);
-		c->d_partials = nullptr;
-		c->partials_cap = 0;
-	}
-	int rc = c->hip(hipMalloc(&c->d_partials, n * sizeof(double)), "hipMalloc partials");
-	if (rc == EBO_OK)
-	{
-		c->partials_cap = n;
-	}
-	return rc;
-}
-
-int ensure_aux(ebo_ctx* c, size_t bytes)
-{
-	if (bytes <= c->aux_cap)
-	{
-		return EBO_OK;
-	}
-	if (c->d_aux)
-	{
-		hipFree(c->d_aux);
-		c->d_aux = nullptr;
-		c->aux_cap = 0;
-	}
-	int rc = c->hip(hipMalloc(&c->d_aux, bytes), "hipMalloc aux");
-	if (rc == EBO_OK)
-	{
-		c->aux_cap = bytes;
-	}
-	return rc;
-}
-
-int ensure_scratch(ebo_ctx* c, size_t bytes)
-{
-	if (bytes <= c->scratch_cap)
-	{
-		return EBO_OK;
-	}
-	if (c->d_scratch)
-	{
-		hipFree(c->d_scratch);
-		c->d_scratch = nullptr;
-		c->scratch_cap = 0;
-	}
-	int rc = c->hip(hipMalloc(&c->d_scratch, bytes), "hipMalloc scratch");
-	if (rc == EBO_OK)
-	{
-		c->scratch_cap = bytes;
-	}
-	return rc;
 }
 
 // LDS of one k_eval3 / k_solve_independent workgroup.  The image is the bounding box of
@@ -244,11 +181,6 @@ int edge_launch_setup(ebo_ctx* c, EdgeLaunch& L)
 	// Workgroup slots.  The batched evaluation runs PERSISTENT workgroups -- as many as the chip holds at once (two
 	// 256-lane ones per CU, else one), each walking the launch's units -- and keys its per-evaluation temporaries (the
 	// global fallback slice, the direction table) by workgroup; the device-resident solve runs one workgroup per unit.
-	if (c->n_cus == 0)
-	{
-		hipDeviceProp_t prop;
-		c->n_cus = (hipGetDeviceProperties(&prop, c->prm.device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-	}
 	{
 		const size_t items = static_cast<size_t>(L.n_units) * L.flow_sets;
 		// (the 256-lane instantiations of k_eval_edge only: the 768-lane ones keep one workgroup per item, ebo_edge.inc)
@@ -296,22 +228,11 @@ int edge_launch_setup(ebo_ctx* c, EdgeLaunch& L)
 			if (cap >= 1024 && bytes <= budget && want)
 			{
 				const size_t listInts = (items + 3) & ~static_cast<size_t>(3);
-				if (c->edge_defer_cap < items)
+				// (one block, in ints: length + padding | list | bbox)
+				int rc = c->grow(c->d_edge_defer, 4 + listInts + items * 4, "hipMalloc edge deferred list");
+				if (rc)
 				{
-					if (c->d_edge_defer)
-					{
-						c->hip(hipStreamSynchronize(c->stream), "sync");
-						hipFree(c->d_edge_defer);
-						c->d_edge_defer = nullptr;
-						c->edge_defer_cap = 0;
-					}
-					int rc = c->hip(hipMalloc(reinterpret_cast<void**>(&c->d_edge_defer), (4 + listInts) * sizeof(int) + items * 4 * sizeof(int)),
-									"hipMalloc edge deferred list");
-					if (rc)
-					{
-						return rc;
-					}
-					c->edge_defer_cap = items;
+					return rc;
 				}
 				L.compact.hdr_doubles = static_cast<int>(168 + listCap / 2);
 				L.compact.list_cap = static_cast<int>(listCap);
@@ -337,24 +258,14 @@ int edge_launch_setup(ebo_ctx* c, EdgeLaunch& L)
 		{
 			return c->fail(EBO_ERR_UNSUPPORTED, "edge loss fallback scratch would exceed 16 GiB; use fewer windows per batch");
 		}
-		if (need > c->edge_scratch_cap)
+		int rc = c->grow(c->d_edge_scratch, need, "hipMalloc edge scratch");
+		if (rc)
 		{
-			if (c->d_edge_scratch)
-			{
-				hipFree(c->d_edge_scratch);
-				c->d_edge_scratch = nullptr;
-				c->edge_scratch_cap = 0;
-			}
-			int rc = c->hip(hipMalloc(&c->d_edge_scratch, need), "hipMalloc edge scratch");
-			if (rc)
-			{
-				return rc;
-			}
-			c->edge_scratch_cap = need;
+			return rc;
 		}
-		L.d_scratch = static_cast<char*>(c->d_edge_scratch);
+		L.d_scratch = static_cast<char*>(c->d_edge_scratch.get());
 	}
-	int rc = ensure_partials(c, static_cast<size_t>(5) * L.n_units * 3);
+	int rc = c->grow(c->d_partials, static_cast<size_t>(5) * L.n_units * 3, "hipMalloc partials");
 	if (rc)
 	{
 		return rc;
@@ -367,6 +278,10 @@ int edge_launch_setup(ebo_ctx* c, EdgeLaunch& L)
 	const double normCoef = 1.0 / ((2 * M_PI) * sigmaSq);
 	if (!c->d_edge_w || c->edge_w_sigma != sig)
 	{
+		if (c->capturing)  // (the upload below is synchronous)
+		{
+			return c->fail(EBO_ERR_STATE, "the edge loss's tensor weights are not built for this sigma_st yet: run the same call once before recording");
+		}
 		double w[49];
 		for (int i = -3; i <= 3; ++i)
 		{
@@ -376,13 +291,10 @@ int edge_launch_setup(ebo_ctx* c, EdgeLaunch& L)
 				w[(i + 3) * 7 + (j + 3)] = normCoef * std::exp(-0.5 / sigmaSq * (x * x + y * y));
 			}
 		}
-		if (!c->d_edge_w)
+		rc = c->grow(c->d_edge_w, 49, "hipMalloc edge weights");
+		if (rc)
 		{
-			rc = c->hip(hipMalloc(reinterpret_cast<void**>(&c->d_edge_w), sizeof(w)), "hipMalloc edge weights");
-			if (rc)
-			{
-				return rc;
-			}
+			return rc;
 		}
 		// synchronous: the table must not change under a launch still in flight
 		rc = c->hip(hipStreamSynchronize(c->stream), "sync");
@@ -410,7 +322,7 @@ int edge_launch_setup(ebo_ctx* c, EdgeLaunch& L)
 		// (sized by the context's units, not by this launch's window list: the rounds of a lock-step solve must not
 		// flip between two sizes -- a reallocation synchronises the device)
 		const size_t need = std::max(static_cast<size_t>(L.wg_slots) * L.ec.cs_stride,
-									 L.compact_table_px > 0 ? static_cast<size_t>(L.n_units) * L.compact_table_px : 0) * 2 * sizeof(double);
+									 L.compact_table_px > 0 ? static_cast<size_t>(L.n_units) * L.compact_table_px : 0) * 2;  // doubles
 		// The table is an optimisation nobody asked for by name, so it must not surprise: at most
 		// EBO_EDGE_CS_MB (default 4096) AND at most a quarter of the memory that is free right now
 		// (several contexts share a GPU: one per FeatureDetector / Optimizer / TrackedPatches of the
@@ -418,30 +330,33 @@ int edge_launch_setup(ebo_ctx* c, EdgeLaunch& L)
 		// re-derives what the table would have held); and a context that kept a large table for one
 		// big batch gives it back when the batches that follow need less than a quarter of it.
 		const size_t limit = env_size("EBO_EDGE_CS_MB", 4096) << 20;
-		if (L.want_jac && L.flow_sets == 1 && need <= limit && need > 0)
+		if (L.want_jac && L.flow_sets == 1 && need * sizeof(double) <= limit && need > 0)
 		{
 			// (the free-memory probe and the allocation happen only when the table has to change size -- once per
-			// batch shape, never per launch: hipFree synchronises the whole device)
-			if (need > c->edge_cs_cap || need < c->edge_cs_cap / 4)
+			// batch shape, never per launch: hipFree synchronises the whole device).  A recording keeps the table it has:
+			// one that is large enough is used as it is, one that is too small is refused like any other growth.
+			const size_t have = c->d_edge_cs.cap();
+			if (need > have && c->capturing)
+			{
+				return c->grown(Grow::kRefused, "hipMalloc edge directions");
+			}
+			if (need > have || (4 * need < have && !c->capturing))
 			{
 				size_t freeB = 0, totalB = 0;
 				const bool probed = hipMemGetInfo(&freeB, &totalB) == hipSuccess;
 				if (c->d_edge_cs)
 				{
-					c->hip(hipStreamSynchronize(c->stream), "sync");
-					hipFree(c->d_edge_cs);
-					c->d_edge_cs = nullptr;
-					freeB += c->edge_cs_cap;
-					c->edge_cs_cap = 0;
+					rc = c->hip(hipStreamSynchronize(c->stream), "sync");
+					if (rc)
+					{
+						return rc;
+					}
+					c->d_edge_cs.reset();
+					freeB += have * sizeof(double);
 				}
-				if ((!probed || need <= freeB / 4) && hipMalloc(reinterpret_cast<void**>(&c->d_edge_cs), need) == hipSuccess)
-				{
-					c->edge_cs_cap = need;
-				}
-				else
+				if ((probed && need * sizeof(double) > freeB / 4) || c->d_edge_cs.ensure(need) != Grow::kOk)
 				{
 					(void)hipGetLastError();  // not an error: evaluate without the table
-					c->d_edge_cs = nullptr;
 				}
 			}
 			L.ec.cs = c->d_edge_cs;
@@ -550,7 +465,7 @@ int run_eval_device(ebo_ctx* c, const double* d_flows, int want_jac, double* d_o
 		}
 	}
 	L.tiles = std::max(1, std::min(t, 64));
-	rc = ensure_partials(c, static_cast<size_t>(L.flow_sets) * L.n_units * L.tiles * kPartialStride);
+	rc = c->grow(c->d_partials, static_cast<size_t>(L.flow_sets) * L.n_units * L.tiles * kPartialStride, "hipMalloc partials");
 	if (rc)
 	{
 		return rc;
@@ -570,53 +485,18 @@ int run_eval_device(ebo_ctx* c, const double* d_flows, int want_jac, double* d_o
 // Jacobians nobody asked for.
 // pinned staging of evaluation rounds: flows [nf][2], results [nf][3], and mode tables [4][nf]
 // (the pipelined lock-step solve has up to four rounds in flight)
-int ensure_eval_staging(ebo_ctx* c, size_t nf)
+int grow_eval_staging(ebo_ctx* c, size_t nf)
 {
-	int rc = EBO_OK;
-	if (nf > c->pin_cap)
+	if (nf <= c->pin_flows.cap() / 2)
 	{
-		(void)hipSetDevice(c->prm.device);  // the staging is mapped for the context's device
-		if (c->pin_flows)
-		{
-			(void)hipHostFree(c->pin_flows);
-			(void)hipHostFree(c->pin_out);
-			(void)hipHostFree(c->pin_modes);
-			c->pin_flows = c->pin_out = nullptr;
-			c->pin_modes = nullptr;
-			c->pin_cap = 0;
-		}
-		hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&c->pin_flows), nf * 2 * sizeof(double), kZeroCopyFlags);
-		if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&c->pin_out), nf * 3 * sizeof(double), kZeroCopyFlags);
-		if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&c->pin_modes), 4 * nf, kZeroCopyFlags);  // one table per round in flight (up to 4)
-		rc = c->hip(e, "hipHostMalloc evaluation staging");
-		if (rc)
-		{
-			return rc;
-		}
-		std::memset(c->pin_out, 0, nf * 3 * sizeof(double));
-		c->pin_cap = nf;
+		return EBO_OK;
 	}
+	(void)hipSetDevice(c->prm.device);  // the staging is mapped for the context's device
+	int rc = (c->capturing || !c->pin_flows) ? EBO_OK : c->hip(hipStreamSynchronize(c->stream), "sync");
+	// (one mode table per round in flight, up to 4)
+	if (rc == EBO_OK) rc = c->grown(ensure3(c->pin_flows, nf * 2, c->pin_out, nf * 3, c->pin_modes, nf * 4, !c->capturing), "hipHostMalloc evaluation staging");
+	if (rc == EBO_OK) std::memset(c->pin_out, 0, nf * 3 * sizeof(double));
 	return rc;
-}
-
-int ensure_device_modes(ebo_ctx* c, size_t nf)
-{
-	if (nf > c->modes_cap)
-	{
-		if (c->d_modes)
-		{
-			hipFree(c->d_modes);
-			c->d_modes = nullptr;
-			c->modes_cap = 0;
-		}
-		int rc = c->hip(hipMalloc(reinterpret_cast<void**>(&c->d_modes), nf), "hipMalloc modes");
-		if (rc)
-		{
-			return rc;
-		}
-		c->modes_cap = nf;
-	}
-	return EBO_OK;
 }
 
 // One half of a pipelined lock-step round: slots [s0, s1) of the flows go up, the launch covers
@@ -740,7 +620,7 @@ int eval_finish(ebo_ctx* c, const unsigned char* modes, size_t s0, size_t s1, bo
 int eval_host(ebo_ctx* c, const double* flows, double* r, double* jac, const unsigned char* modes = nullptr, int windowSlots = 0)
 {
 	const size_t nf = c->n_flows();
-	int rc = ensure_eval_staging(c, nf);
+	int rc = grow_eval_staging(c, nf);
 	if (rc)
 	{
 		return rc;
@@ -809,7 +689,7 @@ int eval_host(ebo_ctx* c, const double* flows, double* r, double* jac, const uns
 		c->modes_active = c->pin_modes;
 		if (!zeroCopy)
 		{
-			rc = ensure_device_modes(c, nf);
+			rc = c->grow(c->d_modes, nf, "hipMalloc modes");
 			if (rc)
 			{
 				return rc;
@@ -879,8 +759,8 @@ struct CtxLockstepBackend
 	int groups() const { return static_cast<int>(ab_size("EBO_SOLVE_GROUPS", 2)); }
 	int pipeline_begin(size_t slots, int G)
 	{
-		int rc = ensure_eval_staging(c, slots);
-		if (rc == EBO_OK) rc = ensure_device_modes(c, slots);
+		int rc = grow_eval_staging(c, slots);
+		if (rc == EBO_OK) rc = c->grow(c->d_modes, slots, "hipMalloc modes");
 		if (rc)
 		{
 			return rc;
@@ -1008,28 +888,6 @@ int run_solve_device(ebo_ctx* c, const ebo_solver_opts* o, double* d_flows_out, 
 	return EBO_OK;
 }
 
-// Grows a device buffer to `bytes`; while recording a graph it may not (a recorded call cannot allocate).
-static int grow_count_buffer(ebo_ctx* c, void** buf, size_t& cap, size_t bytes, const char* what)
-{
-	if (bytes <= cap)
-	{
-		return EBO_OK;
-	}
-	if (c->capturing)
-	{
-		return c->fail(EBO_ERR_STATE, "this count image needs a larger buffer than the context holds: count once before recording");
-	}
-	hipFree(*buf);
-	*buf = nullptr;
-	cap = 0;
-	int rc = c->hip(hipMalloc(buf, bytes), what);
-	if (rc == EBO_OK)
-	{
-		cap = bytes;
-	}
-	return rc;
-}
-
 int count_device(ebo_ctx* c, int mode, const void* d_aux, double* d_image)
 {
 	if (c->custom_n)
@@ -1087,13 +945,8 @@ int count_device(ebo_ctx* c, int mode, const void* d_aux, double* d_image)
 	if (L.plan.kind == kCountSorted)
 	{
 		// the destination list in two halves of list_events entries (4 B each); bins: counts, starts, cursors
-		int rc = grow_count_buffer(c, reinterpret_cast<void**>(&c->d_count_sorted), c->count_sorted_cap,
-								   2 * L.plan.list_events * sizeof(unsigned int), "hipMalloc count sorted list");
-		if (rc == EBO_OK)
-		{
-			rc = grow_count_buffer(c, reinterpret_cast<void**>(&c->d_count_bins), c->count_bins_cap,
-								   (3 * static_cast<size_t>(L.plan.bins) + 2) * sizeof(unsigned int), "hipMalloc count bins");
-		}
+		int rc = c->grow(c->d_count_sorted, 2 * L.plan.list_events, "hipMalloc count sorted list");
+		if (rc == EBO_OK) rc = c->grow(c->d_count_bins, 3 * static_cast<size_t>(L.plan.bins) + 2, "hipMalloc count bins");
 		if (rc)
 		{
 			return rc;
@@ -1469,6 +1322,7 @@ int ebo_create(const ebo_params* p, ebo_ctx** out)
 		return EBO_ERR_ARG;
 	}
 	c->prm = *p;
+	c->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
 	c->npx = p->image_w / p->patch_w;  // feature_detector.cpp:301-304
 	c->npy = p->image_h / p->patch_h;
 	c->P = c->npx * c->npy;
@@ -1492,22 +1346,25 @@ int ebo_create(const ebo_params* p, ebo_ctx** out)
 	const size_t npix = static_cast<size_t>(c->cap_windows) * p->image_w * p->image_h;
 	hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
 	c->own_stream = (e == hipSuccess);
-	if (e == hipSuccess) e = hipMalloc(&c->d_events, c->cap_events * sizeof(uint64_t));
-	if (e == hipSuccess) e = hipMalloc(&c->d_units, static_cast<size_t>(c->cap_windows) * (c->P + 1) * sizeof(Unit));
-	if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_unit_maxdt), static_cast<size_t>(c->cap_windows) * (c->P + 1) * sizeof(int32_t));
-	if (e == hipSuccess) e = hipMalloc(&c->d_flows, nf * 2 * sizeof(double));
-	if (e == hipSuccess) e = hipMalloc(&c->d_out, nf * 3 * sizeof(double));
-	if (e == hipSuccess) e = hipMalloc(&c->d_stats, nf * 4 * sizeof(int32_t));
-	if (e == hipSuccess) e = hipMalloc(&c->d_counts, npix * sizeof(int32_t));
-	if (e == hipSuccess) e = hipMalloc(&c->d_image, npix * sizeof(double));
-	if (e == hipSuccess) e = hipMemset(c->d_counts, 0, npix * sizeof(int32_t));
-	if (e == hipSuccess) e = hipEventCreate(&c->ev0);
-	if (e == hipSuccess) e = hipEventCreate(&c->ev1);
-	if (e != hipSuccess)
+	const size_t nu = static_cast<size_t>(c->cap_windows) * (c->P + 1);
+	const char* const what = "device allocation failed";
+	int rc = c->hip(e, what);
+	if (rc == EBO_OK) rc = c->grow(c->d_events, c->cap_events, what);
+	if (rc == EBO_OK) rc = c->grow(c->d_units, nu, what);
+	if (rc == EBO_OK) rc = c->grow(c->d_unit_maxdt, nu, what);
+	if (rc == EBO_OK) rc = c->grow(c->d_flows, nf * 2, what);
+	if (rc == EBO_OK) rc = c->grow(c->d_out, nf * 3, what);
+	if (rc == EBO_OK) rc = c->grow(c->d_stats, nf * 4, what);
+	if (rc == EBO_OK) rc = c->grow(c->d_counts, npix, what);
+	if (rc == EBO_OK) rc = c->grow(c->d_image, npix, what);
+	if (rc == EBO_OK) rc = c->hip(hipMemset(c->d_counts, 0, npix * sizeof(int32_t)), what);
+	if (rc == EBO_OK) rc = c->hip(hipEventCreate(&c->ev0), what);
+	if (rc == EBO_OK) rc = c->hip(hipEventCreate(&c->ev1), what);
+	if (rc)
 	{
-		g_create_error = std::string("device allocation failed: ") + hipGetErrorString(e);
+		g_create_error = c->err;
 		ebo_destroy(c);
-		return EBO_ERR_HIP;
+		return rc;
 	}
 	*out = c;
 	return EBO_OK;
@@ -1551,56 +1408,6 @@ void ebo_destroy(ebo_ctx* c)
 		(void)hipStreamSynchronize(c->stream);
 	}
 	(void)ebo_comm_destroy(c);
-	hipFree(c->d_events);
-	hipFree(c->d_shard_tbl);
-	hipFree(c->d_units);
-	hipFree(c->d_unit_maxdt);
-	hipFree(c->d_flows);
-	hipFree(c->d_out);
-	if (c->pin_flows)
-	{
-		(void)hipHostFree(c->pin_flows);
-		(void)hipHostFree(c->pin_out);
-		(void)hipHostFree(c->pin_modes);
-	}
-	if (c->pin_bucket)
-	{
-		(void)hipHostFree(c->pin_bucket);
-	}
-	if (c->pin_route)
-	{
-		(void)hipHostFree(c->pin_route);
-	}
-	hipFree(c->d_route_xy);
-	hipFree(c->d_partials);
-	hipFree(c->d_counts);
-	hipFree(c->d_count_sorted);
-	hipFree(c->d_count_bins);
-	hipFree(c->d_opt_grid);
-	hipFree(c->d_modes);
-	hipFree(c->d_opt);
-	hipFree(c->d_image);
-	hipFree(c->d_aux);
-	hipFree(c->d_stats);
-	hipFree(c->d_scratch);
-	hipFree(c->d_edge_scratch);
-	hipFree(c->d_edge_w);
-	hipFree(c->d_edge_cs);
-	hipFree(c->d_edge_defer);
-	hipFree(c->d_raw);
-	hipFree(c->d_bucket);
-	hipFree(c->d_chunk_hist);
-	hipFree(c->d_field);
-	hipFree(c->d_tvf);
-	hipFree(c->d_fe_lut);
-	hipFree(c->d_rect_lut);
-	hipFree(c->d_rect_map);
-	hipFree(c->d_rect_bad);
-	hipFree(c->d_fe);
-	hipFree(c->d_fe_pyr[0]);
-	hipFree(c->d_fe_pyr[1]);
-	hipFree(c->d_fe_lv);
-	hipFree(c->d_fe_pts);
 	if (c->ev0) hipEventDestroy(c->ev0);
 	if (c->ev1) hipEventDestroy(c->ev1);
 	for (hipEvent_t e : c->tv_ev)
@@ -1611,7 +1418,7 @@ void ebo_destroy(ebo_ctx* c)
 	{
 		hipStreamDestroy(c->stream);
 	}
-	delete c;
+	delete c;  // the device and pinned buffers go with it (dev_buf.h)
 }
 
 int ebo_set_stream(ebo_ctx* c, void* hip_stream)
@@ -1723,12 +1530,12 @@ int ebo_contrast_image(ebo_ctx* c, int window, int patch, const double* flow, in
 	const size_t ui = c->unit_index(window, patch);
 	const Unit& u = c->units[ui];
 	const size_t npx = static_cast<size_t>(9) * u.rw * u.rh;
-	int rc = ensure_aux(c, npx * channels * sizeof(double) + 2 * sizeof(double));
+	int rc = c->grow(c->d_aux, npx * channels * sizeof(double) + 2 * sizeof(double), "hipMalloc aux");
 	if (rc)
 	{
 		return rc;
 	}
-	double* d_img = static_cast<double*>(c->d_aux);
+	double* d_img = static_cast<double*>(c->d_aux.get());
 	double* d_flow = d_img + npx * channels;
 	rc = c->hip(hipMemcpyAsync(d_flow, flow, 2 * sizeof(double), hipMemcpyHostToDevice, c->stream), "H2D flow");
 	if (rc)
@@ -1856,7 +1663,7 @@ int ebo_count_image(ebo_ctx* c, int mode, const void* aux, double* image)
 	else if (mode == EBO_COUNT_FIELD)
 	{
 		const size_t bytes = npix * 2 * sizeof(float);
-		rc = ensure_aux(c, bytes);
+		rc = c->grow(c->d_aux, bytes, "hipMalloc aux");
 		if (rc == EBO_OK)
 		{
 			rc = c->hip(hipMemcpyAsync(c->d_aux, aux, bytes, hipMemcpyHostToDevice, c->stream), "H2D field");
@@ -1916,7 +1723,7 @@ int ebo_edge_work_stats(ebo_ctx* c, const double* d_flows, int want_jac, uint64_
 		return c->fail(EBO_ERR_STATE, "needs the edge loss and a loaded window");
 	}
 	(void)hipSetDevice(c->prm.device);
-	int rc = ensure_aux(c, 6 * sizeof(unsigned long long));
+	int rc = c->grow(c->d_aux, 6 * sizeof(unsigned long long), "hipMalloc aux");
 	if (rc)
 	{
 		return rc;
@@ -1926,7 +1733,7 @@ int ebo_edge_work_stats(ebo_ctx* c, const double* d_flows, int want_jac, uint64_
 	{
 		return rc;
 	}
-	c->edge_stats_dev = static_cast<unsigned long long*>(c->d_aux);
+	c->edge_stats_dev = static_cast<unsigned long long*>(c->d_aux.get());
 	rc = run_eval_device(c, d_flows, want_jac, c->d_out);
 	c->edge_stats_dev = nullptr;
 	if (rc)
@@ -1968,14 +1775,14 @@ int ebo_lds_rates(ebo_ctx* c, double* gops)
 		cus = prop.multiProcessorCount;
 	}
 	const int blocks = 4 * cus, iters = 49 * 42;  // 42 footprints per lane
-	int rc = ensure_aux(c, static_cast<size_t>(blocks) * sizeof(double));
+	int rc = c->grow(c->d_aux, static_cast<size_t>(blocks) * sizeof(double), "hipMalloc aux");
 	if (rc)
 	{
 		return rc;
 	}
 	for (int kind = 0; kind < 2 && rc == EBO_OK; ++kind)
 	{
-		if (launch_lds_rate(kind == 0, blocks, 49, static_cast<double*>(c->d_aux), c->stream))  // warm-up
+		if (launch_lds_rate(kind == 0, blocks, 49, static_cast<double*>(c->d_aux.get()), c->stream))  // warm-up
 		{
 			return c->fail(EBO_ERR_HIP, "k_lds_rate launch failed");
 		}
@@ -1983,7 +1790,7 @@ int ebo_lds_rates(ebo_ctx* c, double* gops)
 		for (int rep = 0; rep < 3 && rc == EBO_OK; ++rep)
 		{
 			rc = c->hip(hipEventRecord(c->ev0, c->stream), "hipEventRecord");
-			if (rc == EBO_OK && launch_lds_rate(kind == 0, blocks, iters, static_cast<double*>(c->d_aux), c->stream))
+			if (rc == EBO_OK && launch_lds_rate(kind == 0, blocks, iters, static_cast<double*>(c->d_aux.get()), c->stream))
 			{
 				return c->fail(EBO_ERR_HIP, "k_lds_rate launch failed");
 			}

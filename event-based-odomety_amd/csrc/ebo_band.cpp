@@ -59,20 +59,13 @@ int shard_table(ebo_ctx* c, int n_windows, const int64_t* window_t_ref_us, const
 			uniform = uniform && b.flow >= 0;
 		}
 		(void)hipSetDevice(c->prm.device);
-		if (n * sizeof(BandUnit) > c->shard_tbl_cap)
+		int rc = c->grow(c->d_shard_tbl, n * sizeof(BandUnit), "hipMalloc shard table");
+		if (rc)
 		{
-			hipFree(c->d_shard_tbl);
-			c->d_shard_tbl = nullptr;
-			c->shard_tbl_cap = 0;
-			const int rc = c->hip(hipMalloc(&c->d_shard_tbl, n * sizeof(BandUnit)), "hipMalloc shard table");
-			if (rc)
-			{
-				return rc;
-			}
-			c->shard_tbl_cap = n * sizeof(BandUnit);
+			return rc;
 		}
 		c->shard_tbl_gen = 0;
-		int rc = c->hip(hipMemcpyAsync(c->d_shard_tbl, tbl.data(), n * sizeof(BandUnit), hipMemcpyHostToDevice, c->stream),
+		rc = c->hip(hipMemcpyAsync(c->d_shard_tbl, tbl.data(), n * sizeof(BandUnit), hipMemcpyHostToDevice, c->stream),
 						"H2D shard table");
 		if (rc == EBO_OK)
 		{
@@ -86,7 +79,7 @@ int shard_table(ebo_ctx* c, int n_windows, const int64_t* window_t_ref_us, const
 		c->shard_tbl_tref.assign(window_t_ref_us, window_t_ref_us + n_windows);
 		c->shard_tbl_kind = uniform ? 2 : 1;
 	}
-	*out = static_cast<const BandUnit*>(c->d_shard_tbl);
+	*out = static_cast<const BandUnit*>(c->d_shard_tbl.get());
 	if (uniformFlows)
 	{
 		*uniformFlows = c->shard_tbl_kind == 2;

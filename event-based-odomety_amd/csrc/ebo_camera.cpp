@@ -71,13 +71,13 @@ int ebo_camera_unproject(ebo_ctx* c, const ebo_camera* cam, int n, const double*
 	}
 	(void)hipSetDevice(c->prm.device);
 	const size_t bIn = align256(static_cast<size_t>(n) * 2 * sizeof(double)), bOut = static_cast<size_t>(n) * 3 * sizeof(double);
-	int rc = ensure_scratch(c, bIn + bOut);
+	int rc = c->grow(c->d_scratch, bIn + bOut, "hipMalloc scratch");
 	if (rc)
 	{
 		return rc;
 	}
-	double* d_uv = reinterpret_cast<double*>(static_cast<char*>(c->d_scratch));
-	double* d_out = reinterpret_cast<double*>(static_cast<char*>(c->d_scratch) + bIn);
+	double* d_uv = reinterpret_cast<double*>(static_cast<char*>(c->d_scratch.get()));
+	double* d_out = reinterpret_cast<double*>(static_cast<char*>(c->d_scratch.get()) + bIn);
 	rc = c->hip(hipMemcpyAsync(d_uv, uv, static_cast<size_t>(n) * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream),
 				"H2D points");
 	if (rc)
@@ -119,28 +119,12 @@ int ebo_set_rectification(ebo_ctx* c, const ebo_camera* cam)
 	}
 	(void)hipSetDevice(c->prm.device);
 	const size_t npx = static_cast<size_t>(c->prm.image_w) * c->prm.image_h;
-	int rc = EBO_OK;
-	if (!c->d_rect_lut)
+	int rc = c->grow(c->d_rect_lut, npx * 2 * sizeof(int16_t), "hipMalloc rectification table");
+	if (rc == EBO_OK) rc = c->grow(c->d_rect_map, npx * 2, "hipMalloc rectification map");
+	if (rc == EBO_OK) rc = c->grow(c->d_rect_bad, 256 / sizeof(int), "hipMalloc rectification flag");
+	if (rc)
 	{
-		rc = c->hip(hipMalloc(&c->d_rect_lut, npx * 2 * sizeof(int16_t)), "hipMalloc rectification table");
-		if (rc == EBO_OK)
-		{
-			rc = c->hip(hipMalloc(reinterpret_cast<void**>(&c->d_rect_map), npx * 2 * sizeof(double)), "hipMalloc rectification map");
-		}
-		if (rc == EBO_OK)
-		{
-			rc = c->hip(hipMalloc(reinterpret_cast<void**>(&c->d_rect_bad), 256), "hipMalloc rectification flag");
-		}
-		if (rc)
-		{
-			hipFree(c->d_rect_lut);
-			hipFree(c->d_rect_map);
-			hipFree(c->d_rect_bad);
-			c->d_rect_lut = nullptr;
-			c->d_rect_map = nullptr;
-			c->d_rect_bad = nullptr;
-			return rc;
-		}
+		return rc;
 	}
 	if (launch_rectify_map(consts_of(cam), c->prm.image_w, c->prm.image_h, c->d_rect_map, c->d_rect_lut, c->d_rect_bad, c->stream))
 	{

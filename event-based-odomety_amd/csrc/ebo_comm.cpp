@@ -133,24 +133,17 @@ int ebo_comm_init(ebo_ctx* c, const ebo_comm_id* id, int rank, int nranks)
 	// the exchange's own small buffers, so that no collective path has to allocate before its first collective
 	// (a new communicator starts with an empty exchange buffer: its growth is a function of what THIS communicator's
 	// ranks have gathered, so that every rank holds the same capacity)
-	hipFree(c->d_comm_buf);
-	c->d_comm_buf = nullptr;
-	c->comm_buf_cap = 0;
-	hipFree(c->d_comm_cnt);
-	c->d_comm_cnt = nullptr;
-	if (c->pin_comm)
-	{
-		hipHostFree(c->pin_comm);
-		c->pin_comm = nullptr;
-	}
+	c->d_comm_buf.reset();
+	c->d_comm_cnt.reset();
+	c->pin_comm.reset();
 	const size_t words = static_cast<size_t>(nranks) + 2;
-	hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->d_comm_cnt), words * sizeof(uint64_t));
-	if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&c->pin_comm), words * sizeof(uint64_t), hipHostMallocDefault);
-	if (e != hipSuccess)
+	int rcb = c->grow(c->d_comm_cnt, words, "communicator staging");
+	if (rcb == EBO_OK) rcb = c->grow(c->pin_comm, words, "communicator staging");
+	if (rcb)
 	{
 		api->CommDestroy(c->comm);
 		c->comm = nullptr;
-		return c->hip(e, "communicator staging");
+		return rcb;
 	}
 	return EBO_OK;
 }
@@ -281,19 +274,18 @@ int gather_track_counts(ebo_ctx* c, RcclApi* api, size_t n_local, std::vector<ui
 // (one int, ncclAllReduce min) and either all have the larger buffer or all report the failure.
 int ensure_comm_buf(ebo_ctx* c, RcclApi* api, size_t bytes)
 {
-	if (bytes <= c->comm_buf_cap)
+	if (bytes <= c->d_comm_buf.cap())
 	{
 		return EBO_OK;
 	}
-	void* fresh = nullptr;
-	const hipError_t ea = hipMalloc(&fresh, bytes);
-	if (ea != hipSuccess)
+	// (the one buffer that is allocated BEFORE the old one goes: the ranks have to agree first)
+	Dev<void> fresh;
+	if (fresh.ensure(bytes) != Grow::kOk)
 	{
 		(void)hipGetLastError();
-		fresh = nullptr;
 	}
-	int32_t* d_ok = reinterpret_cast<int32_t*>(c->d_comm_cnt);
-	reinterpret_cast<int32_t*>(c->pin_comm)[0] = fresh ? 1 : 0;
+	int32_t* d_ok = reinterpret_cast<int32_t*>(c->d_comm_cnt.get());
+	reinterpret_cast<int32_t*>(c->pin_comm.get())[0] = fresh ? 1 : 0;
 	hipError_t e = hipMemsetAsync(d_ok, 0, sizeof(int32_t), c->stream);  // a failed copy leaves "not ok"
 	if (e == hipSuccess) e = hipMemcpyAsync(d_ok, c->pin_comm, sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
 	const int nrc = api->AllReduce(d_ok, d_ok, 1, 2 /* ncclInt32 */, 3 /* ncclMin */, c->comm, c->stream);
@@ -303,19 +295,13 @@ int ensure_comm_buf(ebo_ctx* c, RcclApi* api, size_t bytes)
 		e2 = hipMemcpyAsync(c->pin_comm, d_ok, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
 		if (e2 == hipSuccess) e2 = hipStreamSynchronize(c->stream);
 	}
-	const bool allOk = nrc == 0 && e == hipSuccess && e2 == hipSuccess && reinterpret_cast<int32_t*>(c->pin_comm)[0] == 1;
+	const bool allOk = nrc == 0 && e == hipSuccess && e2 == hipSuccess && reinterpret_cast<int32_t*>(c->pin_comm.get())[0] == 1;
 	if (!allOk)
 	{
-		if (fresh)
-		{
-			hipFree(fresh);
-		}
 		return nrc != 0 ? c->fail(EBO_ERR_COMM, "ncclAllReduce(buffer growth)")
 						: c->fail(EBO_ERR_HIP, "a rank is out of device memory for the track exchange");
 	}
-	hipFree(c->d_comm_buf);
-	c->d_comm_buf = fresh;
-	c->comm_buf_cap = bytes;
+	c->d_comm_buf.swap(fresh);  // the old buffer goes with `fresh`
 	return EBO_OK;
 }
 }  // namespace
@@ -415,7 +401,7 @@ int ebo_allgather_tracks(ebo_ctx* c, const ebo_track_point* local, size_t n_loca
 	{
 		return rc;
 	}
-	char* d_send = static_cast<char*>(c->d_comm_buf);
+	char* d_send = static_cast<char*>(c->d_comm_buf.get());
 	char* d_recv = d_send + slot;
 	hipError_t e = hipMemsetAsync(d_send, 0, slot, c->stream);
 	if (e == hipSuccess && n_local)
@@ -598,16 +584,9 @@ int ebo_comm_destroy(ebo_ctx* c)
 	{
 		(void)hipSetDevice(c->prm.device);
 		(void)hipStreamSynchronize(c->stream);
-		hipFree(c->d_comm_cnt);
-		c->d_comm_cnt = nullptr;
-		hipFree(c->d_comm_buf);
-		c->d_comm_buf = nullptr;
-		c->comm_buf_cap = 0;
-		if (c->pin_comm)
-		{
-			hipHostFree(c->pin_comm);
-			c->pin_comm = nullptr;
-		}
+		c->d_comm_cnt.reset();
+		c->d_comm_buf.reset();
+		c->pin_comm.reset();
 	}
 	c->comm_rank = 0;
 	c->comm_size = 1;

@@ -22,6 +22,7 @@
 #include <thread>
 
 #include "../../include/ebo.h"
+#include "dev_buf.h"
 #include "ebo_internal.h"
 #include "field_tv.h"
 #include "host_lm.h"
@@ -45,6 +46,36 @@ struct WindowInfo
 	int64_t t_ref;
 	uint64_t n_events;
 };
+
+// host memory that kernels read and write directly: mapped into the device's address space and
+// coherent (fine-grained), whatever HIP_HOST_COHERENT says
+constexpr unsigned int kZeroCopyFlags = hipHostMallocMapped | hipHostMallocCoherent;
+
+// The two memory policies of DevBuf (dev_buf.h): the only callers of the HIP allocation functions in the host
+// sources.  A failed allocation returns nullptr and leaves its code to hipGetLastError (ebo_ctx::grow reports it).
+struct DeviceMem
+{
+	static void* allocate(size_t bytes)
+	{
+		void* p = nullptr;
+		return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr;
+	}
+	static void release(void* p) { (void)hipFree(p); }
+};
+template <unsigned int Flags>
+struct PinnedMem
+{
+	static void* allocate(size_t bytes)
+	{
+		void* p = nullptr;
+		return hipHostMalloc(&p, bytes, Flags) == hipSuccess ? p : nullptr;
+	}
+	static void release(void* p) { (void)hipHostFree(p); }
+};
+template <class T>
+using Dev = ebo::DevBuf<T, DeviceMem>;
+template <class T, unsigned int Flags = kZeroCopyFlags>
+using Pinned = ebo::DevBuf<T, PinnedMem<Flags>>;
 }  // namespace ebo_host
 using namespace ebo_host;
 
@@ -61,80 +92,62 @@ struct ebo_ctx
 	int cap_windows = 0;
 	int n_windows = 0;
 
-	uint64_t* d_events = nullptr;
-	Unit* d_units = nullptr;
-	int32_t* d_unit_maxdt = nullptr;  // [units] max |t_ref(window) - t| over the unit's events (count kernels' displacement bound)
-	double* d_flows = nullptr;
-	double* d_out = nullptr;
-	double* d_partials = nullptr;
-	size_t partials_cap = 0;
-	int32_t* d_counts = nullptr;
-	double* d_image = nullptr;
-	void* d_aux = nullptr;
-	size_t aux_cap = 0;
-	unsigned char* d_modes = nullptr;        // per-flow-slot evaluation modes of a lock-step solve
-	size_t modes_cap = 0;
+	Dev<uint64_t> d_events;
+	Dev<Unit> d_units;
+	Dev<int32_t> d_unit_maxdt;  // [units] max |t_ref(window) - t| over the unit's events (count kernels' displacement bound)
+	Dev<double> d_flows;
+	Dev<double> d_out;
+	Dev<double> d_partials;
+	Dev<int32_t> d_counts;
+	Dev<double> d_image;
+	Dev<void> d_aux;
+	Dev<unsigned char> d_modes;  // per-flow-slot evaluation modes of a lock-step solve
 	const unsigned char* modes_active = nullptr;  // non-null only inside eval_host(modes)
 	LiveWindows live_active;                      // n > 0 only inside a compact round of a pipelined lock-step solve
-	double2* d_opt_grid = nullptr;   // Optimizer::setGrad's interleaved gradient grid [H][W]
+	Dev<double2> d_opt_grid;  // Optimizer::setGrad's interleaved gradient grid [H][W]
 	bool opt_grid_valid = false;
-	void* d_opt = nullptr;           // scratch of ebo_optimizer_eval / _solve
-	size_t opt_cap = 0;
-	unsigned int* d_count_sorted = nullptr;     // k_csort_*: destination list (two halves); sized by the plan of the largest call
-	size_t count_sorted_cap = 0;                // in bytes
-	unsigned int* d_count_bins = nullptr;       // k_csort_*: counts, starts, cursors per (window, band)
-	size_t count_bins_cap = 0;                  // in bytes
-	int32_t* d_stats = nullptr;
-	void* d_scratch = nullptr;  // patch-integrate staging
-	size_t scratch_cap = 0;
-	double* d_edge_w = nullptr;      // the 49 tensor weights of the edge loss (device table)
+	Dev<void> d_opt;  // scratch of ebo_optimizer_eval / _solve
+	Dev<unsigned int> d_count_sorted;  // k_csort_*: destination list (two halves); sized by the plan of the largest call
+	Dev<unsigned int> d_count_bins;  // k_csort_*: counts, starts, cursors per (window, band)
+	Dev<int32_t> d_stats;
+	Dev<void> d_scratch;  // patch-integrate staging
+	Dev<double> d_edge_w;  // the 49 tensor weights of the edge loss (device table)
 	double edge_w_sigma = -1.0;      // sigma_st they were built for
 	unsigned long long* edge_stats_dev = nullptr;  // set only while ebo_edge_work_stats runs its one evaluation
-	double* d_edge_cs = nullptr;     // eigenvector directions of the edge loss's eigenvalue pass, [workgroup slot][cap_px][2]
-	int n_cus = 0;                   // compute units of the device (0: not asked yet)
+	Dev<double> d_edge_cs;  // eigenvector directions of the edge loss's eigenvalue pass, [workgroup slot][cap_px][2]
+	int n_cus = 0;                   // compute units of the device
 	// the compact path's per-launch tables in one allocation: int length (+ 3 ints of padding) | int list[items] (the
 	// units whose arrays do not fit the compact layout) | int4 bbox[items] (k_edge_classify's tap bounding boxes)
-	int* d_edge_defer = nullptr;
-	size_t edge_defer_cap = 0;       // items
-	size_t edge_cs_cap = 0;          // bytes
-	void* d_edge_scratch = nullptr;  // edge-loss fallback arrays
-	size_t edge_scratch_cap = 0;
-	void* d_field = nullptr;         // motion field of ebo_init_motion_field (+ its staging)
-	size_t field_cap = 0;
+	Dev<int> d_edge_defer;
+	Dev<void> d_edge_scratch;  // edge-loss fallback arrays
+	Dev<void> d_field;  // motion field of ebo_init_motion_field (+ its staging)
 	bool field_valid = false;
 	const int* d_field_fixed = nullptr;  // fixed points of that field, [field_nfixed][2]
 	int field_nfixed = 0;
-	void* d_tvf = nullptr;           // workspace of ebo_interpolate_motion_field
-	size_t tvf_cap = 0;
-	double* d_fe_lut = nullptr;      // image front end: the 256 log-image values of ebo_image_gradients
-	void* d_fe = nullptr;            // its per-call workspace (image, mask, outputs, Harris response, candidate lists)
-	size_t fe_cap = 0;
-	char* d_fe_pyr[2] = {};          // pyramids + derivatives of the last two ebo_lk_add_image images
-	FeLevel* d_fe_lv = nullptr;      // their level table (both have the image's shape)
+	Dev<void> d_tvf;  // workspace of ebo_interpolate_motion_field
+	Dev<double> d_fe_lut;  // image front end: the 256 log-image values of ebo_image_gradients
+	Dev<void> d_fe;  // its per-call workspace (image, mask, outputs, Harris response, candidate lists)
+	Dev<char> d_fe_pyr[2];  // pyramids + derivatives of the last two ebo_lk_add_image images
+	Dev<FeLevel> d_fe_lv;  // their level table (both have the image's shape)
 	std::vector<FeLevel> fe_lv;
-	size_t fe_pyr_bytes = 0;
 	int fe_newer = 0;                // slot of the newer image
 	int fe_images = 0;               // images added, up to 2
-	void* d_fe_pts = nullptr;        // ebo_lk_track's points, status and errors
-	size_t fe_pts_cap = 0;
+	Dev<void> d_fe_pts;  // ebo_lk_track's points, status and errors
 	void* comm = nullptr;            // ncclComm_t of ebo_comm_init
 	int comm_rank = 0, comm_size = 1;
-	uint64_t* d_comm_cnt = nullptr;  // [nranks + 2] counts / flags of the exchange (allocated by ebo_comm_init)
-	uint64_t* pin_comm = nullptr;    // the same, pinned host side
-	void* d_comm_buf = nullptr;      // track exchange buffer; grown collectively (ebo_comm.cpp: ensure_comm_buf)
-	size_t comm_buf_cap = 0;
-	void* d_raw = nullptr;           // raw 24-byte (or compact 8-byte) events staged for device bucketing
+	Dev<uint64_t> d_comm_cnt;  // [nranks + 2] counts / flags of the exchange (allocated by ebo_comm_init)
+	Pinned<uint64_t, hipHostMallocDefault> pin_comm;  // the same, pinned host side
+	Dev<void> d_comm_buf;  // track exchange buffer; grown collectively (ebo_comm.cpp: ensure_comm_buf)
+	Dev<void> d_raw;  // raw 24-byte (or compact 8-byte) events staged for device bucketing
 	hipStream_t copy_stream = nullptr;  // uploads of ebo_set_windows / ebo_set_windows8, overlapped with the bucketing
 	hipEvent_t copy_done[8] = {};
-	void* d_bucket = nullptr;        // bucketing scratch
-	unsigned int* d_chunk_hist = nullptr;  // per-chunk bucket histograms / first ranks of the stable scatter
-	size_t chunk_hist_cap = 0;       // in entries
-	size_t bucket_cap = 0;
+	Dev<void> d_bucket;  // bucketing scratch
+	Dev<unsigned int> d_chunk_hist;  // per-chunk bucket histograms / first ranks of the stable scatter
 	// ebo_set_rectification (ebo_camera.cpp): the sensor's rectification table and map; rect_set selects the
 	// Rectified<> bucketing kernels for the NEXT load
-	void* d_rect_lut = nullptr;      // int16 [image_h][image_w][2]
-	double* d_rect_map = nullptr;    // double [image_h][image_w][2]
-	int* d_rect_bad = nullptr;       // k_rectify_map's error bits
+	Dev<void> d_rect_lut;  // int16 [image_h][image_w][2]
+	Dev<double> d_rect_map;  // double [image_h][image_w][2]
+	Dev<int> d_rect_bad;  // k_rectify_map's error bits
 	std::vector<int16_t> rect_lut;   // host copy for the host counting sort, fetched on its first use
 	bool rect_set = false;
 
@@ -143,28 +156,23 @@ struct ebo_ctx
 	std::vector<int64_t> unit_tmin, unit_tmax;  // ebo_set_patches: earliest / latest event time per unit (ebo_count_image_shard)
 	std::vector<int16_t> unit_box;              // ebo_set_patches: [unit][4] = min x, max x, min y, max y of the unit's events
 	uint64_t units_gen = 0;                     // bumped by every ebo_set_*: invalidates the cached shard tables below
-	void* d_shard_tbl = nullptr;                // BandUnit[units] (band image) / int32 dt_win[units] (dense shard image)
-	size_t shard_tbl_cap = 0;
+	Dev<void> d_shard_tbl;  // BandUnit[units] (band image) / int32 dt_win[units] (dense shard image)
 	uint64_t shard_tbl_gen = 0;                 // units_gen the table was built for (0 = none)
 	int shard_tbl_kind = 0;                     // 1 = dt_win only, 2 = BandUnit
 	std::vector<int64_t> shard_tbl_tref;        // the windows' reference times it was built for
-	int* d_escaped_own = nullptr;               // ebo_count_image_band's own flag word
 	std::vector<WindowInfo> windows;
 	std::vector<uint64_t> h_packed;
+	Dev<uint32_t> d_route_xy;  // ebo_route_set_events: x:16 | y:16 per event of the chunk
+	size_t route_n = 0;
+	Pinned<void> pin_route;  // pinned, device-visible arguments and results of ebo_route_events
+	Pinned<void, hipHostMallocDefault> pin_bucket;  // pinned mirror of the bucketing results (offsets in; units, reference times, flag out)
 	// pinned, device-visible staging of one evaluation round (flows in, (r, J0, J1) out, modes):
 	// small rounds let the kernels read and write it directly (no copy packets at all), large
-	// ones copy from/to it at DMA speed
-	uint32_t* d_route_xy = nullptr;  // ebo_route_set_events: x:16 | y:16 per event of the chunk
-	size_t route_cap = 0;
-	size_t route_n = 0;
-	void* pin_route = nullptr;       // pinned, device-visible arguments and results of ebo_route_events
-	size_t pin_route_cap = 0;
-	void* pin_bucket = nullptr;      // pinned mirror of the bucketing results (offsets in; units, reference times, flag out)
-	size_t pin_bucket_cap = 0;
-	double* pin_flows = nullptr;
-	double* pin_out = nullptr;
-	unsigned char* pin_modes = nullptr;
-	size_t pin_cap = 0;
+	// ones copy from/to it at DMA speed.  Three blocks of ONE logical size (grow_eval_staging, ebo_api.cpp):
+	// flows [nf][2], results [nf][3], mode tables [4][nf]
+	Pinned<double> pin_flows;
+	Pinned<double> pin_out;
+	Pinned<unsigned char> pin_modes;
 
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	// ebo_two_view_timing (ebo_twoview.cpp): events around the phases of ebo_relative_pose_ransac, created on first use
@@ -202,6 +210,39 @@ struct ebo_ctx
 		err = std::string(what) + ": " + hipGetErrorString(e);
 		return EBO_ERR_HIP;
 	}
+
+	// The one way a buffer of the context comes to hold at least n elements (contents not kept): `what` names it in
+	// "<what>: <hip error>".  A live buffer is released only once the stream has drained (a launch in flight may still
+	// use it), and never while a graph is being recorded: a recorded call cannot allocate, free or synchronise, so a
+	// buffer that does not fit then is refused with EBO_ERR_STATE and left as it is -- recording and context intact.
+	template <class B>
+	int grow(B& b, size_t n, const char* what)
+	{
+		if (n > b.cap() && b.get() && !capturing)
+		{
+			const int rc = hip(hipStreamSynchronize(stream), "sync");
+			if (rc)
+			{
+				return rc;
+			}
+		}
+		return grown(b.ensure(n, !capturing), what);
+	}
+	int grown(Grow g, const char* what)
+	{
+		if (g == Grow::kRefused)
+		{
+			return fail(EBO_ERR_STATE, std::string(what) +
+										   ": refused while recording a graph, the call needs a larger buffer than the context holds: "
+										   "run the same call once before recording");
+		}
+		if (g == Grow::kFailed)
+		{
+			const hipError_t e = hipGetLastError();
+			return hip(e != hipSuccess ? e : hipErrorOutOfMemory, what);
+		}
+		return EBO_OK;
+	}
 };
 
 // Between ebo_graph_begin and ebo_graph_end only the asynchronous *_device calls may run: anything that copies
@@ -215,12 +256,9 @@ namespace ebo_host
 {
 extern thread_local std::string g_create_error;  // errors without a context (ebo_last_error(NULL))
 extern const size_t kLdsBudget;
-extern const unsigned int kZeroCopyFlags;
 ebo::EvalConsts make_consts(const ebo_ctx* c);
 void rect_of(const ebo_ctx* c, int px, int py, int& x, int& y, int& w, int& h);
 bool mid_timestamp(int64_t a, int64_t b, int64_t& out);
-int ensure_scratch(ebo_ctx* c, size_t bytes);
-int ensure_aux(ebo_ctx* c, size_t bytes);
 ebo::SolveConsts make_solve_consts(const ebo_solver_opts* o);
 int check_solver_opts(ebo_ctx* c, const ebo_solver_opts* o);
 int shard_table(ebo_ctx* c, int n_windows, const int64_t* window_t_ref_us, const ebo::BandUnit** out, bool* uniformFlows);

@@ -11,27 +11,6 @@ size_t align256(size_t v)
 	return (v + 255) & ~static_cast<size_t>(255);
 }
 
-// grows a device buffer to at least `need` bytes (contents are not kept)
-int ensure(ebo_ctx* c, void** p, size_t* cap, size_t need, const char* what)
-{
-	if (need <= *cap)
-	{
-		return EBO_OK;
-	}
-	if (*p)
-	{
-		hipFree(*p);
-		*p = nullptr;
-		*cap = 0;
-	}
-	int rc = c->hip(hipMalloc(p, need), what);
-	if (rc == EBO_OK)
-	{
-		*cap = need;
-	}
-	return rc;
-}
-
 int entry_checks(ebo_ctx* c)
 {
 	if (c->capturing)
@@ -80,7 +59,7 @@ int ebo_image_gradients(ebo_ctx* c, const uint8_t* image, double* grad_x, double
 		{
 			lut[v] = std::log(v * (1.0 / 255.0) + 10e-2) / 8;
 		}
-		rc = c->hip(hipMalloc(&c->d_fe_lut, sizeof(lut)), "hipMalloc log table");
+		rc = c->grow(c->d_fe_lut, 256, "hipMalloc log table");
 		if (rc)
 		{
 			return rc;
@@ -88,16 +67,17 @@ int ebo_image_gradients(ebo_ctx* c, const uint8_t* image, double* grad_x, double
 		rc = c->hip(hipMemcpy(c->d_fe_lut, lut, sizeof(lut), hipMemcpyHostToDevice), "H2D log table");
 		if (rc)
 		{
+			c->d_fe_lut.reset();  // (its presence says that it is filled)
 			return rc;
 		}
 	}
 	const size_t bImg = align256(npx), bG = align256(npx * 8);
-	rc = ensure(c, &c->d_fe, &c->fe_cap, bImg + 2 * bG, "hipMalloc front-end workspace");
+	rc = c->grow(c->d_fe, bImg + 2 * bG, "hipMalloc front-end workspace");
 	if (rc)
 	{
 		return rc;
 	}
-	char* base = static_cast<char*>(c->d_fe);
+	char* base = static_cast<char*>(c->d_fe.get());
 	uint8_t* d_img = reinterpret_cast<uint8_t*>(base);
 	double* d_gx = reinterpret_cast<double*>(base + bImg);
 	double* d_gy = reinterpret_cast<double*>(base + bImg + bG);
@@ -152,13 +132,13 @@ int ebo_good_features(ebo_ctx* c, const uint8_t* image, const uint8_t* mask, int
 	const size_t bImg = align256(npx), bResp = align256(npx * 8), bMax = align256(nb * 8);
 	const size_t bCR = align256(capPow2 * 8), bCI = align256(capPow2 * 4);
 	const size_t bCorners = align256(static_cast<size_t>(max_corners) * 8);
-	rc = ensure(c, &c->d_fe, &c->fe_cap, 2 * bImg + bResp + bMax + bCR + bCI + bCorners + 256,
+	rc = c->grow(c->d_fe, 2 * bImg + bResp + bMax + bCR + bCI + bCorners + 256,
 				"hipMalloc front-end workspace");
 	if (rc)
 	{
 		return rc;
 	}
-	char* p = static_cast<char*>(c->d_fe);
+	char* p = static_cast<char*>(c->d_fe.get());
 	uint8_t* d_img = reinterpret_cast<uint8_t*>(p);
 	uint8_t* d_mask = reinterpret_cast<uint8_t*>(p + bImg);
 	p += 2 * bImg;
@@ -261,25 +241,18 @@ int ebo_lk_add_image(ebo_ctx* c, const uint8_t* image)
 			w = nw;
 			h = nh;
 		}
-		for (int s = 0; s < 2; ++s)
-		{
-			rc = c->hip(hipMalloc(reinterpret_cast<void**>(&c->d_fe_pyr[s]), off), "hipMalloc pyramid");
-			if (rc)
-			{
-				return rc;
-			}
-		}
-		rc = c->hip(hipMalloc(reinterpret_cast<void**>(&c->d_fe_lv), lv.size() * sizeof(FeLevel)), "hipMalloc levels");
+		// (fe_lv says that all of this succeeded: a failed attempt leaves nothing behind)
+		rc = c->grow(c->d_fe_pyr[0], off, "hipMalloc pyramid");
+		if (rc == EBO_OK) rc = c->grow(c->d_fe_pyr[1], off, "hipMalloc pyramid");
+		if (rc == EBO_OK) rc = c->grow(c->d_fe_lv, lv.size(), "hipMalloc levels");
+		if (rc == EBO_OK) rc = c->hip(hipMemcpy(c->d_fe_lv, lv.data(), lv.size() * sizeof(FeLevel), hipMemcpyHostToDevice), "H2D levels");
 		if (rc)
 		{
+			c->d_fe_pyr[0].reset();
+			c->d_fe_pyr[1].reset();
+			c->d_fe_lv.reset();
 			return rc;
 		}
-		rc = c->hip(hipMemcpy(c->d_fe_lv, lv.data(), lv.size() * sizeof(FeLevel), hipMemcpyHostToDevice), "H2D levels");
-		if (rc)
-		{
-			return rc;
-		}
-		c->fe_pyr_bytes = off;
 		c->fe_lv = lv;
 	}
 	// the older image's slot takes the new one; the newer becomes the older without recomputation
@@ -342,12 +315,12 @@ int ebo_lk_track(ebo_ctx* c, int n, const float* prev_xy, float* next_xy, uint8_
 	}
 	const size_t bXY = align256(static_cast<size_t>(n) * 8), bSt = align256(static_cast<size_t>(n)),
 				 bErr = align256(static_cast<size_t>(n) * 4);
-	rc = ensure(c, &c->d_fe_pts, &c->fe_pts_cap, 2 * bXY + bSt + bErr, "hipMalloc LK points");
+	rc = c->grow(c->d_fe_pts, 2 * bXY + bSt + bErr, "hipMalloc LK points");
 	if (rc)
 	{
 		return rc;
 	}
-	char* p = static_cast<char*>(c->d_fe_pts);
+	char* p = static_cast<char*>(c->d_fe_pts.get());
 	float* d_prev = reinterpret_cast<float*>(p);
 	float* d_next = reinterpret_cast<float*>(p + bXY);
 	uint8_t* d_status = reinterpret_cast<uint8_t*>(p + 2 * bXY);

@@ -32,22 +32,13 @@ int ebo_init_motion_field(ebo_ctx* c, int64_t timestamp, int use_average, int n_
 	const size_t bOff = al((static_cast<size_t>(n_patches) + 1) * 8), bXY = al(nSamples * 16), bT = al(nSamples * 8);
 	const size_t bFix = al(static_cast<size_t>(std::max(n_patches, 1)) * 8);
 	const size_t need = bField + bOff + bXY + bT + bFix + 512;
-	if (need > c->field_cap)
+	c->field_valid = false;  // (d_field_fixed points into the block: nothing may use it after a failed growth)
+	int rcg = c->grow(c->d_field, need, "hipMalloc motion field");
+	if (rcg)
 	{
-		if (c->d_field)
-		{
-			hipFree(c->d_field);
-			c->d_field = nullptr;
-			c->field_cap = 0;
-		}
-		int rc = c->hip(hipMalloc(&c->d_field, need), "hipMalloc motion field");
-		if (rc)
-		{
-			return rc;
-		}
-		c->field_cap = need;
+		return rcg;
 	}
-	char* base = static_cast<char*>(c->d_field);
+	char* base = static_cast<char*>(c->d_field.get());
 	FieldLaunch L;
 	L.w = w;
 	L.h = h;
@@ -161,20 +152,10 @@ int ebo_interpolate_motion_field(ebo_ctx* c, int use_l1, const ebo_solver_opts* 
 		}
 	}
 	const size_t need = tvf_workspace_bytes(w, h);
-	if (need > c->tvf_cap)
+	int rcg = c->grow(c->d_tvf, need, "hipMalloc TV workspace");
+	if (rcg)
 	{
-		if (c->d_tvf)
-		{
-			hipFree(c->d_tvf);
-			c->d_tvf = nullptr;
-			c->tvf_cap = 0;
-		}
-		int rc = c->hip(hipMalloc(&c->d_tvf, need), "hipMalloc TV workspace");
-		if (rc)
-		{
-			return rc;
-		}
-		c->tvf_cap = need;
+		return rcg;
 	}
 	ebo_solver_opts o;
 	if (opts)
@@ -191,7 +172,7 @@ int ebo_interpolate_motion_field(ebo_ctx* c, int use_l1, const ebo_solver_opts* 
 		o.parameter_tolerance = 1e-8;
 	}
 	FieldTvStats st;
-	int rc = field_tv_solve(w, h, static_cast<float*>(c->d_field), c->d_field_fixed, c->field_nfixed,
+	int rc = field_tv_solve(w, h, static_cast<float*>(c->d_field.get()), c->d_field_fixed, c->field_nfixed,
 							use_l1 != 0, o, c->d_tvf, c->stream, &st, &c->err);
 	if (rc)
 	{

@@ -112,12 +112,12 @@ static int patch_integrate_common(ebo_ctx* c, const ebo_event* ev, const size_t*
 	auto align = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
 	const size_t bEv = align(total * 8), bOff = align(off32.size() * 4), bRect = align(static_cast<size_t>(n_patches) * 32);
 	const size_t bTraj = align(tr.size() * 8), bNoff = align(noff.size() * 8), bNabla = align(nablaEnd * 8);
-	int rc = ensure_scratch(c, bEv + bOff + bRect + bTraj + bNoff + bNabla);
+	int rc = c->grow(c->d_scratch, bEv + bOff + bRect + bTraj + bNoff + bNabla, "hipMalloc scratch");
 	if (rc)
 	{
 		return rc;
 	}
-	char* base = static_cast<char*>(c->d_scratch);
+	char* base = static_cast<char*>(c->d_scratch.get());
 	char* dEv = base;
 	char* dOff = dEv + bEv;
 	char* dRect = dOff + bOff;
@@ -172,17 +172,10 @@ int ebo_route_set_events(ebo_ctx* c, const ebo_event* ev, size_t n)
 	}
 	(void)hipSetDevice(c->prm.device);
 	c->route_n = 0;
-	if (n > c->route_cap)
+	int rcg = c->grow(c->d_route_xy, n, "hipMalloc route events");
+	if (rcg)
 	{
-		hipFree(c->d_route_xy);
-		c->d_route_xy = nullptr;
-		c->route_cap = 0;
-		int rc = c->hip(hipMalloc(reinterpret_cast<void**>(&c->d_route_xy), n * sizeof(uint32_t)), "hipMalloc route events");
-		if (rc)
-		{
-			return rc;
-		}
-		c->route_cap = n;
+		return rcg;
 	}
 	std::vector<uint32_t> xy(n);
 	for (size_t i = 0; i < n; ++i)
@@ -232,22 +225,12 @@ int ebo_route_events(ebo_ctx* c, int n_patches, const double* rects, const uint3
 	auto al = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
 	const size_t bR = al(np * 32), bU = al(np * 4), bI = al(np * cap * 4 + 4);
 	const size_t need = bR + 4 * bU + bI;
-	if (need > c->pin_route_cap)
+	int rcg = c->grow(c->pin_route, need, "hipHostMalloc route staging");
+	if (rcg)
 	{
-		if (c->pin_route)
-		{
-			(void)hipHostFree(c->pin_route);
-			c->pin_route = nullptr;
-			c->pin_route_cap = 0;
-		}
-		int rc = c->hip(hipHostMalloc(&c->pin_route, need, kZeroCopyFlags), "hipHostMalloc route staging");
-		if (rc)
-		{
-			return rc;
-		}
-		c->pin_route_cap = need;
+		return rcg;
 	}
-	char* pin = static_cast<char*>(c->pin_route);
+	char* pin = static_cast<char*>(c->pin_route.get());
 	std::memcpy(pin, rects, np * 32);
 	std::memcpy(pin + bR, start, np * 4);
 	std::memcpy(pin + bR + bU, max_take, np * 4);
@@ -332,21 +315,17 @@ int ebo_optimizer_set_grad(ebo_ctx* c, const double* grad_x, const double* grad_
 	}
 	(void)hipSetDevice(c->prm.device);
 	const size_t n = static_cast<size_t>(c->prm.image_w) * c->prm.image_h;
-	int rc = EBO_OK;
-	if (!c->d_opt_grid)
-	{
-		rc = c->hip(hipMalloc(reinterpret_cast<void**>(&c->d_opt_grid), n * sizeof(double2)), "hipMalloc gradient grid");
-		if (rc)
-		{
-			return rc;
-		}
-	}
-	rc = ensure_aux(c, 2 * n * sizeof(double));
+	int rc = c->grow(c->d_opt_grid, n, "hipMalloc gradient grid");
 	if (rc)
 	{
 		return rc;
 	}
-	double* stage = static_cast<double*>(c->d_aux);
+	rc = c->grow(c->d_aux, 2 * n * sizeof(double), "hipMalloc aux");
+	if (rc)
+	{
+		return rc;
+	}
+	double* stage = static_cast<double*>(c->d_aux.get());
 	hipError_t e = hipMemcpyAsync(stage, grad_x, n * sizeof(double), hipMemcpyHostToDevice, c->stream);
 	if (e == hipSuccess)
 	{
@@ -391,12 +370,12 @@ int ebo_estimate_num_events(ebo_ctx* c, int n, const double* rects, const double
 	}
 	(void)hipSetDevice(c->prm.device);
 	const size_t nn = static_cast<size_t>(n);
-	int rc = ensure_scratch(c, nn * 10 * sizeof(double));
+	int rc = c->grow(c->d_scratch, nn * 10 * sizeof(double), "hipMalloc scratch");
 	if (rc)
 	{
 		return rc;
 	}
-	double* d = static_cast<double*>(c->d_scratch);
+	double* d = static_cast<double*>(c->d_scratch.get());
 	double* dRects = d;
 	double* dPoses = d + 4 * nn;
 	double* dFlows = d + 8 * nn;
@@ -476,12 +455,12 @@ int ebo_patch_warp_image(ebo_ctx* c, int n, const double* rects, const double* p
 	}
 	const size_t head = nn * 9 * sizeof(double) + nn * sizeof(int) + nn * sizeof(size_t);
 	const size_t headAligned = (head + 15) & ~static_cast<size_t>(15);
-	int rc = ensure_scratch(c, headAligned + total * sizeof(double));
+	int rc = c->grow(c->d_scratch, headAligned + total * sizeof(double), "hipMalloc scratch");
 	if (rc)
 	{
 		return rc;
 	}
-	char* base = static_cast<char*>(c->d_scratch);
+	char* base = static_cast<char*>(c->d_scratch.get());
 	double* dRects = reinterpret_cast<double*>(base);
 	double* dPoses = dRects + 4 * nn;
 	double* dFlows = dPoses + 4 * nn;
@@ -574,22 +553,12 @@ int optimizer_stage(ebo_ctx* c, int n, const double* rects, const double* nabla,
 	const size_t bX = al(static_cast<size_t>(n) * 5 * 8), bStats = al(static_cast<size_t>(n) * 8 * 8);
 	const size_t need = bPatch + 2 * bVec + bX + bStats + (wantRes ? bVec : 0) + (wantJac ? 5 * bVec : 0) + 256;
 	(void)hipSetDevice(c->prm.device);
-	if (need > c->opt_cap)
+	int rcg = c->grow(c->d_opt, need, "hipMalloc optimizer scratch");
+	if (rcg)
 	{
-		if (c->d_opt)
-		{
-			hipFree(c->d_opt);
-			c->d_opt = nullptr;
-			c->opt_cap = 0;
-		}
-		int rc = c->hip(hipMalloc(&c->d_opt, need), "hipMalloc optimizer scratch");
-		if (rc)
-		{
-			return rc;
-		}
-		c->opt_cap = need;
+		return rcg;
 	}
-	char* b = static_cast<char*>(c->d_opt);
+	char* b = static_cast<char*>(c->d_opt.get());
 	B.patches = reinterpret_cast<OptPatch*>(b);
 	b += bPatch;
 	B.nabla_in = reinterpret_cast<double*>(b);
@@ -752,13 +721,13 @@ int ebo_optimizer_cost_map(ebo_ctx* c, int n, const double* rects, const double*
 		}
 	}
 	const size_t bx = hxc.size() * 8, bo = static_cast<size_t>(n) * cells * 8;
-	rc = ensure_scratch(c, bx + bo + 256);
+	rc = c->grow(c->d_scratch, bx + bo + 256, "hipMalloc scratch");
 	if (rc)
 	{
 		return rc;
 	}
-	double* dX = static_cast<double*>(c->d_scratch);
-	double* dOut = reinterpret_cast<double*>(static_cast<char*>(c->d_scratch) + ((bx + 255) & ~static_cast<size_t>(255)));
+	double* dX = static_cast<double*>(c->d_scratch.get());
+	double* dOut = reinterpret_cast<double*>(static_cast<char*>(c->d_scratch.get()) + ((bx + 255) & ~static_cast<size_t>(255)));
 	hipError_t e = hipMemcpyAsync(dX, hxc.data(), bx, hipMemcpyHostToDevice, c->stream);
 	if (e != hipSuccess)
 	{

@@ -8,7 +8,6 @@
 #include <cmath>
 
 using namespace ebo;
-using ebo_host::ensure_scratch;
 
 namespace
 {
@@ -32,7 +31,7 @@ struct Carve
 template <class T>
 T* at(ebo_ctx* c, size_t off)
 {
-	return reinterpret_cast<T*>(static_cast<char*>(c->d_scratch) + off);
+	return reinterpret_cast<T*>(static_cast<char*>(c->d_scratch.get()) + off);
 }
 
 int check_params(ebo_ctx* c, const ebo_two_view_params* p)
@@ -154,7 +153,7 @@ int ransac(ebo_ctx* c, int n_pairs, const int* offsets, const double* f1, const 
 	const size_t oWinner = cv.take(static_cast<size_t>(n_pairs) * sizeof(int));
 	const size_t oFlags = cv.take(static_cast<size_t>(total) + 1);
 	const size_t oWinModels = cv.take(static_cast<size_t>(n_pairs) * 12 * sizeof(double));
-	rc = ensure_scratch(c, cv.at);
+	rc = c->grow(c->d_scratch, cv.at, "hipMalloc scratch");
 	if (rc)
 	{
 		return rc;
@@ -413,7 +412,7 @@ int ebo_relative_pose_scores(ebo_ctx* c, const double* model, int n, const doubl
 	Carve cv;
 	const size_t bF = static_cast<size_t>(n) * 3 * sizeof(double);
 	const size_t oF1 = cv.take(bF), oF2 = cv.take(bF), oS = cv.take(static_cast<size_t>(n) * sizeof(double)), oFl = cv.take(n);
-	rc = ensure_scratch(c, cv.at);
+	rc = c->grow(c->d_scratch, cv.at, "hipMalloc scratch");
 	if (rc)
 	{
 		return rc;
@@ -483,7 +482,7 @@ int ebo_triangulate(ebo_ctx* c, int n_poses, const double* poses, int n, const i
 	const size_t bF = static_cast<size_t>(n) * 3 * sizeof(double), bP = static_cast<size_t>(n_poses) * 12 * sizeof(double);
 	const size_t oP = cv.take(bP), oPair = cv.take(static_cast<size_t>(n) * 2 * sizeof(int));
 	const size_t oF1 = cv.take(bF), oF2 = cv.take(bF), oOut = cv.take(bF);
-	rc = ensure_scratch(c, cv.at);
+	rc = c->grow(c->d_scratch, cv.at, "hipMalloc scratch");
 	if (rc)
 	{
 		return rc;
@@ -529,7 +528,7 @@ int ebo_epipolar_inliers(ebo_ctx* c, const double* model, int n, const double* f
 	Carve cv;
 	const size_t bF = static_cast<size_t>(n) * 3 * sizeof(double);
 	const size_t oF1 = cv.take(bF), oF2 = cv.take(bF), oFl = cv.take(n);
-	rc = ensure_scratch(c, cv.at);
+	rc = c->grow(c->d_scratch, cv.at, "hipMalloc scratch");
 	if (rc)
 	{
 		return rc;

@@ -61,22 +61,12 @@ static int set_windows_on_device(ebo_ctx* c, const void* d_raw, const size_t* of
 	auto al = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
 	const size_t bOff = al((n_windows + 1) * 8), bCnt = al(nUnits * 4), bT = al(nUnits * 8), bW = al(n_windows * 8);
 	const size_t need = bOff + bCnt + 3 * bT + bW + 256 + bW;
-	if (need > c->bucket_cap)
+	int rcb = c->grow(c->d_bucket, need, "hipMalloc bucket scratch");
+	if (rcb)
 	{
-		if (c->d_bucket)
-		{
-			hipFree(c->d_bucket);
-			c->d_bucket = nullptr;
-			c->bucket_cap = 0;
-		}
-		int rc = c->hip(hipMalloc(&c->d_bucket, need), "hipMalloc bucket scratch");
-		if (rc)
-		{
-			return rc;
-		}
-		c->bucket_cap = need;
+		return rcb;
 	}
-	char* base = static_cast<char*>(c->d_bucket);
+	char* base = static_cast<char*>(c->d_bucket.get());
 	BucketLaunch L;
 	L.d_raw = d_raw;
 	L.d_offsets = reinterpret_cast<unsigned long long*>(base);
@@ -97,20 +87,10 @@ static int set_windows_on_device(ebo_ctx* c, const void* d_raw, const size_t* of
 	{
 		// [windows][chunks][P + 1] counters of the stable scatter: events x (P + 1) / 512 bytes
 		const size_t needHist = static_cast<size_t>(n_windows) * std::max(L.max_chunks, 1) * (P + 1);
-		if (needHist > c->chunk_hist_cap)
+		int rch = c->grow(c->d_chunk_hist, needHist, "hipMalloc chunk histograms");
+		if (rch)
 		{
-			if (c->d_chunk_hist)
-			{
-				hipFree(c->d_chunk_hist);
-				c->d_chunk_hist = nullptr;
-				c->chunk_hist_cap = 0;
-			}
-			int rch = c->hip(hipMalloc(reinterpret_cast<void**>(&c->d_chunk_hist), needHist * sizeof(unsigned int)), "hipMalloc chunk histograms");
-			if (rch)
-			{
-				return rch;
-			}
-			c->chunk_hist_cap = needHist;
+			return rch;
 		}
 		L.d_chunk_hist = c->d_chunk_hist;
 	}
@@ -126,22 +106,12 @@ static int set_windows_on_device(ebo_ctx* c, const void* d_raw, const size_t* of
 	const size_t tail = bT + bW + 256;  // unit tref | window tref | flag, contiguous in the scratch block
 	const size_t pUnits = al(nUnits * sizeof(Unit));
 	const size_t pinNeed = bOff + pUnits + tail + bW;
-	if (pinNeed > c->pin_bucket_cap)
+	int rcp = c->grow(c->pin_bucket, pinNeed, "hipHostMalloc bucket mirror");
+	if (rcp)
 	{
-		if (c->pin_bucket)
-		{
-			(void)hipHostFree(c->pin_bucket);
-			c->pin_bucket = nullptr;
-			c->pin_bucket_cap = 0;
-		}
-		int rcp = c->hip(hipHostMalloc(&c->pin_bucket, pinNeed, hipHostMallocDefault), "hipHostMalloc bucket mirror");
-		if (rcp)
-		{
-			return rcp;
-		}
-		c->pin_bucket_cap = pinNeed;
+		return rcp;
 	}
-	char* pin = static_cast<char*>(c->pin_bucket);
+	char* pin = static_cast<char*>(c->pin_bucket.get());
 	std::memcpy(pin, off64.data(), off64.size() * 8);
 	int rc = c->hip(hipMemcpyAsync(const_cast<unsigned long long*>(L.d_offsets), pin, off64.size() * 8,
 								   hipMemcpyHostToDevice, c->stream),
@@ -355,13 +325,10 @@ int ebo_set_windows(ebo_ctx* c, const ebo_event* ev, const size_t* offsets, int 
 	}
 	// default: raw events go to the device once; bucketing and packing happen there
 	(void)hipSetDevice(c->prm.device);
-	if (!c->d_raw)
+	int rc = c->grow(c->d_raw, c->cap_events * sizeof(ebo_event), "hipMalloc raw events");
+	if (rc)
 	{
-		int rc = c->hip(hipMalloc(&c->d_raw, c->cap_events * sizeof(ebo_event)), "hipMalloc raw events");
-		if (rc)
-		{
-			return rc;
-		}
+		return rc;
 	}
 	std::vector<size_t> rel(n_windows + 1);
 	for (int w = 0; w <= n_windows; ++w)
@@ -449,13 +416,10 @@ int ebo_set_windows8(ebo_ctx* c, const ebo_event8* ev, const int64_t* t_base, co
 		return rc;
 	}
 	(void)hipSetDevice(c->prm.device);
-	if (!c->d_raw)
+	rc = c->grow(c->d_raw, c->cap_events * sizeof(ebo_event), "hipMalloc raw events");
+	if (rc)
 	{
-		rc = c->hip(hipMalloc(&c->d_raw, c->cap_events * sizeof(ebo_event)), "hipMalloc raw events");
-		if (rc)
-		{
-			return rc;
-		}
+		return rc;
 	}
 	const size_t total = offsets[n_windows] - offsets[0];
 	std::vector<size_t> rel(n_windows + 1);

@@ -154,7 +154,9 @@ int ebo_set_stream(ebo_ctx* ctx, void* hip_stream);
  * ebo_count_image_device, ...) are recorded instead of run; ebo_graph_end instantiates the graph.
  * ebo_graph_launch replays it `times` times back to back on the context's stream, asynchronously,
  * with no host work between the steps.  Recorded calls must not allocate or synchronise: run the
- * same sequence once before recording (work tables are allocated on first use).  The graph reads
+ * same sequence once before recording (work tables are allocated on first use).  A recorded call
+ * whose tables would have to grow, or whose edge-loss weights are not built yet, is refused with
+ * EBO_ERR_STATE: nothing was recorded for it, and the recording and the context stay usable.  The graph reads
  * and writes the device pointers it was recorded with; ebo_set_windows / ebo_set_patches with the
  * same sizes reuse the same buffers, other changes need a new recording.  ebo_graph_end always
  * ends the recording, also after a failed call (EBO_ERR_HIP then, no graph).  Not in the reference:

@@ -149,3 +149,45 @@ def test_recorded_warped_count_on_a_fresh_context(ebo, synth):
         c.count_image_device(ebo.COUNT_WARPED, d_flows.data_ptr(), d_img.data_ptr())
         c.synchronize()
         assert torch.equal(replayed, d_img) and float(d_img.sum()) > 0
+
+
+@pytest.mark.parametrize("loss", ["variance", "edge"])
+def test_first_evaluation_inside_a_recording_is_refused_and_the_context_goes_on(ebo, synth, loss):
+    """A recordable call whose work tables are not sized yet would have to allocate, which a recording cannot: the
+    first eval_device of a fresh context, made inside a recording, is refused with ERR_STATE before anything touches
+    the device.  The recording ends normally and the context works: the same call outside a recording, then recorded,
+    replays with the direct result's bits."""
+    import ctypes as C
+    import torch
+    L = ebo.LOSS_VARIANCE if loss == "variance" else ebo.LOSS_EDGE
+    c, ev, offsets, gt = _ctx(ebo, synth, L)
+    with c:
+        stream = torch.cuda.Stream()
+        c.set_stream(stream.cuda_stream)
+        torch.cuda.set_stream(stream)
+        d_flows = torch.from_numpy(gt * 0.5).to("cuda")
+        d_ref = torch.zeros((3 * c.P, 3), dtype=torch.float64, device="cuda")
+        d_out = torch.zeros_like(d_ref)
+        torch.cuda.synchronize()
+        lib = ebo.lib()
+        assert lib.ebo_graph_begin(c._h) == 0
+        try:
+            with pytest.raises(ebo.EboError) as refused:
+                c.eval_device(d_flows.data_ptr(), 1, d_out.data_ptr())
+        finally:
+            h = C.c_void_p()
+            ended = lib.ebo_graph_end(c._h, C.byref(h))
+            if h:
+                lib.ebo_graph_destroy(h)
+        assert refused.value.code == ebo.ERR_STATE and "before recording" in str(refused.value)
+        assert ended == 0  # the recording itself was intact
+        c.eval_device(d_flows.data_ptr(), 1, d_ref.data_ptr())
+        torch.cuda.synchronize()
+        assert float(d_out.abs().sum()) == 0.0 and float(d_ref.abs().sum()) > 0
+        g = c.record(lambda: c.eval_device(d_flows.data_ptr(), 1, d_out.data_ptr()))
+        assert float(d_out.abs().sum()) == 0.0  # recording runs nothing
+        g.launch(2)
+        torch.cuda.synchronize()
+        assert torch.equal(d_out, d_ref)
+        g.close()
+        torch.cuda.set_stream(torch.cuda.default_stream())
