@@ -30,7 +30,6 @@ def assert_jac_close(J, Jo, rtol=1e-8, patch_rel=1e-8, floor=1e-13):
             ratio = np.nanmax(np.where(scale > 0, (err - rtol * np.abs(Jo)) / scale, 0.0))
         with open(rec, "a") as f:
             f.write("%.3e %d\n" % (ratio, len(J)))
-        return
     bad = ~(err <= bound)  # also catches NaN on one side only
     bad &= ~(np.isnan(J) & np.isnan(Jo))
     if bad.any():
