@@ -198,6 +198,10 @@ def lib():
         _sc = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
         _lib.ebo_relative_pose_scores.argtypes = _sc
         _lib.ebo_relative_pose_scores_device.argtypes = _sc
+        _lib.ebo_absolute_pose_ransac.argtypes = _tv
+        _lib.ebo_absolute_pose_ransac_device.argtypes = _tv
+        _lib.ebo_absolute_pose_scores.argtypes = _sc
+        _lib.ebo_absolute_pose_scores_device.argtypes = _sc
         _tr = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.ebo_triangulate.argtypes = _tr
         _lib.ebo_triangulate_device.argtypes = _tr
@@ -1151,6 +1155,63 @@ class Context:
         model = np.ascontiguousarray(model, dtype=np.float64).reshape(3, 4)
         p = lambda v: C.c_void_p(int(v)) if v else None
         self._check(lib().ebo_relative_pose_scores_device(self._h, _vp(model), int(n), p(d_f1), p(d_f2), C.c_double(threshold),
+                                                          p(d_scores), p(d_flags)))
+
+    # -- absolute pose (three-point RANSAC on bearing vectors and landmarks) --------------------------
+    def absolute_pose_ransac(self, offsets, f, points, params, diagnostics=False, device=False):
+        """ebo_absolute_pose_ransac over len(offsets) - 1 keyframes.  f: float64 [total][3] unit bearing vectors,
+        points: float64 [total][3] landmarks in world coordinates (device=True: device pointers as int, and the _device
+        entry); params: a TwoViewParams whose threshold the caller has set.  -> list of dicts (found, model [3][4] =
+        the camera-to-world pose, winner, iterations, n_inliers, inliers int32 [n_inliers]); with diagnostics=True also
+        a dict of every hypothesis's counts [frames][H], models [frames][H][3][4] and samples [frames][H][4]."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        n_frames = len(offsets) - 1
+        total = int(offsets[-1]) if n_frames >= 0 and len(offsets) else 0
+        if device:
+            p1, p2 = C.c_void_p(int(f)), C.c_void_p(int(points))
+            fn = lib().ebo_absolute_pose_ransac_device
+        else:
+            f = np.ascontiguousarray(f, dtype=np.float64).reshape(-1, 3)
+            points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+            if len(f) != total or len(points) != total:
+                raise ValueError("f / points must hold offsets[-1] rows")
+            p1, p2 = _vp(f), _vp(points)
+            fn = lib().ebo_absolute_pose_ransac
+        res = (TwoViewResult * max(n_frames, 1))()
+        idx = np.zeros(max(total, 1), dtype=np.int32)
+        H = max(int(params.max_iterations), 1)
+        diag = None
+        if diagnostics:
+            diag = dict(counts=np.zeros((max(n_frames, 0), H), dtype=np.int32), models=np.zeros((max(n_frames, 0), H, 3, 4)),
+                        samples=np.zeros((max(n_frames, 0), H, 4), dtype=np.int32))
+        self._check(fn(self._h, n_frames, _vp(offsets), p1, p2, C.byref(params), res, _vp(idx),
+                       _vp(diag["counts"]) if diag else None, _vp(diag["models"]) if diag else None,
+                       _vp(diag["samples"]) if diag else None))
+        out = []
+        for k in range(n_frames):
+            r = res[k]
+            out.append(dict(found=bool(r.found), model=np.array(r.model[:]).reshape(3, 4), winner=r.winner,
+                            iterations=r.iterations, n_inliers=r.n_inliers,
+                            inliers=idx[r.inlier_offset:r.inlier_offset + r.n_inliers].copy()))
+        return (out, diag) if diagnostics else out
+
+    def absolute_pose_scores(self, pose, f, points, threshold):
+        """ebo_absolute_pose_scores: -> (scores float64 [n], inlier flags bool [n]) of a given pose [3][4]."""
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(3, 4)
+        f = np.ascontiguousarray(f, dtype=np.float64).reshape(-1, 3)
+        points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n = len(f)
+        sc = np.zeros(n)
+        fl = np.zeros(n, dtype=np.uint8)
+        self._check(lib().ebo_absolute_pose_scores(self._h, _vp(pose), n, _vp(f), _vp(points), C.c_double(threshold), _vp(sc),
+                                                   _vp(fl)))
+        return sc, fl.astype(bool)
+
+    def absolute_pose_scores_device(self, pose, n, d_f, d_points, threshold, d_scores=0, d_flags=0):
+        """The same on device arrays (pointers as int; either output may be 0), asynchronous on the context's stream."""
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(3, 4)
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        self._check(lib().ebo_absolute_pose_scores_device(self._h, _vp(pose), int(n), p(d_f), p(d_points), C.c_double(threshold),
                                                           p(d_scores), p(d_flags)))
 
     def triangulate(self, poses, pose_pair, f1, f2):

@@ -525,5 +525,15 @@ int launch_tv_triangulate(int n_poses, const double* d_poses, int n, const int* 
 						  const double* d_f2, double* d_points, void* stream);
 int launch_tv_epipolar(const double* model12, int n, const double* d_f1, const double* d_f2, double threshold,
 					   unsigned char* d_flags, void* stream);
+// absolute pose (ebo_abspose.inc, ebo_abspose.cpp).  models: [n_frames * H][3][4]; d_samples may be null.
+int launch_ap_hypotheses(int n_frames, int H, const int* d_offsets, const double* d_f, const double* d_points, uint64_t seed,
+						 double* d_models, int* d_valid, int* d_samples, void* stream);
+int launch_ap_count(int n_frames, int H, int max_n, const int* d_offsets, const double* d_f, const double* d_points,
+					const double* d_models, const int* d_valid, double threshold, int* d_counts, void* stream);
+int launch_ap_winner_flags(int n_frames, int H, int max_n, const int* d_offsets, const double* d_f, const double* d_points,
+						   const double* d_models, const int* d_valid, const int* d_winner, double threshold,
+						   unsigned char* d_flags, double* d_win_models, void* stream);
+int launch_ap_scores(const double* pose, int n, const double* d_f, const double* d_points, double threshold, double* d_scores,
+					 unsigned char* d_flags, void* stream);
 
 }  // namespace ebo

@@ -1268,6 +1268,7 @@ __global__ void __launch_bounds__(64) k_route(const uint32_t* __restrict__ xy, u
 #include "ebo_bucket.inc"
 #include "ebo_camera.inc"
 #include "ebo_twoview.inc"
+#include "ebo_abspose.inc"
 #include "ebo_field.inc"
 #include "ebo_fieldtv.inc"
 #include "ebo_optimizer.inc"
@@ -1897,6 +1898,61 @@ int launch_tv_epipolar(const double* model12, int n, const double* d_f1, const d
 	std::copy(model12, model12 + 12, m.m);
 	hipLaunchKernelGGL(k_tv_epipolar, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), m, n, d_f1, d_f2,
 					   threshold, d_flags);
+	return check_launch();
+}
+
+// absolute pose (ebo_abspose.inc)
+int launch_ap_hypotheses(int n_frames, int H, const int* d_offsets, const double* d_f, const double* d_points, uint64_t seed,
+						 double* d_models, int* d_valid, int* d_samples, void* stream)
+{
+	const long long total = static_cast<long long>(n_frames) * H;
+	if (total <= 0)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_ap_hypotheses, dim3(static_cast<unsigned int>((total + kApBlock - 1) / kApBlock)), dim3(kApBlock), 0,
+					   static_cast<hipStream_t>(stream), n_frames, H, d_offsets, d_f, d_points, static_cast<unsigned long long>(seed),
+					   d_models, d_valid, d_samples);
+	return check_launch();
+}
+
+int launch_ap_count(int n_frames, int H, int max_n, const int* d_offsets, const double* d_f, const double* d_points,
+					const double* d_models, const int* d_valid, double threshold, int* d_counts, void* stream)
+{
+	if (n_frames <= 0 || H <= 0 || max_n < 4)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_ap_count, dim3((H + kApHypChunk - 1) / kApHypChunk, n_frames, (max_n + kApTile - 1) / kApTile), dim3(256), 0,
+					   static_cast<hipStream_t>(stream), H, d_offsets, d_f, d_points, d_models, d_valid, threshold, d_counts);
+	return check_launch();
+}
+
+int launch_ap_winner_flags(int n_frames, int H, int max_n, const int* d_offsets, const double* d_f, const double* d_points,
+						   const double* d_models, const int* d_valid, const int* d_winner, double threshold,
+						   unsigned char* d_flags, double* d_win_models, void* stream)
+{
+	if (n_frames <= 0)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_ap_winner_flags, dim3(max_n > 0 ? (max_n + 255) / 256 : 1, n_frames), dim3(256), 0,
+					   static_cast<hipStream_t>(stream), H, d_offsets, d_f, d_points, d_models, d_valid, d_winner, threshold, d_flags,
+					   d_win_models);
+	return check_launch();
+}
+
+int launch_ap_scores(const double* pose, int n, const double* d_f, const double* d_points, double threshold, double* d_scores,
+					 unsigned char* d_flags, void* stream)
+{
+	if (n <= 0)
+	{
+		return 0;
+	}
+	TvModelArg m;
+	std::copy(pose, pose + 12, m.m);
+	hipLaunchKernelGGL(k_ap_scores, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), m, n, d_f, d_points,
+					   threshold, d_scores, d_flags);
 	return check_launch();
 }
 

@@ -1,12 +1,15 @@
 // track_recording — the reference's feature-tracking experiment on a DAVIS240C recording directory, without OpenCV:
 //
-//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify]
+//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--odometry]
 //
 // DIR holds events.txt, images.txt + the frames (8-bit grey PNG), optionally groundtruth.txt / calib.txt.
 // --rectify: the events of every compensation window are undistorted with the recording's calib.txt as they are
 // loaded (tools::EvaluatorParams::rectifyEvents); frames and tracked patches stay in raw coordinates.  The
 // recording is played through tools::Replayer into tools::Evaluator::replay (tools/recording_evaluator.h; the files
 // equal those of per-event callbacks).
+// --odometry: visual_odometry::VisualOdometryFrontEnd (visual_odometry/visual_odometry.h) runs as the keyframe hook on a
+// context of its own and OUT/keyframe_poses.txt gets one line per keyframe, stored ones first: the timestamp and the
+// camera-to-world pose [R | t] row by row (the first keyframe is the world frame, the first baseline the unit of length).
 // Writes OUT/trajectory.txt and OUT/final_cost.txt and prints one JSON line: frames, events, tracks (archived patches),
 // compensation windows, total ms (construction to the files written), ms per frame interval and Mevents/s.
 // Built by `make -C event-based-odomety_amd/csrc track_recording`.
@@ -19,10 +22,11 @@
 #include "../include/dataset_reader/davis240c_recording.h"
 #include "../include/tools/recording_evaluator.h"
 #include "../include/tools/replayer.h"
+#include "../include/visual_odometry/visual_odometry.h"
 
 static int usage(const char* argv0)
 {
-	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify]\n", argv0);
+	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--odometry]\n", argv0);
 	return 2;
 }
 
@@ -32,6 +36,7 @@ int main(int argc, char** argv)
 	bool trackerExperiment = false;
 	size_t windowBatch = 1;
 	bool rectify = false;
+	bool odometry = false;
 	for (int i = 1; i < argc; ++i)
 	{
 		const std::string a = argv[i];
@@ -50,6 +55,10 @@ int main(int argc, char** argv)
 		else if (a == "--rectify")
 		{
 			rectify = true;
+		}
+		else if (a == "--odometry")
+		{
+			odometry = true;
 		}
 		else if (a == "--window-batch" && i + 1 < argc)
 		{
@@ -83,9 +92,30 @@ int main(int argc, char** argv)
 			p.cameraModelParams = recording->getCalibration();
 			p.rectifyEvents = true;
 		}
-		size_t events = 0, frames = 0, tracks = 0, windows = 0;
+		size_t events = 0, frames = 0, tracks = 0, windows = 0, keyframes = 0, landmarks = 0;
+		ebo_ctx* odometryCtx = nullptr;
+		if (odometry)
 		{
-			tools::Evaluator evaluator(p);
+			ebo_params prm;
+			ebo_default_params(&prm);
+			if (ebo_create(&prm, &odometryCtx) != EBO_OK)
+			{
+				throw std::runtime_error(std::string("ebo_create: ") + ebo_last_error(nullptr));
+			}
+		}
+		{
+			std::unique_ptr<visual_odometry::VisualOdometryFrontEnd> frontEnd;
+			tools::Evaluator::KeyframeHook hook;
+			if (odometry)
+			{
+				frontEnd.reset(new visual_odometry::VisualOdometryFrontEnd(odometryCtx, recording->getCalibration(),
+																		   visual_odometry::VisualOdometryParams()));
+				hook = [&](const tracker::Patches& patches, const common::timestamp_t& t) {
+					visual_odometry::Keyframe keyframe(patches, t);
+					frontEnd->newKeyframeCandidate(keyframe);
+				};
+			}
+			tools::Evaluator evaluator(p, hook);
 			tools::Replayer replayer(recording);
 			evaluator.replay(replayer);
 			evaluator.finish();
@@ -93,14 +123,47 @@ int main(int argc, char** argv)
 			events = evaluator.events();
 			windows = evaluator.windows();
 			tracks = evaluator.detector().getArchivedPatches().size();
+			if (odometry)
+			{
+				FILE* f = std::fopen((out + "/keyframe_poses.txt").c_str(), "w");
+				if (!f)
+				{
+					throw std::runtime_error("cannot write " + out + "/keyframe_poses.txt");
+				}
+				const auto line = [&](const visual_odometry::Keyframe& kf) {
+					double m[12];
+					kf.pose.toArray(m);
+					std::fprintf(f, "%lld", static_cast<long long>(kf.timestamp.count()));
+					for (const double v : m)
+					{
+						std::fprintf(f, " %.17g", v);
+					}
+					std::fprintf(f, "\n");
+					++keyframes;
+				};
+				for (const auto& kf : frontEnd->getStoredFrames())
+				{
+					line(kf);
+				}
+				for (const auto& kf : frontEnd->getActiveFrames())
+				{
+					line(kf.second);
+				}
+				std::fclose(f);
+				landmarks = frontEnd->getMapLandmarks().landmarks.size() + frontEnd->getStoredLandmarks().size();
+			}
+		}
+		if (odometryCtx)
+		{
+			ebo_destroy(odometryCtx);
 		}
 		const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 		std::printf("{\"frames\": %zu, \"events\": %zu, \"tracks\": %zu, \"windows\": %zu, \"total_ms\": %.3f, "
 					"\"ms_per_frame_interval\": %.4f, \"mevents_per_s\": %.4f, \"tracker_experiment\": %s, "
-					"\"window_batch\": %zu, \"rectify\": %s}\n",
+					"\"window_batch\": %zu, \"rectify\": %s, \"odometry\": %s, \"keyframes\": %zu, \"landmarks\": %zu}\n",
 					frames, events, tracks, windows, ms, frames > 1 ? ms / static_cast<double>(frames - 1) : 0.0,
 					ms > 0 ? static_cast<double>(events) / (ms * 1e3) : 0.0, trackerExperiment ? "true" : "false",
-					windowBatch, rectify ? "true" : "false");
+					windowBatch, rectify ? "true" : "false", odometry ? "true" : "false", keyframes, landmarks);
 	}
 	catch (const std::exception& e)
 	{

@@ -895,6 +895,98 @@ int ebo_triangulate_device(ebo_ctx* ctx, int n_poses, const double* d_poses, int
 int ebo_epipolar_inliers(ebo_ctx* ctx, const double* model, int n, const double* f1, const double* f2, double threshold,
 						 uint8_t* flags);
 
+/* ---- absolute pose: three-point RANSAC on (bearing vector, landmark) pairs ----------------------------
+ * What VisualOdometryFrontEnd::localizeCamera (visual_odometry.cpp:212-286) does through OpenGV's
+ * AbsolutePoseSacProblem(KNEIP), stated as this project's own rules (OpenGV's source is not part of the reference
+ * tree, so parity with it is NOT claimed).  tests/abspose_ref.py restates every rule in numpy.  As in the two-view
+ * section: float64 throughout, one rounding per operation in exactly the association written here, no contraction,
+ * only + - * / sqrt and comparisons, fixed iteration counts; dot, cross, mix / hash, rotation and jacobi(M, sweeps)
+ * are the ones stated there.  A comparison with a NaN is false.
+ * A *pose* is (R, t), double [3][4] row-major = [R | t], taking camera coordinates to world coordinates
+ * (match.Tw2c as localizeCamera sets it); f[i] is the unit bearing vector of point i in the camera, p[i] its
+ * landmark in world coordinates.
+ *
+ * A1. score(pose, i):  d = p - t;  q_j = (R[0][j] * d0 + R[1][j] * d1) + R[2][j] * d2;  r = q / sqrt(dot(q, q));
+ *       score = 1 - dot(f, r).
+ *     Point i is an inlier when score < threshold; a NaN score is not an inlier.
+ * A2. Sampling.  Rule 3 with FOUR draws (d = 0 .. 3; `pair` = the frame's index in the call).  Points 1-3 of the
+ *     sample are solved, point 4 chooses among the candidates.
+ * A3. Minimal solve.  Indices 1, 2, 3 are the sample's first three points.
+ *       b12 = dot(f1, f2); b13 = dot(f1, f3); b23 = dot(f2, f3);  d12 = p1 - p2; d13 = p1 - p3; d23 = p2 - p3;
+ *       a12 = dot(d12, d12); a13 = dot(d13, d13); a23 = dot(d23, d23);  ww = cross(d12, d13).
+ *     NO MODEL unless dot(ww, ww) > 0 (collinear or coincident landmarks) and dot(f_i, f_i) > 0 for all FOUR bearing
+ *     vectors of the sample (a zero or NaN bearing).  The depths l_i (X_i = l_i f_i in the
+ *     camera) satisfy l_i^2 + l_j^2 - 2 b_ij l_i l_j = a_ij; eliminating the right-hand sides gives two homogeneous
+ *     conics in (l1, l2, l3), as symmetric matrices
+ *       D1 = [[a23, -(b12*a23), 0], [., a23 - a12, b23*a12], [., ., -a12]]
+ *       D2 = [[a23, 0, -(b13*a23)], [., -a13, b23*a13], [., ., a23 - a13]].
+ *     cof(M): C[i][j] = M[i+1][j+1] * M[i+2][j+2] - M[i+1][j+2] * M[i+2][j+1] (indices mod 3);
+ *             det(M) = dot(M[0][:], C[0][:]);   rows(A, B) = (dot(A[0], B[0]) + dot(A[1], B[1])) + dot(A[2], B[2]).
+ *     det(D1 + g D2) = c0 + c1 g + c2 g^2 + c3 g^3 with c0 = det(D1), c3 = det(D2), c1 = rows(cof(D1), D2),
+ *     c2 = rows(cof(D2), D1).  NO MODEL when c3 == 0.  b = c2 / c3, c = c1 / c3, d = c0 / c3;
+ *       P(x) = ((x + b) * x + c) * x + d;   P'(x) = ((3 * x) + (2 * b)) * x + c.
+ *     Start: q = b * b - 3 * c; v = sqrt(q); t1 = (-b - v) / 3; k1 = P(t1); t2 = (-b + v) / 3; k2 = P(t2);
+ *       when q > 0 and k1 > 0: x = t1 - sqrt(k1 / v)     (left of the local maximum, where P is concave and negative)
+ *       when q > 0 otherwise:  x = t2 + sqrt(|k2| / v)   (right of the local minimum, where P is convex and positive)
+ *       otherwise:             x = -b / 3                (the inflection point)
+ *     so that Newton's iteration is monotone from there.  THIRTY-TWO times: x = x - P(x) / P'(x), the iterate left
+ *     as it is when P'(x) == 0.  g = x.
+ *     D0 = D1 + g * D2 entry by entry; (e, V) = jacobi(D0, 8).  D0 has rank 2: the eigenvalue of smallest magnitude
+ *     is dropped (m = 0; m = 1 when |e1| < |e0|; m = 2 when |e2| < the smaller of those: the first of equals), the
+ *     other two, in index order, are (ea, va), (eb, vb).  NO MODEL unless (ea > 0 and eb < 0) or (ea < 0 and eb > 0).
+ *     s = sqrt((-eb) / ea).  D0 then splits into the two planes n = va - sg * vb, sg = +s and then -s.  For each:
+ *       dropped when n0 == 0;  w0 = (-n1) / n0;  w1 = (-n2) / n0                      (l1 = w0 l2 + w1 l3);
+ *       with tau = l3 / l2 the conic D1 becomes qa tau^2 + qb tau + qc = 0,
+ *         qa = a23 * (w1 * w1) - a12;
+ *         qb = a23 * ((2 * w0) * w1 - (2 * b12) * w1) + (2 * a12) * b23;
+ *         qc = a23 * ((w0 * w0 + 1) - (2 * b12) * w0) - a12;
+ *       dropped when qa == 0;  disc = qb * qb - (4 * qa) * qc;  dropped unless disc >= 0;
+ *       tau = ((-qb) + sqrt(disc)) / (2 * qa) and then ((-qb) - sqrt(disc)) / (2 * qa).  For each:
+ *         dropped unless tau > 0;  den = (1 + tau * tau) - (2 * b23) * tau;  dropped unless den > 0;
+ *         l2 = sqrt(a23 / den);  l3 = tau * l2;  l1 = w0 * l2 + w1 * l3;  dropped unless l1 > 0.
+ *         Polish, THREE Gauss-Newton steps on the distance equations:
+ *           r0 = ((l1*l1 + l2*l2) - ((2*b12) * l1) * l2) - a12;  r1 = ((l1*l1 + l3*l3) - ((2*b13) * l1) * l3) - a13;
+ *           r2 = ((l2*l2 + l3*l3) - ((2*b23) * l2) * l3) - a23;
+ *           J = [[2*l1 - (2*b12)*l2, 2*l2 - (2*b12)*l1, 0], [2*l1 - (2*b13)*l3, 0, 2*l3 - (2*b13)*l1],
+ *                [0, 2*l2 - (2*b23)*l3, 2*l3 - (2*b23)*l2]];  C = cof(J);  dj = det(J);
+ *           l_i = l_i - dot(C[:][i], r) / dj for i = 1, 2, 3 from the old values; a step with dj == 0 changes nothing.
+ *         X_i = l_i * f_i;  u = X1 - X2;  v = X1 - X3;  w = cross(u, v);  Bc = [u v w] (columns);  C = cof(Bc);
+ *         dc = det(Bc);  dropped when dc == 0;  inv[k][j] = C[j][k] / dc;
+ *         R[i][j] = dot((d12_i, d13_i, ww_i), inv[:][j]);   t_i = p1_i - dot(R[i][:], X1).
+ *     At most four candidates, in the order (+s, +sqrt) (+s, -sqrt) (-s, +sqrt) (-s, -sqrt).
+ *     The counts were settled the way rule 4's sweep counts were.
+ * A4. Disambiguation.  The model is the FIRST candidate with the smallest A1 score of the sample's fourth point; a
+ *     score that is not finite counts as +infinity.  With no candidate, or all scores infinite, the hypothesis has
+ *     no model, is written out as an all-zero [3][4] and has zero inliers.
+ * A5. Selection.  Rule 6 with w^4 (two squarings) in place of w^8.  FOUND when best >= 4.
+ *
+ * ebo_absolute_pose_ransac (replaces opengv::sac::Ransac::computeModel over AbsolutePoseSacProblem(KNEIP),
+ *   visual_odometry.cpp:236-250, for MANY keyframes in one call): the contract of ebo_relative_pose_ransac with
+ *   (f, points) in place of (f1, f2).  Frame k owns points offsets[k] .. offsets[k+1]-1 of f / points (double
+ *   [offsets[n_frames]][3]; offsets[0] = 0).  ALL n_frames x max_iterations hypotheses are sampled, solved (A2-A4)
+ *   and scored against every point of their frame (A1) on the device in one pass; the counts come back once, A5 runs
+ *   on the host, and one more launch lists the winners' inliers, ascending, as indices within the frame.  `model` of
+ *   the result is the camera-to-world pose.  A frame with fewer than 4 points is not found (winner -1, iterations 0),
+ *   not an error.  hyp_samples is int [n_frames][max_iterations][4].  A frame's result does not depend on the other
+ *   frames of the call.  The caller sets params->threshold (localizeCamera's is
+ *   (double)(float)(1 - cos(atan2(reprojectionError, 200)))); ebo_default_two_view_params' 5e-5 is the two-view one.
+ *   EBO_ERR_ARG and EBO_ERR_STATE as for ebo_relative_pose_ransac.  Synchronous.
+ * ebo_absolute_pose_scores: A1 for a GIVEN pose and n points: scores double [n] and / or inlier flags uint8 [n]
+ *   (either may be NULL).  The re-selection after a refinement (visual_odometry.cpp:262-264).
+ * The _device forms take device pointers for f and points (and, for scores, for the outputs); the scores form is
+ *   asynchronous on the context's stream.
+ * ebo_two_view_timing brackets ebo_absolute_pose_ransac too, with the same five slots. */
+int ebo_absolute_pose_ransac(ebo_ctx* ctx, int n_frames, const int* offsets, const double* f, const double* points,
+							 const ebo_two_view_params* params, ebo_two_view_result* result, int* inlier_idx,
+							 int* hyp_counts_or_null, double* hyp_models_or_null, int* hyp_samples_or_null);
+int ebo_absolute_pose_ransac_device(ebo_ctx* ctx, int n_frames, const int* offsets, const double* d_f, const double* d_points,
+									const ebo_two_view_params* params, ebo_two_view_result* result, int* inlier_idx,
+									int* hyp_counts_or_null, double* hyp_models_or_null, int* hyp_samples_or_null);
+int ebo_absolute_pose_scores(ebo_ctx* ctx, const double* pose, int n, const double* f, const double* points, double threshold,
+							 double* scores_or_null, uint8_t* inlier_flags_or_null);
+int ebo_absolute_pose_scores_device(ebo_ctx* ctx, const double* pose, int n, const double* d_f, const double* d_points,
+									double threshold, double* d_scores_or_null, uint8_t* d_inlier_flags_or_null);
+
 /* Device-side timing of everything enqueued between begin and end on the
  * context's stream (hipEvent based). */
 int ebo_timer_begin(ebo_ctx* ctx);
