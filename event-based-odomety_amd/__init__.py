@@ -111,6 +111,15 @@ class Summary(C.Structure):
     ]
 
 
+def default_ba_opts(**over):
+    """ebo_default_ba_opts (Ceres' Solver::Options defaults) as a SolverOpts; keyword arguments override fields."""
+    o = SolverOpts()
+    lib().ebo_default_ba_opts(C.addressof(o))
+    for k, v in over.items():
+        setattr(o, k, v)
+    return o
+
+
 class Camera(C.Structure):
     """ebo_camera: common::CameraModelParams<double>, in its field order."""
     _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "k3", "p1", "p2")]
@@ -200,6 +209,11 @@ def lib():
         _lib.ebo_relative_pose_scores_device.argtypes = _sc
         _lib.ebo_absolute_pose_ransac.argtypes = _tv
         _lib.ebo_absolute_pose_ransac_device.argtypes = _tv
+        _ba = [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ebo_bundle_adjust.argtypes = _ba
+        _lib.ebo_bundle_adjust_device.argtypes = _ba
+        _lib.ebo_default_ba_opts.argtypes = [C.c_void_p]
+        _lib.ebo_default_ba_opts.restype = None
         _lib.ebo_absolute_pose_scores.argtypes = _sc
         _lib.ebo_absolute_pose_scores_device.argtypes = _sc
         _tr = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1213,6 +1227,56 @@ class Context:
         p = lambda v: C.c_void_p(int(v)) if v else None
         self._check(lib().ebo_absolute_pose_scores_device(self._h, _vp(pose), int(n), p(d_f), p(d_points), C.c_double(threshold),
                                                           p(d_scores), p(d_flags)))
+
+    # -- bundle adjustment (Schur-complement LM over many windows) -------------------------------------
+    def bundle_adjust(self, problems, cam, huber, fix_points=False, opts=None, trace=False):
+        """ebo_bundle_adjust over a list of problems, each a dict of poses float64 [F][3][4] (camera to world), fixed
+        [F], points [P][3], of / op int [N] (frame and point of an observation, local indices) and uv [N][2].
+        -> list of dicts (poses, points, summary = dict of the ebo_summary fields, and with trace=True trace
+        [max_num_iterations + 1][4])."""
+        o = opts if opts is not None else default_ba_opts()
+        n = len(problems)
+
+        def cat(key, dt, shape):
+            parts = [np.asarray(p[key], dtype=dt).reshape(shape) for p in problems]
+            return np.ascontiguousarray(np.concatenate(parts), dtype=dt) if parts else np.zeros((0,) + tuple(shape[1:]), dt)
+
+        off = lambda key, div: np.ascontiguousarray(np.concatenate(
+            [[0], np.cumsum([np.asarray(p[key]).size // div for p in problems])]), dtype=np.int32)
+        fo, po, oo = off("poses", 12), off("points", 3), off("of", 1)
+        poses, fixed, points = cat("poses", np.float64, (-1, 12)), cat("fixed", np.uint8, (-1,)), cat("points", np.float64, (-1, 3))
+        of, op, uv = cat("of", np.int32, (-1,)), cat("op", np.int32, (-1,)), cat("uv", np.float64, (-1, 2))
+        summ = (Summary * max(n, 1))()
+        rows = int(o.max_num_iterations) + 1
+        tr = np.zeros((max(n, 1), max(rows, 1), 4)) if trace else None
+        cam = camera(cam)
+        self._check(lib().ebo_bundle_adjust(self._h, n, _vp(fo), _vp(po), _vp(oo), _vp(poses), _vp(fixed), _vp(points), _vp(of),
+                                            _vp(op), _vp(uv), C.addressof(cam), C.c_double(huber), 1 if fix_points else 0,
+                                            C.addressof(o), C.addressof(summ), _vp(tr) if trace else None))
+        out = []
+        for k in range(n):
+            s = summ[k]
+            d = dict(poses=poses[fo[k]:fo[k + 1]].reshape(-1, 3, 4).copy(), points=points[po[k]:po[k + 1]].copy(),
+                     summary={f: getattr(s, f) for f, _ in Summary._fields_})
+            if trace:
+                d["trace"] = tr[k].copy()
+            out.append(d)
+        return out
+
+    def bundle_adjust_device(self, frame_offsets, point_offsets, obs_offsets, d_poses, d_fixed, d_points, d_of, d_op, d_uv, cam,
+                             huber, fix_points=False, opts=None, d_trace=0):
+        """ebo_bundle_adjust_device: host int32 offsets, device pointers as int (observations already in (point, frame)
+        order); poses and points are updated in place on the device.  -> list of summary dicts."""
+        o = opts if opts is not None else default_ba_opts()
+        fo, po, oo = (np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (frame_offsets, point_offsets, obs_offsets))
+        n = len(fo) - 1
+        summ = (Summary * max(n, 1))()
+        cam = camera(cam)
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        self._check(lib().ebo_bundle_adjust_device(self._h, n, _vp(fo), _vp(po), _vp(oo), p(d_poses), p(d_fixed), p(d_points),
+                                                   p(d_of), p(d_op), p(d_uv), C.addressof(cam), C.c_double(huber),
+                                                   1 if fix_points else 0, C.addressof(o), C.addressof(summ), p(d_trace)))
+        return [{f: getattr(summ[k], f) for f, _ in Summary._fields_} for k in range(n)]
 
     def triangulate(self, poses, pose_pair, f1, f2):
         """ebo_triangulate: poses float64 [n_poses][3][4] camera-to-world, pose_pair int [n][2] -> world points [n][3]."""

@@ -9,6 +9,8 @@
 #include <stdint.h>
 
 #include <hip/hip_runtime.h>
+#include "../../include/ebo.h"
+#include "ebo_bundle.h"
 
 namespace ebo
 {
@@ -535,5 +537,28 @@ int launch_ap_winner_flags(int n_frames, int H, int max_n, const int* d_offsets,
 						   unsigned char* d_flags, double* d_win_models, void* stream);
 int launch_ap_scores(const double* pose, int n, const double* d_f, const double* d_points, double threshold, double* d_scores,
 					 unsigned char* d_flags, void* stream);
+
+// bundle adjustment (ebo_bundle.inc, ebo_bundle.cpp): where each problem's slices begin (sums of the sizes of the
+// problems before it, device arrays) and the call's device arrays
+struct BaTables
+{
+	const int* frameOff;
+	const int* pointOff;
+	const int* obsOff;
+	const long long* tableOff;
+	double* poses;
+	const unsigned char* fixed;
+	double* points;
+	const int* of;
+	const int* op;
+	const double* uv;
+	double* work;  // ba_work_doubles (ebo_bundle.h)
+	int* iwork;    // ba_work_ints
+	size_t totalF, totalP, totalN, totalTable;
+};
+// max_frames: frames of the problem that has most; the LDS of the reduced system is sized as if all of them were free
+// (the _device form cannot read the flags): up to 83.5 KB at 24 frames.  d_trace may be null
+int launch_bundle_adjust(int n_problems, int max_frames, const BaTables& t, const ebo_camera& cam, double huber, int fix_points,
+						 const ebo_solver_opts& o, ebo_summary* d_summaries, double* d_trace, void* stream);
 
 }  // namespace ebo

@@ -1269,6 +1269,7 @@ __global__ void __launch_bounds__(64) k_route(const uint32_t* __restrict__ xy, u
 #include "ebo_camera.inc"
 #include "ebo_twoview.inc"
 #include "ebo_abspose.inc"
+#include "ebo_bundle.inc"
 #include "ebo_field.inc"
 #include "ebo_fieldtv.inc"
 #include "ebo_optimizer.inc"
@@ -1953,6 +1954,24 @@ int launch_ap_scores(const double* pose, int n, const double* d_f, const double*
 	std::copy(pose, pose + 12, m.m);
 	hipLaunchKernelGGL(k_ap_scores, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), m, n, d_f, d_points,
 					   threshold, d_scores, d_flags);
+	return check_launch();
+}
+
+// bundle adjustment (ebo_bundle.inc)
+int launch_bundle_adjust(int n_problems, int max_frames, const BaTables& t, const ebo_camera& cam, double huber, int fix_points,
+						 const ebo_solver_opts& o, ebo_summary* d_summaries, double* d_trace, void* stream)
+{
+	if (n_problems <= 0)
+	{
+		return 0;
+	}
+	const size_t lds = sizeof(double) * (ba_reduced_doubles(max_frames) + 1);
+	if (allow_big_lds(k_bundle_adjust, lds + 8 * 1024))
+	{
+		return -2;
+	}
+	hipLaunchKernelGGL(k_bundle_adjust, dim3(n_problems), dim3(kBaLanes), lds, static_cast<hipStream_t>(stream), t, cam, huber,
+					   fix_points, o, d_summaries, d_trace);
 	return check_launch();
 }
 

@@ -16,7 +16,10 @@
 //     is not claimed;
 //   * where the reference calls opengv::absolute_pose::optimize_nonlinear the caller may plug a refinement in
 //     (setLocalizeRefinement); there is none by default and the RANSAC pose is used as it is;
+//     useDeviceLocalizeRefinement() installs ebo_bundle_adjust with the points held constant (bundle_adjustment.h);
 //   * optimize() is a hook (setOptimizer), called where the reference calls it; there is none by default;
+//     useDeviceBundleAdjustment() installs ebo_bundle_adjust (include/ebo.h "bundle adjustment", B1-B9), this
+//     project's own statement of the windowed problem: parity with Ceres is not claimed;
 //   * addNewLandmarks triangulates all tracks whose observation list has just reached two in ONE ebo_triangulate
 //     call, after the loop over the inliers (nothing in that loop reads a landmark);
 //   * deleteLandmarks moves the landmarks whose last observation went to storedLandmarks_ in ascending track id (the
@@ -29,6 +32,7 @@
 #include <map>
 #include <utility>
 
+#include "bundle_adjustment.h"
 #include "two_view.h"
 
 namespace visual_odometry
@@ -44,15 +48,37 @@ class VisualOdometryFrontEnd
 
 	VisualOdometryFrontEnd(ebo_ctx* ctx, const common::CameraModelParams<double>& calibration, const VisualOdometryParams& params,
 						   uint64_t seed = 0)
-		: ctx_(ctx), cameraModel_(calibration), params_(params), twoView_(ctx, calibration, params, seed)
+		: ctx_(ctx), calibration_(calibration), cameraModel_(calibration), params_(params), twoView_(ctx, calibration, params, seed)
 	{
 		ebo_default_two_view_params(&ransac_);
 		ransac_.threshold = localizeThreshold();
 		ransac_.seed = seed;
 	}
 
+	// the hooks that the two use... members install hold this object's address: it is neither copied nor moved
+	VisualOdometryFrontEnd(const VisualOdometryFrontEnd&) = delete;
+	VisualOdometryFrontEnd& operator=(const VisualOdometryFrontEnd&) = delete;
+
 	void setLocalizeRefinement(LocalizeRefinement refinement) { localizeRefinement_ = std::move(refinement); }
 	void setOptimizer(Optimizer optimizer) { optimizer_ = std::move(optimizer); }
+	// optimize() (visual_odometry.cpp:416-497) on the device: HuberLoss(params.huberLoss), params.maxNumIterations, the
+	// first two active frames constant; lastBundleAdjustment() is its summary
+	void useDeviceBundleAdjustment()
+	{
+		optimizer_ = [this](std::map<size_t, Keyframe>& active, MapLandmarks& map) {
+			lastBundle_ = bundleAdjust(ctx_, calibration_, params_.huberLoss, params_.maxNumIterations, active, map);
+		};
+	}
+	// the refinement after localizeCamera's RANSAC (:262) on the device, over the RANSAC inliers
+	void useDeviceLocalizeRefinement()
+	{
+		localizeRefinement_ = [this](const common::Pose3d& pose, const bearingVectors_t& f, const std::vector<common::Vector3d>& points,
+									 const std::vector<int>& inliers) {
+			return refinePose(ctx_, params_.huberLoss, params_.maxNumIterations, pose, f, points, inliers, &lastRefinement_);
+		};
+	}
+	const ebo_summary& lastBundleAdjustment() const { return lastBundle_; }
+	const ebo_summary& lastRefinement() const { return lastRefinement_; }
 	// the two-view layer that initCameras goes through (its refinement and RANSAC parameters are set there)
 	TwoViewInitializer& twoView() { return twoView_; }
 	// max_iterations, probability and seed of localizeCamera's RANSAC; the threshold follows reprojectionError
@@ -313,6 +339,7 @@ class VisualOdometryFrontEnd
 
    private:
 	ebo_ctx* ctx_;
+	common::CameraModelParams<double> calibration_;
 	common::CameraModel<double> cameraModel_;
 	VisualOdometryParams params_;
 	TwoViewInitializer twoView_;
@@ -320,6 +347,8 @@ class VisualOdometryFrontEnd
 	ebo_two_view_result last_{};
 	LocalizeRefinement localizeRefinement_;
 	Optimizer optimizer_;
+	ebo_summary lastBundle_{};
+	ebo_summary lastRefinement_{};
 
 	std::map<size_t, Keyframe> activeFrames_;
 	std::list<Keyframe> storedFrames_;

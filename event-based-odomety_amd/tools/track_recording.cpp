@@ -1,6 +1,6 @@
 // track_recording — the reference's feature-tracking experiment on a DAVIS240C recording directory, without OpenCV:
 //
-//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--odometry]
+//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--odometry [--bundle-adjust] [--refine]]
 //
 // DIR holds events.txt, images.txt + the frames (8-bit grey PNG), optionally groundtruth.txt / calib.txt.
 // --rectify: the events of every compensation window are undistorted with the recording's calib.txt as they are
@@ -10,6 +10,9 @@
 // --odometry: visual_odometry::VisualOdometryFrontEnd (visual_odometry/visual_odometry.h) runs as the keyframe hook on a
 // context of its own and OUT/keyframe_poses.txt gets one line per keyframe, stored ones first: the timestamp and the
 // camera-to-world pose [R | t] row by row (the first keyframe is the world frame, the first baseline the unit of length).
+// --bundle-adjust, --refine (both need --odometry): the front end's optimize() after every added keyframe and the
+// refinement after localizeCamera's RANSAC, both through ebo_bundle_adjust (useDeviceBundleAdjustment,
+// useDeviceLocalizeRefinement).
 // Writes OUT/trajectory.txt and OUT/final_cost.txt and prints one JSON line: frames, events, tracks (archived patches),
 // compensation windows, total ms (construction to the files written), ms per frame interval and Mevents/s.
 // Built by `make -C event-based-odomety_amd/csrc track_recording`.
@@ -26,7 +29,7 @@
 
 static int usage(const char* argv0)
 {
-	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--odometry]\n", argv0);
+	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--odometry [--bundle-adjust] [--refine]]\n", argv0);
 	return 2;
 }
 
@@ -36,7 +39,7 @@ int main(int argc, char** argv)
 	bool trackerExperiment = false;
 	size_t windowBatch = 1;
 	bool rectify = false;
-	bool odometry = false;
+	bool odometry = false, bundleAdjust = false, refine = false;
 	for (int i = 1; i < argc; ++i)
 	{
 		const std::string a = argv[i];
@@ -60,6 +63,14 @@ int main(int argc, char** argv)
 		{
 			odometry = true;
 		}
+		else if (a == "--bundle-adjust")
+		{
+			bundleAdjust = true;
+		}
+		else if (a == "--refine")
+		{
+			refine = true;
+		}
 		else if (a == "--window-batch" && i + 1 < argc)
 		{
 			char* end = nullptr;
@@ -75,7 +86,7 @@ int main(int argc, char** argv)
 			return usage(argv[0]);
 		}
 	}
-	if (dataset.empty() || out.empty())
+	if (dataset.empty() || out.empty() || ((bundleAdjust || refine) && !odometry))
 	{
 		return usage(argv[0]);
 	}
@@ -110,6 +121,14 @@ int main(int argc, char** argv)
 			{
 				frontEnd.reset(new visual_odometry::VisualOdometryFrontEnd(odometryCtx, recording->getCalibration(),
 																		   visual_odometry::VisualOdometryParams()));
+				if (bundleAdjust)
+				{
+					frontEnd->useDeviceBundleAdjustment();
+				}
+				if (refine)
+				{
+					frontEnd->useDeviceLocalizeRefinement();
+				}
 				hook = [&](const tracker::Patches& patches, const common::timestamp_t& t) {
 					visual_odometry::Keyframe keyframe(patches, t);
 					frontEnd->newKeyframeCandidate(keyframe);

@@ -987,6 +987,112 @@ int ebo_absolute_pose_scores(ebo_ctx* ctx, const double* pose, int n, const doub
 int ebo_absolute_pose_scores_device(ebo_ctx* ctx, const double* pose, int n, const double* d_f, const double* d_points,
 									double threshold, double* d_scores_or_null, uint8_t* d_inlier_flags_or_null);
 
+/* ---- bundle adjustment: windowed Levenberg-Marquardt with a Schur complement ----------------------------
+ * What VisualOdometryFrontEnd::optimize (visual_odometry.cpp:416-497) does through Ceres on reprojection_error.h and
+ * local_parameterization_se3.hpp, and with the points held constant the refinement after localizeCamera's RANSAC
+ * (:262), stated as this project's own rules for MANY small problems in one call.  Parity with Ceres, Sophus or Eigen
+ * is NOT claimed (INTEGRATION.md 7 lists the differences).  tests/bundle_ref.py restates every rule in numpy.  The
+ * conventions are those of "absolute pose": float64, one rounding per operation in the association written here, no
+ * contraction, only + - * / sqrt and comparisons, a comparison with a NaN is false.  dot is the two-view section's;
+ * dot6(a, b) = ((((a0*b0 + a1*b1) + a2*b2) + a3*b3) + a4*b4) + a5*b5.
+ * A problem is F frames, P points and N observations (frame, point, u, v).  A pose T = [R | t] is double [3][4],
+ * camera to world (Tw2c); a frame whose `fixed` flag is set is constant; the camera is constant.  Unless fix_points
+ * is set, a point with fewer than two observations takes no part (the size() < 2 skip of :445): its observations
+ * are dropped and it comes back unchanged.  With fix_points every point is constant and every observation takes part.
+ * The variables are 6 per free frame (ups, om) and 3 per point that takes part.
+ *
+ * B1. Residual.  d = X - t;  q_j = (R[0][j] * d0 + R[1][j] * d1) + R[2][j] * d2;  (uh, vh) = project(q) of the camera
+ *     section;  r = (u - uh, v - vh).
+ * B2. Loss (ceres::HuberLoss(a) with the corrector for rho'' <= 0, as host_lm.cpp has it).  s = r0 * r0 + r1 * r1;
+ *     b = a * a;  when s > b: root = sqrt(s); rho = (2 * a) * root - b; rho' = max(DBL_MIN, a / root);  otherwise
+ *     rho = s, rho' = 1.  sr = sqrt(rho');  rt = (r0 * sr, r1 * sr) is the corrected residual.
+ * B3. Jacobian.  With xP, yP, r2, rad of project:  dr = k1 + (2 * k2) * r2;
+ *       dxx = ((rad + ((2 * xP) * xP) * dr) + (2 * p1) * yP) + (6 * p2) * xP;
+ *       dxy = ((((2 * xP) * yP) * dr) + (2 * p1) * xP) + (2 * p2) * yP;
+ *       dyy = ((rad + ((2 * yP) * yP) * dr) + (2 * p2) * xP) + (6 * p1) * yP;      iz = 1 / q2;
+ *       A[0] = (fx * (dxx * iz), fx * (dxy * iz), fx * (-((dxx * xP + dxy * yP) * iz))) * sr    (each entry times sr)
+ *       A[1] = (fy * (dxy * iz), fy * (dyy * iz), fy * (-((dxy * xP + dyy * yP) * iz))) * sr
+ *     (A = sr d(project)/dq; k3 unused as in the model.)  With dq/dups = -I, dq/dom = hat(q), dq/dX = R^T, row k of
+ *       Jc = (A[k][0], A[k][1], A[k][2], A[k][2]*q1 - A[k][1]*q2, A[k][0]*q2 - A[k][2]*q0, A[k][1]*q0 - A[k][0]*q1)
+ *       Jp = (-dot(A[k], R[0][:]), -dot(A[k], R[1][:]), -dot(A[k], R[2][:]))
+ *     and every entry is then multiplied by the scale of its column (B6).
+ * B4. Update, on the right as LocalParameterizationSE3::Plus does, without sin / cos:  h = om * 0.5;
+ *       n = sqrt(1 + ((hx*hx + hy*hy) + hz*hz));  (x, y, z, w) = (hx / n, hy / n, hz / n, 1 / n);  C = the matrix of
+ *       that quaternion by common::Pose3d's formula (x2 = 2 * x, ..; twx = x2 * w, ..; txx = x2 * x, txy = y2 * x,
+ *       txz = z2 * x, tyy = y2 * y, tyz = z2 * y, tzz = z2 * z; C = [[1 - (tyy + tzz), txy - twz, txz + twy],
+ *       [txy + twz, 1 - (txx + tzz), tyz - twx], [txz - twy, tyz + twx, 1 - (txx + tyy)]]);
+ *       R'[i][j] = dot(R[i][:], C[:][j]);  t'_i = t_i + dot(R[i][:], ups).   A point: X' = X + step.
+ *     Every step entry is first multiplied by its column's scale.  No re-orthonormalisation.
+ * B5. Sums.  Observations are in (point, frame) order, no pair twice.  With J0, J1 the two rows of an observation:
+ *       U_k[a][b] = sum of (J0c[a] * J0c[b] + J1c[a] * J1c[b]),  g_k[a] = sum of (J0c[a] * rt0 + J1c[a] * rt1)
+ *         over the observations of free frame k in ascending point order, from 0;
+ *       V_l[a][b], g_l[a] the same with Jp over the observations of point l in ascending frame order (ALL its frames);
+ *       W_o[a][b] = J0c[a] * J0p[b] + J1c[a] * J1p[b] for an observation o of a free frame.
+ * B6. Column scaling (Ceres' Jacobi scaling; opts->jacobi_scaling): scale_c = 1 / (1 + sqrt(n_c)), n_c = the diagonal
+ *     entry of U_k / V_l computed at the start with all scales 1; fixed for the solve.
+ * B7. Damping and point blocks.  damp(d) = l * l with l = sqrt(min(max(d, min_lm_diagonal), max_lm_diagonal) / radius),
+ *     added to every diagonal entry d of U_k and V_l.  inv(V_l)[i][j] = C[j][i] / det with cof / det of A3; a
+ *     determinant that is not > 0 makes the step invalid.  Y_o[a][b] = dot(W_o[a][:], inv(V_l)[:][b]).
+ * B8. Reduced system over the free frames in ascending order, 6 rows each:  for rows (j, a), (k, b):
+ *       S = (U_k[a][b] with its damping when j = k, otherwise 0), then minus dot(Y_oj[a][:], W_ok[b][:]) for every point
+ *       l seen by both, in ascending l;   rhs = g_k[a], then minus dot(Y_ok[a][:], g_l) in ascending l.
+ *     Cholesky S = L L^T, lower, column by column: every entry loses its products L[i][k] * L[j][k] one at a time in
+ *     ascending k, then is divided by the pivot's square root; a pivot that is not > 0 or not finite makes the step
+ *     invalid.  L y = rhs: y_k = rhs_k / L[k][k], then rhs_i = rhs_i - L[i][k] * y_k for i > k, k ascending.
+ *     L^T x = y: x_k = y_k / L[k][k], then y_i = y_i - L[k][i] * x_k for i < k, k DEscending.  Points:
+ *       e[b] = g_l[b], then minus dot6(W_o[:][b], x_k) over the point's observations in free frames, ascending;
+ *       x_l[a] = dot(inv(V_l)[a][:], e).    step = -x; an entry that is not finite makes the step invalid.
+ *     With fix_points there are no point blocks: S is the damped U_k on its diagonal blocks, rhs = g_k.
+ * B9. Trust region: TrustRegionMinimizer + LevenbergMarquardtStrategy as HostLm (csrc/host_lm.cpp) restates them.
+ *     tree(v): 256 partial sums, partial i = v[i] + v[i + 256] + .. in that order from 0; then for s = 128, 64, .., 1:
+ *     partial[i] = partial[i] + partial[i + s] for i < s; the result is partial[0].
+ *       cost = 0.5 * tree(rho over the observations);
+ *       model cost change = -tree(m), m = mr0 * (rt0 + mr0 / 2) + mr1 * (rt1 + mr1 / 2),
+ *         mr_k = dot6(Jc row k, step of the frame) (0 for a fixed frame) + dot(Jp row k, step of the point) (0 with fix_points);
+ *         a change that is not > 0 makes the step invalid;
+ *       |x| = sqrt(tree(squares of the 12 pose entries of every free frame and the 3 of every point that takes part, in
+ *         array order, 0 for the others)), the step norm the same of (x - candidate);
+ *       gradient norm = max over the variables of |g_c / scale_c| (0 when there is none).
+ *     An invalid step: radius = radius * 0.5, and termination 2 after max_consecutive_invalid in a row.  A candidate
+ *     whose cost is not finite counts as DBL_MAX (a rejected step).  Then, in this order: converged when
+ *     step norm <= parameter_tolerance * (|x| + parameter_tolerance); converged when
+ *     |cost - candidate cost| <= function_tolerance * cost (the candidate is not taken); quality, acceptance
+ *     (quality > min_relative_decrease), radius = min(max_radius, radius / max(1/3, 1 - (2q - 1)^3)) with
+ *     (2q - 1)^3 = (c * c) * c, rejection radius = radius / decrease, decrease = decrease * 2, and the non-monotonic
+ *     bookkeeping exactly as HostLm::supply.  Before each iteration: termination 1 at max_num_iterations, converged
+ *     when the last step was taken and gradient norm <= gradient_tolerance, converged when radius < min_radius.
+ *     The result is the lowest-cost point visited.  A cost that is not finite at the start is termination 2 with
+ *     poses and points returned bit for bit.
+ *
+ * ebo_bundle_adjust: problem p owns frames frame_offsets[p] .. frame_offsets[p+1]-1 of poses ([.][3][4]) and
+ *   pose_fixed, points point_offsets[p] .. of points ([.][3]) and observations obs_offsets[p] .. of obs_frame,
+ *   obs_point (indices LOCAL to the problem) and obs_uv ([.][2]); all offsets start at 0.  Observations may come in
+ *   any order; the entry sorts them.  poses and points are updated in place with the solver's best point; one
+ *   ebo_summary per problem (num_evals_jac counts Jacobian evaluations, num_evals_cost candidate evaluations).
+ *   trace_or_null: double [n_problems][opts->max_num_iterations + 1][4] = (cost, radius after the iteration, step
+ *   quality, flag) per iteration, row 0 the start; flag 1 taken, 0 rejected, -1 invalid step, 2 converged at this
+ *   candidate; rows never reached are 0.  fix_points non-zero holds every point constant: one 6 x 6 system per free
+ *   frame, the pose refinement.  opts as ebo_default_ba_opts fills them (Ceres' Solver::Options defaults, which the
+ *   reference leaves untouched at :488-491); opts->mode is not read.
+ *   Limits per problem: 24 frames, 4096 points, 65535 observations; 65535 problems.  EBO_ERR_ARG beyond them and for
+ *   an index out of range, a (frame, point) pair observed twice, offsets that decrease or do not start at 0, huber not
+ *   positive (or NaN), a negative max_num_iterations, a needed pointer NULL.  EBO_ERR_STATE while a graph is being
+ *   recorded.  A problem's result depends neither on the other problems of the call nor on the run.  Synchronous.
+ * ebo_bundle_adjust_device: device pointers for every array except the offsets, cam, opts and summaries.  It cannot
+ *   look at the indices: observations must already be in (point, frame) order with indices in range and no pair
+ *   twice; a problem for which that does not hold is not solved (termination 2, its poses and points untouched).
+ * ebo_two_view_timing brackets both: slot [0] the kernel, [4] the whole call, the others 0. */
+void ebo_default_ba_opts(ebo_solver_opts* opts);
+int ebo_bundle_adjust(ebo_ctx* ctx, int n_problems, const int* frame_offsets, const int* point_offsets, const int* obs_offsets,
+					  double* poses, const uint8_t* pose_fixed, double* points, const int* obs_frame, const int* obs_point,
+					  const double* obs_uv, const ebo_camera* cam, double huber, int fix_points, const ebo_solver_opts* opts,
+					  ebo_summary* summaries, double* trace_or_null);
+int ebo_bundle_adjust_device(ebo_ctx* ctx, int n_problems, const int* frame_offsets, const int* point_offsets,
+							 const int* obs_offsets, double* d_poses, const uint8_t* d_pose_fixed, double* d_points,
+							 const int* d_obs_frame, const int* d_obs_point, const double* d_obs_uv, const ebo_camera* cam,
+							 double huber, int fix_points, const ebo_solver_opts* opts, ebo_summary* summaries,
+							 double* d_trace_or_null);
+
 /* Device-side timing of everything enqueued between begin and end on the
  * context's stream (hipEvent based). */
 int ebo_timer_begin(ebo_ctx* ctx);
