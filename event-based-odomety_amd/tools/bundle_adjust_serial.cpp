@@ -7,8 +7,10 @@
 //   bundle_adjust_serial <problem.f64> <result.f64> <repeats>
 //       problem.f64, raw float64: F, P, N, fix_points, max_num_iterations, use_nonmonotonic, function_tolerance,
 //         gradient_tolerance, parameter_tolerance, huber, camera (fx fy cx cy k1 k2 k3 p1 p2), poses [F][12], fixed [F],
-//         points [P][3], frame [N], point [N], uv [N][2]; observations in (point, frame) order.  The other options are
-//         ebo_default_ba_opts'.
+//         points [P][3], frame [N], point [N], uv [N][2]; observations in (point, frame) order.  Then the rest of
+//         ebo_solver_opts in its order: initial_radius, max_radius, min_radius, min_relative_decrease, min_lm_diagonal,
+//         max_lm_diagonal, max_consecutive_nonmonotonic, max_consecutive_invalid, jacobi_scaling.  A file that ends
+//         after uv takes ebo_default_ba_opts' for these nine; mode, which the solve never reads, is never carried.
 //       result.f64: iterations, num_evals_cost, num_evals_jac, termination, initial_cost, final_cost, poses, points,
 //         trace [max_num_iterations + 1][4].  Prints one JSON line with the median milliseconds of `repeats` solves.
 #include <algorithm>
@@ -57,14 +59,15 @@ int main(int argc, char** argv)
 	}
 	const std::vector<double> in = readAll(argv[1]);
 	const int repeats = std::atoi(argv[3]);
-	if (in.size() < 19 || repeats < 1)
+	constexpr size_t kHead = 19, kTail = 9;
+	if (in.size() < kHead || repeats < 1)
 	{
 		std::fprintf(stderr, "short problem file or no repeats\n");
 		return 2;
 	}
 	const int F = static_cast<int>(in[0]), P = static_cast<int>(in[1]), N = static_cast<int>(in[2]);
-	if (F < 0 || F > kBaMaxFrames || P < 0 || P > kBaMaxPoints || N < 0 || N > kBaMaxObs ||
-		in.size() != 19 + 13 * static_cast<size_t>(F) + 3 * static_cast<size_t>(P) + 4 * static_cast<size_t>(N))
+	const size_t upToUv = kHead + 13 * static_cast<size_t>(F) + 3 * static_cast<size_t>(P) + 4 * static_cast<size_t>(N);
+	if (F < 0 || F > kBaMaxFrames || P < 0 || P > kBaMaxPoints || N < 0 || N > kBaMaxObs || (in.size() != upToUv && in.size() != upToUv + kTail))
 	{
 		std::fprintf(stderr, "sizes over the limits or not those of the file\n");
 		return 2;
@@ -76,11 +79,29 @@ int main(int argc, char** argv)
 	o.function_tolerance = in[6];
 	o.gradient_tolerance = in[7];
 	o.parameter_tolerance = in[8];
+	if (in.size() == upToUv + kTail)
+	{
+		const double* t = in.data() + upToUv;
+		o.initial_radius = t[0];
+		o.max_radius = t[1];
+		o.min_radius = t[2];
+		o.min_relative_decrease = t[3];
+		o.min_lm_diagonal = t[4];
+		o.max_lm_diagonal = t[5];
+		o.max_consecutive_nonmonotonic = static_cast<int>(t[6]);
+		o.max_consecutive_invalid = static_cast<int>(t[7]);
+		o.jacobi_scaling = static_cast<int>(t[8]);
+	}
 	const double huber = in[9];
 	ebo_camera cam;
 	cam.fx = in[10], cam.fy = in[11], cam.cx = in[12], cam.cy = in[13], cam.k1 = in[14], cam.k2 = in[15], cam.k3 = in[16], cam.p1 = in[17],
 	cam.p2 = in[18];
-	const double* at = in.data() + 19;
+	if (o.max_num_iterations < 0)
+	{
+		std::fprintf(stderr, "a negative iteration count\n");
+		return 2;
+	}
+	const double* at = in.data() + kHead;
 	const std::vector<double> poses0(at, at + 12 * F);
 	at += 12 * F;
 	std::vector<unsigned char> fixed(F);

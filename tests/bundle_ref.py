@@ -171,6 +171,8 @@ class Solver:
         self.scale = np.ones(6 * self.F + 3 * self.P)
         # what the guard of tests/test_bundle_cpu.py looks at: every step quality, and both sides of every convergence test
         self.qualities, self.checks = [], []
+        self.exit_checks = []    # (value, threshold) of every gradient_tolerance and min_radius test taken
+        self.failed_pivots = []  # the pivot every factorisation that broke off stopped at
         self.pfree = np.concatenate([np.repeat(self.free, 6), np.repeat(self.active & (not self.fix), 3)])
         self.mask12 = np.concatenate([np.repeat(self.free, 12), np.repeat(self.active & (not self.fix), 3)])
 
@@ -309,6 +311,7 @@ class Solver:
                 d = L[k, k]
                 if not (d > 0.0 and finite(d)):
                     invalid = True
+                    self.failed_pivots.append(float(d))
                     break
                 L[k, k] = np.sqrt(d)
                 L[k + 1:, k] = L[k + 1:, k] / L[k, k]
@@ -414,7 +417,8 @@ class Solver:
         def done(term):
             st["termination"] = term
             st["final_cost"] = min_cost
-            return dict(poses=best_pose.reshape(-1, 3, 4), points=best_pt, summary=st, trace=trace)
+            return dict(poses=best_pose.reshape(-1, 3, 4), points=best_pt, summary=st, trace=trace,
+                        last_poses=x_pose.reshape(-1, 3, 4), last_points=x_pt)  # last_*: the iterate the solve stopped at
 
         if not finite(x_cost):
             return done(2)
@@ -435,8 +439,11 @@ class Solver:
                 best_pose, best_pt = x_pose.copy(), x_pt.copy()
             if st["iterations"] >= max_it:
                 return done(1)
+            if last_successful:
+                self.exit_checks.append((grad_max, o["gradient_tolerance"]))
             if last_successful and grad_max <= o["gradient_tolerance"]:
                 return done(0)
+            self.exit_checks.append((radius, o["min_radius"]))
             if radius < o["min_radius"]:
                 return done(0)
             st["iterations"] += 1
@@ -520,14 +527,24 @@ def solve(problem, huber, fix_points=False, opts=None, reverse_sums=False):
     return out
 
 
+# the option fields of the problem file: five in its head, the rest of ebo_solver_opts in its order at its end (mode, which
+# the bundle adjustment never reads, is not carried)
+HEAD_OPTS = ("max_num_iterations", "use_nonmonotonic", "function_tolerance", "gradient_tolerance", "parameter_tolerance")
+TAIL_OPTS = ("initial_radius", "max_radius", "min_radius", "min_relative_decrease", "min_lm_diagonal", "max_lm_diagonal",
+             "max_consecutive_nonmonotonic", "max_consecutive_invalid", "jacobi_scaling")
+
+
 def write_problem(path, pr, huber, fix_points, opts):
-    """The problem file of tools/bundle_adjust_serial.cpp and tests/cpp/bundle_lines_test.cpp: raw float64, observations
-    sorted by (point, frame)."""
+    """The problem file of tools/bundle_adjust_serial.cpp and tests/cpp/bundle_lines_test.cpp: raw float64, a head of 19
+    (F, P, N, fix_points, the five HEAD_OPTS, huber, the camera's nine), the arrays with the observations sorted by
+    (point, frame), then the nine TAIL_OPTS: every field of opts reaches the reader.  The tail comes last so that a
+    reader of the arrays alone, and a file written without it (the defaults then), stay valid."""
     of, op, uv = sort_observations(len(pr["poses"]), pr["of"], pr["op"], pr["uv"])
-    head = [len(pr["poses"]), len(pr["points"]), len(of), int(fix_points), opts["max_num_iterations"], opts["use_nonmonotonic"],
-            opts["function_tolerance"], opts["gradient_tolerance"], opts["parameter_tolerance"], huber, *pr["cam"]]
+    assert set(opts) == set(HEAD_OPTS + TAIL_OPTS), sorted(opts)
+    head = [len(pr["poses"]), len(pr["points"]), len(of), int(fix_points), *[opts[k] for k in HEAD_OPTS], huber, *pr["cam"]]
     np.concatenate([np.array(head, float), np.asarray(pr["poses"], float).reshape(-1), np.asarray(pr["fixed"], float),
-                    np.asarray(pr["points"], float).reshape(-1), of.astype(float), op.astype(float), uv.reshape(-1)]).tofile(str(path))
+                    np.asarray(pr["points"], float).reshape(-1), of.astype(float), op.astype(float), uv.reshape(-1),
+                    np.array([opts[k] for k in TAIL_OPTS], float)]).tofile(str(path))
 
 
 # ---- scenes ----------------------------------------------------------------------------------------------------------
@@ -654,3 +671,45 @@ def test_scenes():
 
 
 test_scenes.__test__ = False
+
+
+def big_scene():
+    """A problem at both limits: 16 frames, 4096 points each seen by all 16, one observation dropped: 65535."""
+    s = scene(33, 16, 4096, views=(16, 16), noise=0.3)
+    for k in ("of", "op", "uv"):
+        s[k] = s[k][:-1]
+    return s
+
+
+def branch_scenes():
+    """name -> (problem, fix_points, opts): the scenes of tests/test_gpu_bundle_branches.py, one per branch of B9 that
+    test_scenes() never takes and per option it never varies (the table in that module's header; what each must show is
+    asserted by test_bundle_cpu.py::test_the_branch_scenes_take_their_branches)."""
+    a = scene(1, 3, 4)
+    noisy = scene(22, 4, 30, noise=0.3, outliers=0.1, perturb_pose=0.2, perturb_pt=0.8)
+    far = scene(23, 3, 12, perturb_pose=0.3, perturb_pt=1.5)
+    wild = scene(68, 3, 12, perturb_pose=0.3, perturb_pt=1.5)
+    d = default_opts
+    return {
+        "rej": (noisy, False, d()),
+        "rej_mrd": (noisy, False, d(min_relative_decrease=0.5)),
+        "rej4": (far, False, d(initial_radius=1e16)),
+        "nonmono": (far, False, d(initial_radius=1e16, use_nonmonotonic=1)),
+        "nonmono_cut": (far, False, d(initial_radius=1e16, use_nonmonotonic=1, max_num_iterations=8)),
+        "nonmono_m5": (wild, False, d(initial_radius=1e16, use_nonmonotonic=1)),
+        "nonmono_m2": (wild, False, d(initial_radius=1e16, use_nonmonotonic=1, max_consecutive_nonmonotonic=2)),
+        "invalid": (edge_scene(), False, d(min_lm_diagonal=0.0)),
+        "invalid3": (edge_scene(), False, d(min_lm_diagonal=0.0, max_consecutive_invalid=3)),
+        "minrad": (a, False, d(initial_radius=1e-33)),
+        "gtol": (a, False, d(function_tolerance=0.0, parameter_tolerance=0.0, gradient_tolerance=1e-6)),
+        "ptol": (a, False, d(function_tolerance=0.0, gradient_tolerance=0.0)),
+        "ptol4": (a, False, d(function_tolerance=0.0, gradient_tolerance=0.0, parameter_tolerance=1e-4)),
+        "maxrad": (a, False, d(max_radius=2e4, function_tolerance=0.0)),
+        "lmclip": (a, False, d(min_lm_diagonal=0.1, max_lm_diagonal=0.1, initial_radius=1.0)),
+        "noscale": (a, False, d(jacobi_scaling=0)),
+        "noscale_clip": (a, False, d(jacobi_scaling=0, min_lm_diagonal=0.1, max_lm_diagonal=0.1, initial_radius=1.0)),
+        "ftol3": (noisy, False, d(function_tolerance=1e-3)),
+        "fix24": (scene(31, 24, 60, n_fixed=0, views=(3, 24), noise=0.3, perturb_pose=0.03, perturb_pt=0.0), True, d()),
+        "dense24": (scene(32, 24, 30, noise=0.3), False, d()),
+        "big": (big_scene(), False, d(max_num_iterations=2)),
+    }

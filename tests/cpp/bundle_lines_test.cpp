@@ -2,7 +2,8 @@
 // two use... members of VisualOdometryFrontEnd), pinned by signature and run on a window handed over in a file.
 //
 //   bundle_lines_test adjust <problem.f64> <out.f64>
-//       problem.f64 is tools/bundle_adjust_serial.cpp's (fix_points 0): frame k becomes the active keyframe with
+//       problem.f64 is tools/bundle_adjust_serial.cpp's (fix_points 0; the options that follow uv are not read: of
+//       the options the façade takes the iteration count alone): frame k becomes the active keyframe with
 //       timestamp 1000 (k + 1) holding a patch per observation (track id 3 l + 5 for point l), point l the map's
 //       landmark of that track, observed by those keyframes.  Calls visual_odometry::bundleAdjust with the file's Huber
 //       width and iteration count and writes iterations, termination, initial and final cost, the keyframes' poses in

@@ -1,9 +1,10 @@
 """CPU: the bundle-adjustment rules of include/ebo.h (B1-B9) as tests/bundle_ref.py restates them -- the analytic
 Jacobians against complex-step and central differences, the update against exp's series, the Schur step against a
 dense solve of the full normal equations, the device's own text (csrc/ebo_bundle.inc compiled for the host by
-tools/bundle_adjust_serial.cpp) against the restatement, the restatement's minimum against scipy's, and the two
-measurements tests/test_gpu_bundle.py leans on: every scene's delta (the restatement against itself with every stated
-sum reversed) and the guard that no decision of any scene is a coin toss."""
+tools/bundle_adjust_serial.cpp) against the restatement, the restatement's minimum against scipy's, and the
+measurements tests/test_gpu_bundle.py and tests/test_gpu_bundle_branches.py lean on: every scene's delta (the
+restatement against itself with every stated sum reversed), the guard that no decision of any scene is a coin toss,
+and that the branch scenes take the branches they are there for."""
 import json
 import os
 import subprocess
@@ -113,50 +114,155 @@ def test_schur_step_against_a_dense_solve(name):
     assert np.all(step[~s.pfree] == 0.0)
 
 
+_scenes, _solved = {}, {}
+
+
+def all_scenes():
+    """test_scenes() and branch_scenes() under their (distinct) names, built once."""
+    if not _scenes:
+        _scenes.update(B.test_scenes())
+        branch = B.branch_scenes()
+        assert not set(branch) & set(_scenes)
+        _scenes.update(branch)
+    return _scenes
+
+
 def solve_both(name):
-    pr, fix, o = B.test_scenes()[name]
-    return B.solve(pr, B.HUBER, fix, o), B.solve(pr, B.HUBER, fix, o, reverse_sums=True)
+    """The restatement's solve of a scene in the stated order and with every stated sum reversed; solved once, read only."""
+    if name not in _solved:
+        pr, fix, o = all_scenes()[name]
+        _solved[name] = (B.solve(pr, B.HUBER, fix, o), B.solve(pr, B.HUBER, fix, o, reverse_sums=True))
+    return _solved[name]
+
+
+def flags(run):
+    return run["trace"][1:run["summary"]["iterations"] + 1, 3]
 
 
 def test_delta_and_no_coin_tosses():
-    """For every scene of the GPU tests: delta, and the guard -- no step quality within 1e-6 relative of
-    min_relative_decrease, no convergence test within 1e-6 relative of its threshold, and the same integers and trace
-    flags in both sum orders.  No scene is excluded."""
+    """For every scene of the GPU tests (test_scenes and branch_scenes): delta, and the guard -- no step quality within
+    1e-6 relative of the scene's min_relative_decrease, no convergence test (step norm, cost change, gradient, radius)
+    within 1e-6 relative of its threshold, the same integers and trace flags in both sum orders, and where a
+    factorisation broke off its pivot is exactly 0 in both orders (an invalid step that is the problem's, not a
+    rounding's).  No scene is excluded."""
     worst_e = 0.0
-    for name in B.test_scenes():
+    for name, (_, _, o) in all_scenes().items():
         a, b = solve_both(name)
         delta = B.result_difference(a, b)
         for k in ("iterations", "num_evals_cost", "num_evals_jac", "termination"):
             assert a["summary"][k] == b["summary"][k], (name, k)
         assert np.array_equal(a["trace"][:, 3], b["trace"][:, 3]), name
+        mrd = o["min_relative_decrease"]
         for run in (a, b):
             q = np.array(run["solver"].qualities)
-            assert len(q) == 0 or (np.abs(q - 1e-3) > 1e-9).all(), (name, q)
+            assert len(q) == 0 or (np.abs(q - mrd) > 1e-6 * mrd).all(), (name, q)
             for sn, st, dc, ft in run["solver"].checks:
                 assert abs(sn - st) > 1e-6 * st and abs(dc - ft) > 1e-6 * ft, (name, sn, st, dc, ft)
+            for value, bound in run["solver"].exit_checks:
+                assert abs(value - bound) > 1e-6 * bound, (name, value, bound)
+            piv = run["solver"].failed_pivots
+            assert all(p == 0.0 for p in piv), (name, piv)
+            assert len(piv) == int((flags(run) == -1.0).sum()), (name, piv)      # every invalid step is such a pivot
         if name.startswith("e") and name != "edge":
             worst_e = max(worst_e, delta)
         else:
-            print("delta %-5s %.3g  (iterations %d, termination %d)" % (name, delta, a["summary"]["iterations"], a["summary"]["termination"]))
+            print("delta %-11s %.3g  (iterations %d, termination %d)" % (name, delta, a["summary"]["iterations"], a["summary"]["termination"]))
     print("delta e00-e63 <= %.3g" % worst_e)
+
+
+def test_the_branch_scenes_take_their_branches():
+    """What branch_scenes() is for, read off the restatement alone: an edit of a seed that loses a branch fails here.
+    Trace flags: 1 taken, 0 rejected, -1 invalid, 2 converged at this candidate."""
+    scenes = B.branch_scenes()
+    run = {n: solve_both(n)[0] for n in scenes}
+    summ = {n: run[n]["summary"] for n in scenes}
+    # rejected steps; in rej4 several in a row, so that `decrease` doubles more than once
+    for n in ("rej", "rej4", "rej_mrd"):
+        assert (flags(run[n]) == 0.0).any(), n
+    f = flags(run["rej4"])
+    assert ((f[1:] == 0.0) & (f[:-1] == 0.0)).any()
+    # rej_mrd is rej with another min_relative_decrease: a step rej takes is rejected
+    assert scenes["rej_mrd"][0] is scenes["rej"][0]
+    q = np.array(run["rej"]["solver"].qualities)
+    taken = q[flags(run["rej"])[:len(q)] == 1.0]
+    assert (taken <= scenes["rej_mrd"][2]["min_relative_decrease"]).any()
+    fr, fm = flags(run["rej"]), flags(run["rej_mrd"])
+    k = int(np.nonzero(fr[:min(len(fr), len(fm))] != fm[:min(len(fr), len(fm))])[0][0])
+    assert fr[k] == 1.0 and fm[k] == 0.0
+    # invalid steps only, to termination 2 after max_consecutive_invalid of them, without one cost evaluation
+    for n, its in (("invalid", 5), ("invalid3", 3)):
+        assert summ[n]["iterations"] == its and summ[n]["termination"] == 2 and summ[n]["num_evals_cost"] == 0, n
+        assert (flags(run[n]) == -1.0).all(), n
+    assert np.array_equal(run["invalid"]["trace"][:6, 1], 1e4 * 0.5 ** np.arange(6))
+    # a step taken although the cost rises
+    t = run["nonmono"]["trace"][:summ["nonmono"]["iterations"] + 1]
+    acc = t[t[:, 3] == 1.0, 0]
+    assert not (flags(run["nonmono"]) == 0.0).any() and (acc[1:] > acc[:-1]).any()
+    # ... and the solve cut right after it: the lowest-cost point visited comes back, not the last iterate
+    cut = run["nonmono_cut"]
+    assert summ["nonmono_cut"]["termination"] == 1 and summ["nonmono_cut"]["iterations"] == 8
+    assert cut["trace"][8, 3] == 1.0 and summ["nonmono_cut"]["final_cost"] < cut["trace"][8, 0]
+    assert summ["nonmono_cut"]["final_cost"] == cut["trace"][7, 0]
+    assert not np.array_equal(cut["poses"], cut["last_poses"]) and not np.array_equal(cut["points"], cut["last_points"])
+    # nonmono_m5 / nonmono_m2: one problem under max_consecutive_nonmonotonic 5 and 2.  Ten rejections in a row first
+    # (decrease up to 1024); then several steps that raise the cost; under 2 the count of steps that set no new minimum
+    # reaches its limit and is reset more than once, and the path is another: rejections return where 5 has none
+    f5, f2 = flags(run["nonmono_m5"]), flags(run["nonmono_m2"])
+    assert (f5[:10] == 0.0).all() and (f5[10:-1] == 1.0).all() and (f2[:10] == 0.0).all()
+    for n in ("nonmono_m5", "nonmono_m2"):
+        t = run[n]["trace"][:summ[n]["iterations"] + 1]
+        acc = t[t[:, 3] == 1.0, 0]
+        assert int((acc[1:] > acc[:-1]).sum()) >= 4, n
+        assert summ[n]["termination"] == 0
+    assert scenes["nonmono_m2"][0] is scenes["nonmono_m5"][0]
+    assert (f2[10:] == 0.0).sum() >= 2 and summ["nonmono_m2"]["iterations"] != summ["nonmono_m5"]["iterations"]
+    # the exits: gradient_tolerance (no flag-2 row), parameter_tolerance (a flag-2 row whose step norm is under its
+    # bound while the cost change is not: function_tolerance is 0), min_radius
+    assert summ["gtol"]["termination"] == 0 and summ["gtol"]["iterations"] > 0 and not (flags(run["gtol"]) == 2.0).any()
+    sn, st, dc, ft = run["ptol"]["solver"].checks[-1]
+    assert summ["ptol"]["termination"] == 0 and flags(run["ptol"])[-1] == 2.0 and sn <= st and dc > ft
+    assert summ["minrad"]["iterations"] == 0 and summ["minrad"]["termination"] == 0
+    # a parameter_tolerance and a function_tolerance that are not the defaults, each ending its solve earlier and alone
+    sn, st, dc, ft = run["ptol4"]["solver"].checks[-1]
+    assert flags(run["ptol4"])[-1] == 2.0 and sn <= st and dc > ft and summ["ptol4"]["iterations"] < summ["ptol"]["iterations"]
+    sn, st, dc, ft = run["ftol3"]["solver"].checks[-1]
+    assert scenes["ftol3"][0] is scenes["rej"][0]
+    assert flags(run["ftol3"])[-1] == 2.0 and dc <= ft and sn > st and summ["ftol3"]["iterations"] < summ["rej"]["iterations"]
+    # the options that clip
+    assert run["maxrad"]["trace"][:summ["maxrad"]["iterations"] + 1, 1].max() == 2e4
+    for n in ("lmclip", "noscale"):                                    # they change the path of scene a
+        assert not np.array_equal(run[n]["trace"], solve_both("a")[0]["trace"]), n
+    # B7 damps by the diagonal itself, so without a clip the scaling of B6 moves the path by roundings only (noscale
+    # follows a to 1e-10); with the diagonal clipped to a constant it decides the path: 5 iterations against lmclip's 9
+    assert {k: v for k, v in scenes["noscale_clip"][2].items() if k != "jacobi_scaling"} == \
+           {k: v for k, v in scenes["lmclip"][2].items() if k != "jacobi_scaling"}
+    assert summ["noscale_clip"]["iterations"] != summ["lmclip"]["iterations"]
+    # the shapes
+    assert run["fix24"]["solver"].dim == 144 and scenes["fix24"][1]
+    s = run["dense24"]["solver"]
+    assert s.dim == 132 and s.N == s.F * s.P == 720
+    s = run["big"]["solver"]
+    assert s.N == B.MAX_OBS == 65535 and s.P == B.MAX_POINTS == 4096 and s.active.all()
 
 
 def test_the_devices_text_equals_the_restatement(tmp_path):
     """csrc/ebo_bundle.inc compiled for the host (tools/bundle_adjust_serial.cpp, g++ -O2 -ffp-contract=off), the lanes of
-    a phase run one after the other: integers equal, doubles within 10 x delta; the count of bit-equal doubles printed."""
+    a phase run one after the other: integers equal, doubles within 10 x delta; the count of bit-equal doubles printed.
+    The problem file carries every option, so every branch scene runs here as well, `big` among them (the tool
+    solves it in well under a second): a fault of the device's text can be looked for under a host debugger."""
     exe = tmp_path / "bundle_adjust_serial"
     src = os.path.join(ROOT, "event-based-odomety_amd", "tools", "bundle_adjust_serial.cpp")
     subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-o", str(exe), src])
-    scenes = B.test_scenes()
+    scenes = all_scenes()
     equal = total = 0
-    for name in ("a", "b", "c", "d", "edge", "it0", "it1", "nan", "e00", "e31", "e63"):
+    for name in ("a", "b", "c", "d", "edge", "it0", "it1", "nan", "e00", "e31", "e63") + tuple(B.branch_scenes()):
         pr, fix, o = scenes[name]
         a, b = solve_both(name)
         delta = B.result_difference(a, b)
         B.write_problem(tmp_path / "p.f64", pr, B.HUBER, fix, o)
         out = subprocess.run([str(exe), str(tmp_path / "p.f64"), str(tmp_path / "r.f64"), "1"], capture_output=True, text=True)
         assert out.returncode == 0, out.stderr
-        json.loads(out.stdout.strip().splitlines()[-1])
+        ms = json.loads(out.stdout.strip().splitlines()[-1])["ms_median"]
         r = np.fromfile(str(tmp_path / "r.f64"))
         F, P = len(pr["poses"]), len(pr["points"])
         s = a["summary"]
@@ -165,8 +271,10 @@ def test_the_devices_text_equals_the_restatement(tmp_path):
         want = np.concatenate([[s["initial_cost"], s["final_cost"]], a["poses"].reshape(-1), a["points"].reshape(-1), a["trace"].reshape(-1)])
         assert got.shape == want.shape
         assert np.array_equal(r[6 + 12 * F + 3 * P:].reshape(-1, 4)[:, 3], a["trace"][:, 3]), name
+        same = int(((got.view(np.uint64) == want.view(np.uint64)) | (np.isnan(got) & np.isnan(want))).sum())
+        print("%-11s %d of %d doubles bit-equal, largest difference %.3g, delta %.3g, %.1f ms" % (name, same, got.size, B.difference(got, want), delta, ms))
         assert B.difference(got, want) <= 10 * delta, (name, B.difference(got, want), delta)
-        equal += int(((got.view(np.uint64) == want.view(np.uint64)) | (np.isnan(got) & np.isnan(want))).sum())
+        equal += same
         total += got.size
     print("%d of %d doubles bit-equal" % (equal, total))
 
