@@ -1,7 +1,9 @@
-// ebo_abspose.inc — absolute pose on the device: three-point RANSAC hypotheses over (bearing vector, landmark) pairs,
-// their inlier counts, and the per-point score for a given pose.  Replaces what the reference does serially through
-// OpenGV in VisualOdometryFrontEnd::localizeCamera (visual_odometry.cpp:212-286).  Included inside ebo_kernels.hip's
-// anonymous namespace, after ebo_twoview.inc, whose dot, cross, mix, rotation and 3 x 3 Jacobi rotation it reuses.
+// ebo_abspose.inc — absolute pose on the device: three-point RANSAC hypotheses over (bearing vector, landmark) pairs
+// and the per-point score for a given pose; the kernels that count and list a hypothesis's inliers are
+// ebo_ransac.inc's.  Replaces what the reference does serially through OpenGV in
+// VisualOdometryFrontEnd::localizeCamera (visual_odometry.cpp:212-286).  Included inside ebo_kernels.hip's anonymous
+// namespace, after ebo_twoview.inc, whose dot, cross, mix, rotation and 3 x 3 Jacobi rotation it reuses (and through
+// which ebo_ransac.inc comes in).
 // The rules are written out in include/ebo.h ("absolute pose", A1-A5); tests/abspose_ref.py restates them in numpy.
 // Every float64 operation is rounded on its own (__dadd_rn / __dsub_rn / __dmul_rn / __ddiv_rn / __dsqrt_rn).
 
@@ -9,8 +11,6 @@ constexpr int kApNewton = 32;        // Newton steps on the cubic (A3)
 constexpr int kApPolish = 3;         // Gauss-Newton steps on the three distance equations (A3)
 constexpr int kApSweeps = 8;         // jacobi(D0, 8)
 constexpr int kApBlock = 64;         // hypotheses per workgroup of the hypothesis kernel: one lane each
-constexpr int kApTile = 1024;        // points of a frame staged in LDS at a time (48 KB)
-constexpr int kApHypChunk = 8;       // hypotheses scored per workgroup of the counting kernel
 
 // A1: the bearing-vector reprojection score of one (bearing, landmark) pair under a camera-to-world pose
 __device__ __forceinline__ double ap_score(const TvPoseRT& T, const double (&f)[3], const double (&p)[3])
@@ -27,34 +27,7 @@ __device__ __forceinline__ double ap_score(const TvPoseRT& T, const double (&f)[
 	return __dsub_rn(1.0, tv_dot3(f[0], f[1], f[2], r0, r1, r2));
 }
 
-// A2: rule 3 with four draws
-__device__ __forceinline__ void ap_sample(unsigned long long seed, int frame, int h, int n, int (&out)[4])
-{
-	const unsigned long long G = 0x9E3779B97F4A7C15ull;
-	unsigned long long x = tv_mix(seed + G);
-	x = tv_mix((x ^ static_cast<unsigned long long>(frame)) + G);
-	x = tv_mix((x ^ static_cast<unsigned long long>(h)) + G);
-	int pos[4], val[4];
-#pragma unroll
-	for (int d = 0; d < 4; ++d)
-	{
-		const unsigned long long r = tv_mix((x ^ static_cast<unsigned long long>(d)) + G);
-		const int j = d + static_cast<int>(static_cast<unsigned int>(r >> 32) % static_cast<unsigned int>(n - d));
-		int vj = j, vd = d;
-#pragma unroll
-		for (int e = 0; e < 4; ++e)
-		{
-			if (e < d)  // later records override earlier ones
-			{
-				vj = (pos[e] == j) ? val[e] : vj;
-				vd = (pos[e] == d) ? val[e] : vd;
-			}
-		}
-		out[d] = vj;
-		pos[d] = j;
-		val[d] = vd;
-	}
-}
+// A2: rule 3 with four draws is ransac_sample<4> (ebo_ransac.inc)
 
 // cofactors with cyclic indices, C[i][j] = M[i+1][j+1] * M[i+2][j+2] - M[i+1][j+2] * M[i+2][j+1]; returns dot(M[0], C[0])
 __device__ __forceinline__ double ap_cof(const double (&M)[3][3], double (&C)[3][3])
@@ -306,7 +279,7 @@ __global__ void __launch_bounds__(kApBlock) k_ap_hypotheses(int nFrames, int H, 
 	if (n >= 4)
 	{
 		int smp[4];
-		ap_sample(seed, frame, h, n, smp);
+		ransac_sample<4>(seed, frame, h, n, smp);
 		double sf[4][3], sp[4][3];
 #pragma unroll
 		for (int i = 0; i < 4; ++i)
@@ -338,127 +311,14 @@ __global__ void __launch_bounds__(kApBlock) k_ap_hypotheses(int nFrames, int H, 
 	valid[g] = ok ? 1 : 0;
 }
 
-// Counting kernel: unit of work = (frame, hypothesis, point).  A workgroup stages one tile of one frame's bearing
-// vectors and landmarks in LDS and scores it against kApHypChunk hypotheses, one wave per hypothesis at a time; a
-// wave counts its inliers with ballots and adds the integer to counts[] (zeroed before the launch): exact and
-// order-free.  grid = (ceil(H / kApHypChunk), nFrames, tiles of the largest frame)
-__global__ void __launch_bounds__(256) k_ap_count(int H, const int* __restrict__ offsets, const double* __restrict__ f,
-												  const double* __restrict__ pts, const double* __restrict__ models,
-												  const int* __restrict__ valid, double threshold, int* __restrict__ counts)
+// what ebo_ransac.inc's kernels need to know of this path
+struct ApProblem
 {
-	__shared__ double sf[3 * kApTile];
-	__shared__ double sp[3 * kApTile];
-	const int frame = blockIdx.y;
-	const long long base = offsets[frame];
-	const int n = offsets[frame + 1] - offsets[frame];
-	const int t0 = blockIdx.z * kApTile;
-	if (n < 4 || t0 >= n)
+	static constexpr int kSample = 4;
+	static __device__ __forceinline__ double score(const TvPoseRT& T, const double (&f)[3], const double (&p)[3])
 	{
-		return;  // the whole workgroup leaves together
+		return ap_score(T, f, p);
 	}
-	const int nt = min(kApTile, n - t0);
-	for (int e = threadIdx.x; e < 3 * nt; e += 256)
-	{
-		sf[e] = f[3 * (base + t0) + e];
-		sp[e] = pts[3 * (base + t0) + e];
-	}
-	__syncthreads();
-	const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-	for (int hh = wave; hh < kApHypChunk; hh += 4)
-	{
-		const int h = blockIdx.x * kApHypChunk + hh;
-		if (h >= H)
-		{
-			break;
-		}
-		const long long g = static_cast<long long>(frame) * H + h;
-		if (!valid[g])
-		{
-			continue;
-		}
-		const TvPoseRT T = tv_load_pose(models + 12 * g);
-		int cnt = 0;
-		for (int i0 = 0; i0 < nt; i0 += 64)
-		{
-			const int i = i0 + lane;
-			bool in = false;
-			if (i < nt)
-			{
-				const double a[3] = {sf[3 * i], sf[3 * i + 1], sf[3 * i + 2]};
-				const double b[3] = {sp[3 * i], sp[3 * i + 1], sp[3 * i + 2]};
-				in = ap_score(T, a, b) < threshold;
-			}
-			cnt += __popcll(__ballot(in));
-		}
-		if (lane == 0 && cnt)
-		{
-			atomicAdd(counts + g, cnt);
-		}
-	}
-}
-
-// one lane per point: score and inlier flag for a given pose (either output may be null)
-__global__ void __launch_bounds__(256) k_ap_scores(TvModelArg pose, int n, const double* __restrict__ f,
-												   const double* __restrict__ pts, double threshold,
-												   double* __restrict__ scores, unsigned char* __restrict__ flags)
-{
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n)
-	{
-		return;
-	}
-	const TvPoseRT T = tv_pose_of(pose);
-	const size_t o = 3 * static_cast<size_t>(i);
-	const double a[3] = {f[o], f[o + 1], f[o + 2]};
-	const double b[3] = {pts[o], pts[o + 1], pts[o + 2]};
-	const double s = ap_score(T, a, b);
-	if (scores)
-	{
-		scores[i] = s;
-	}
-	if (flags)
-	{
-		flags[i] = s < threshold ? 1 : 0;
-	}
-}
-
-// the winners' inlier flags, all frames in one launch: grid = (ceil(largest frame / 256), nFrames).  winner[frame] < 0
-// (no hypothesis: fewer than 4 points) clears the frame's flags.  Lane 0 of a frame's first workgroup copies the
-// winner's pose to winModels[frame][12] (zeros when there is none).
-__global__ void __launch_bounds__(256) k_ap_winner_flags(int H, const int* __restrict__ offsets, const double* __restrict__ f,
-														 const double* __restrict__ pts, const double* __restrict__ models,
-														 const int* __restrict__ valid, const int* __restrict__ winner,
-														 double threshold, unsigned char* __restrict__ flags,
-														 double* __restrict__ winModels)
-{
-	const int frame = blockIdx.y;
-	const long long base = offsets[frame];
-	const int n = offsets[frame + 1] - offsets[frame];
-	const int w = winner[frame];
-	const long long g = static_cast<long long>(frame) * H + (w < 0 ? 0 : w);
-	const bool have = w >= 0 && w < H && valid[g] != 0;
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i == 0)
-	{
-		for (int e = 0; e < 12; ++e)
-		{
-			winModels[12 * frame + e] = have ? models[12 * g + e] : 0.0;
-		}
-	}
-	if (i >= n)
-	{
-		return;
-	}
-	unsigned char fl = 0;
-	if (have)
-	{
-		const TvPoseRT T = tv_load_pose(models + 12 * g);
-		const size_t o = 3 * static_cast<size_t>(base + i);
-		const double a[3] = {f[o], f[o + 1], f[o + 2]};
-		const double b[3] = {pts[o], pts[o + 1], pts[o + 2]};
-		fl = ap_score(T, a, b) < threshold ? 1 : 0;
-	}
-	flags[base + i] = fl;
-}
+};
 
 #endif  // EBO_ABSPOSE_RULES_ONLY

@@ -13,28 +13,6 @@ using namespace ebo;
 
 namespace
 {
-size_t align256(size_t v)
-{
-	return (v + 255) & ~static_cast<size_t>(255);
-}
-
-struct Carve
-{
-	size_t at = 0;
-	size_t take(size_t bytes)
-	{
-		const size_t o = at;
-		at = align256(at + bytes);
-		return o;
-	}
-};
-
-template <class T>
-T* at(ebo_ctx* c, size_t off)
-{
-	return reinterpret_cast<T*>(static_cast<char*>(c->d_scratch.get()) + off);
-}
-
 int check_offsets(ebo_ctx* c, const int* off, int n, int cap, const char* what)
 {
 	if (!off || off[0] != 0)
@@ -56,17 +34,10 @@ int adjust(ebo_ctx* c, int n, const int* fo, const int* po, const int* oo, doubl
 		   const int* of, const int* op, const double* uv, bool hostArrays, const ebo_camera* cam, double huber, int fixPoints,
 		   const ebo_solver_opts* opts, ebo_summary* summaries, double* trace)
 {
-	if (!c)
+	int rc = enter(c, "ebo_bundle_adjust: a problem count outside [0, 65535]", n >= 0 && n <= kBaMaxProblems);
+	if (rc)
 	{
-		return EBO_ERR_ARG;
-	}
-	if (c->capturing)
-	{
-		return c->fail(EBO_ERR_STATE, kNotWhileRecording);
-	}
-	if (n < 0 || n > kBaMaxProblems)
-	{
-		return c->fail(EBO_ERR_ARG, "ebo_bundle_adjust: a problem count outside [0, 65535]");
+		return rc;
 	}
 	if (!cam || !opts || !(huber > 0.0) || opts->max_num_iterations < 0)
 	{
@@ -80,7 +51,7 @@ int adjust(ebo_ctx* c, int n, const int* fo, const int* po, const int* oo, doubl
 	{
 		return c->fail(EBO_ERR_ARG, "ebo_bundle_adjust: null summaries");
 	}
-	int rc = check_offsets(c, fo, n, kBaMaxFrames, "frame");
+	rc = check_offsets(c, fo, n, kBaMaxFrames, "frame");
 	rc = rc ? rc : check_offsets(c, po, n, kBaMaxPoints, "point");
 	rc = rc ? rc : check_offsets(c, oo, n, kBaMaxObs, "observation");
 	if (rc)
@@ -136,10 +107,9 @@ int adjust(ebo_ctx* c, int n, const int* fo, const int* po, const int* oo, doubl
 			}
 		}
 	}
-	(void)hipSetDevice(c->prm.device);
 	const auto wall0 = std::chrono::steady_clock::now();
 	const size_t traceDoubles = static_cast<size_t>(n) * (static_cast<size_t>(opts->max_num_iterations) + 1) * 4;
-	Carve cv;
+	ScratchCarve cv;
 	const size_t oFo = cv.take((n + 1) * sizeof(int)), oPo = cv.take((n + 1) * sizeof(int)), oOo = cv.take((n + 1) * sizeof(int));
 	const size_t oTo = cv.take((n + 1) * sizeof(long long));
 	const size_t oSum = cv.take(n * sizeof(ebo_summary));
@@ -165,7 +135,7 @@ int adjust(ebo_ctx* c, int n, const int* fo, const int* po, const int* oo, doubl
 	auto up = [&](size_t off, const void* src, size_t bytes) {
 		if (e == hipSuccess && bytes)
 		{
-			e = hipMemcpyAsync(at<char>(c, off), src, bytes, hipMemcpyHostToDevice, c->stream);
+			e = hipMemcpyAsync(c->scratch<char>(off), src, bytes, hipMemcpyHostToDevice, c->stream);
 		}
 	};
 	up(oFo, fo, (n + 1) * sizeof(int));
@@ -173,12 +143,12 @@ int adjust(ebo_ctx* c, int n, const int* fo, const int* po, const int* oo, doubl
 	up(oOo, oo, (n + 1) * sizeof(int));
 	up(oTo, tableOff.data(), (n + 1) * sizeof(long long));
 	BaTables t{};
-	t.frameOff = at<int>(c, oFo);
-	t.pointOff = at<int>(c, oPo);
-	t.obsOff = at<int>(c, oOo);
-	t.tableOff = at<long long>(c, oTo);
-	t.work = at<double>(c, oWork);
-	t.iwork = at<int>(c, oIwork);
+	t.frameOff = c->scratch<int>(oFo);
+	t.pointOff = c->scratch<int>(oPo);
+	t.obsOff = c->scratch<int>(oOo);
+	t.tableOff = c->scratch<long long>(oTo);
+	t.work = c->scratch<double>(oWork);
+	t.iwork = c->scratch<int>(oIwork);
 	t.totalF = tF;
 	t.totalP = tP;
 	t.totalN = tN;
@@ -192,13 +162,13 @@ int adjust(ebo_ctx* c, int n, const int* fo, const int* po, const int* oo, doubl
 		up(oOf, sf.data(), tN * sizeof(int));
 		up(oOp, sp.data(), tN * sizeof(int));
 		up(oUv, suv.data(), 2 * tN * sizeof(double));
-		t.poses = at<double>(c, oPoses);
-		t.fixed = at<unsigned char>(c, oFixed);
-		t.points = at<double>(c, oPoints);
-		t.of = at<int>(c, oOf);
-		t.op = at<int>(c, oOp);
-		t.uv = at<double>(c, oUv);
-		dTrace = trace ? at<double>(c, oTrace) : nullptr;
+		t.poses = c->scratch<double>(oPoses);
+		t.fixed = c->scratch<unsigned char>(oFixed);
+		t.points = c->scratch<double>(oPoints);
+		t.of = c->scratch<int>(oOf);
+		t.op = c->scratch<int>(oOp);
+		t.uv = c->scratch<double>(oUv);
+		dTrace = trace ? c->scratch<double>(oTrace) : nullptr;
 	}
 	else
 	{
@@ -213,22 +183,16 @@ int adjust(ebo_ctx* c, int n, const int* fo, const int* po, const int* oo, doubl
 	{
 		return c->hip(e, "bundle-adjustment uploads");
 	}
-	if (c->tv_timing)
-	{
-		(void)hipEventRecord(c->tv_ev[0], c->stream);
-	}
-	if (launch_bundle_adjust(n, maxF, t, *cam, huber, fixPoints ? 1 : 0, *opts, at<ebo_summary>(c, oSum), dTrace, c->stream))
+	mark(c, 0);
+	if (launch_bundle_adjust(n, maxF, t, *cam, huber, fixPoints ? 1 : 0, *opts, c->scratch<ebo_summary>(oSum), dTrace, c->stream))
 	{
 		return c->hip(hipGetLastError(), "bundle-adjustment kernel launch");
 	}
-	if (c->tv_timing)
-	{
-		(void)hipEventRecord(c->tv_ev[1], c->stream);
-	}
+	mark(c, 1);
 	auto down = [&](void* dst, size_t off, size_t bytes) {
 		if (e == hipSuccess && bytes)
 		{
-			e = hipMemcpyAsync(dst, at<char>(c, off), bytes, hipMemcpyDeviceToHost, c->stream);
+			e = hipMemcpyAsync(dst, c->scratch<char>(off), bytes, hipMemcpyDeviceToHost, c->stream);
 		}
 	};
 	down(summaries, oSum, n * sizeof(ebo_summary));

@@ -20,11 +20,6 @@ CameraConsts consts_of(const ebo_camera* cam)
 	k.p2 = cam->p2;
 	return k;
 }
-
-size_t align256(size_t v)
-{
-	return (v + 255) & ~static_cast<size_t>(255);
-}
 }  // namespace
 
 extern "C" {

@@ -76,6 +76,23 @@ template <class T>
 using Dev = ebo::DevBuf<T, DeviceMem>;
 template <class T, unsigned int Flags = kZeroCopyFlags>
 using Pinned = ebo::DevBuf<T, PinnedMem<Flags>>;
+
+inline size_t align256(size_t v)
+{
+	return (v + 255) & ~static_cast<size_t>(255);
+}
+
+// a bump allocator over the context's scratch buffer: take() gives offsets for ebo_ctx::scratch<T>(), `at` is the size to grow to
+struct ScratchCarve
+{
+	size_t at = 0;
+	size_t take(size_t bytes)
+	{
+		const size_t o = at;
+		at = align256(at + bytes);
+		return o;
+	}
+};
 }  // namespace ebo_host
 using namespace ebo_host;
 
@@ -175,7 +192,7 @@ struct ebo_ctx
 	Pinned<unsigned char> pin_modes;
 
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
-	// ebo_two_view_timing (ebo_twoview.cpp): events around the phases of ebo_relative_pose_ransac, created on first use
+	// ebo_two_view_timing (ebo_twoview.cpp): events around the phases of a RANSAC call (ebo_ransac.cpp), created on first use
 	hipEvent_t tv_ev[5] = {};
 	bool tv_timing = false;
 	float tv_ms[5] = {};  // hypothesis kernel, counting kernel, host walk, winner upload + inlier-list kernel, whole call (wall clock)
@@ -194,6 +211,12 @@ struct ebo_ctx
 	size_t unit_index(int window, int patch) const
 	{
 		return custom_n ? static_cast<size_t>(patch) : static_cast<size_t>(window) * (P + 1) + patch;
+	}
+
+	template <class T>
+	T* scratch(size_t off)
+	{
+		return reinterpret_cast<T*>(static_cast<char*>(d_scratch.get()) + off);
 	}
 
 	int fail(int code, const std::string& msg)
@@ -250,6 +273,62 @@ struct ebo_ctx
 // process unable to use the stream again -- so every other entry point refuses up front.
 static const char* const kNotWhileRecording =
 	"not while recording a graph (ebo_graph_begin): only ebo_eval_device, ebo_solve_device and ebo_count_image_device can be recorded";
+
+namespace ebo_host
+{
+// how a synchronous entry point begins: a context, no recording, its arguments (`what` is the message when they are
+// not in order), the context's device
+inline int enter(ebo_ctx* c, const char* what, bool argsOk)
+{
+	if (!c)
+	{
+		return EBO_ERR_ARG;
+	}
+	if (c->capturing)
+	{
+		return c->fail(EBO_ERR_STATE, kNotWhileRecording);
+	}
+	if (!argsOk)
+	{
+		return c->fail(EBO_ERR_ARG, what);
+	}
+	(void)hipSetDevice(c->prm.device);
+	return EBO_OK;
+}
+
+// phase marks of ebo_two_view_timing: nothing is recorded unless the caller asked for timing
+inline void mark(ebo_ctx* c, int i)
+{
+	if (c->tv_timing)
+	{
+		(void)hipEventRecord(c->tv_ev[i], c->stream);
+	}
+}
+
+// One RANSAC path as ebo_ransac.cpp's driver sees it.  A group is what one RANSAC runs over (a keyframe pair, a
+// frame); a and b are the path's two [n][3] arrays.  The words are those of the path's error messages.
+struct RansacProblem
+{
+	ebo::RansacKind kind;  // the problem type of the counting, winner and score kernels
+	int sample;            // points a hypothesis draws
+	int (*hypotheses)(int n_groups, int H, const int* d_offsets, const double* d_a, const double* d_b, uint64_t seed,
+					  double* d_models, int* d_valid, int* d_samples, void* stream);
+	const char* entry;     // "ebo_relative_pose_ransac"
+	const char* group;     // "pair"
+	const char* points;    // "correspondences"
+	const char* arrays;    // "bearing vectors"
+	const char* label;     // "two-view": names the path in "<label> uploads: <hip error>"
+	const char* scoresArgs;    // the *_scores entries' whole argument message
+	const char* scoresUpload;  // and what their upload is called
+};
+// hostArrays: a / b are host arrays and are staged in scratch; otherwise device pointers used in place
+int ransac(ebo_ctx* c, const RansacProblem& P, int n_groups, const int* offsets, const double* a, const double* b, bool hostArrays,
+		   const ebo_two_view_params* prm, ebo_two_view_result* result, int* inlier_idx, int* hyp_counts, double* hyp_models,
+		   int* hyp_samples);
+// hostArrays: as above, and scores / flags are host arrays too
+int ransac_scores(ebo_ctx* c, const RansacProblem& P, const double* model, int n, const double* a, const double* b, bool hostArrays,
+				  double threshold, double* scores, uint8_t* flags);
+}  // namespace ebo_host
 
 // helpers defined in ebo_api.cpp and shared by the other host translation units
 namespace ebo_host

@@ -6,11 +6,6 @@ using namespace ebo;
 
 namespace
 {
-size_t align256(size_t v)
-{
-	return (v + 255) & ~static_cast<size_t>(255);
-}
-
 int entry_checks(ebo_ctx* c)
 {
 	if (c->capturing)

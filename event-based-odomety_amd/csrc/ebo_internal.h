@@ -514,15 +514,6 @@ int launch_rectify_map(const CameraConsts& k, int w, int h, double* d_map, void*
 // two-view geometry (ebo_twoview.inc, ebo_twoview.cpp).  models: [n_pairs * H][3][4]; d_samples may be null.
 int launch_tv_hypotheses(int n_pairs, int H, const int* d_offsets, const double* d_f1, const double* d_f2, uint64_t seed,
 						 double* d_models, int* d_valid, int* d_samples, void* stream);
-// d_counts [n_pairs * H] must be zero on entry; max_n: correspondences of the largest pair
-int launch_tv_count(int n_pairs, int H, int max_n, const int* d_offsets, const double* d_f1, const double* d_f2,
-					const double* d_models, const int* d_valid, double threshold, int* d_counts, void* stream);
-int launch_tv_winner_flags(int n_pairs, int H, int max_n, const int* d_offsets, const double* d_f1, const double* d_f2,
-						   const double* d_models, const int* d_valid, const int* d_winner, double threshold,
-						   unsigned char* d_flags, double* d_win_models, void* stream);
-// model12: HOST pointer to a [3][4] model (travels as a kernel argument); either output may be null
-int launch_tv_scores(const double* model12, int n, const double* d_f1, const double* d_f2, double threshold, double* d_scores,
-					 unsigned char* d_flags, void* stream);
 int launch_tv_triangulate(int n_poses, const double* d_poses, int n, const int* d_pose_pair, const double* d_f1,
 						  const double* d_f2, double* d_points, void* stream);
 int launch_tv_epipolar(const double* model12, int n, const double* d_f1, const double* d_f2, double threshold,
@@ -530,13 +521,22 @@ int launch_tv_epipolar(const double* model12, int n, const double* d_f1, const d
 // absolute pose (ebo_abspose.inc, ebo_abspose.cpp).  models: [n_frames * H][3][4]; d_samples may be null.
 int launch_ap_hypotheses(int n_frames, int H, const int* d_offsets, const double* d_f, const double* d_points, uint64_t seed,
 						 double* d_models, int* d_valid, int* d_samples, void* stream);
-int launch_ap_count(int n_frames, int H, int max_n, const int* d_offsets, const double* d_f, const double* d_points,
-					const double* d_models, const int* d_valid, double threshold, int* d_counts, void* stream);
-int launch_ap_winner_flags(int n_frames, int H, int max_n, const int* d_offsets, const double* d_f, const double* d_points,
-						   const double* d_models, const int* d_valid, const int* d_winner, double threshold,
-						   unsigned char* d_flags, double* d_win_models, void* stream);
-int launch_ap_scores(const double* pose, int n, const double* d_f, const double* d_points, double threshold, double* d_scores,
-					 unsigned char* d_flags, void* stream);
+// What the two paths share (ebo_ransac.inc, ebo_ransac.cpp): kind selects the problem type the kernels are instantiated
+// for.  A group is a keyframe pair or a frame; d_a / d_b are its two [n][3] arrays (f1, f2 or bearing vectors, landmarks).
+enum class RansacKind
+{
+	kTwoView,
+	kAbsPose
+};
+// d_counts [n_groups * H] must be zero on entry; max_n: points of the largest group
+int launch_ransac_count(RansacKind kind, int n_groups, int H, int max_n, const int* d_offsets, const double* d_a, const double* d_b,
+						const double* d_models, const int* d_valid, double threshold, int* d_counts, void* stream);
+int launch_ransac_winner_flags(RansacKind kind, int n_groups, int H, int max_n, const int* d_offsets, const double* d_a,
+							   const double* d_b, const double* d_models, const int* d_valid, const int* d_winner, double threshold,
+							   unsigned char* d_flags, double* d_win_models, void* stream);
+// model12: HOST pointer to a [3][4] model (travels as a kernel argument); either output may be null
+int launch_ransac_scores(RansacKind kind, const double* model12, int n, const double* d_a, const double* d_b, double threshold,
+						 double* d_scores, unsigned char* d_flags, void* stream);
 
 // bundle adjustment (ebo_bundle.inc, ebo_bundle.cpp): where each problem's slices begin (sums of the sizes of the
 // problems before it, device arrays) and the call's device arrays

@@ -1836,46 +1836,6 @@ int launch_tv_hypotheses(int n_pairs, int H, const int* d_offsets, const double*
 	return check_launch();
 }
 
-int launch_tv_count(int n_pairs, int H, int max_n, const int* d_offsets, const double* d_f1, const double* d_f2,
-					const double* d_models, const int* d_valid, double threshold, int* d_counts, void* stream)
-{
-	if (n_pairs <= 0 || H <= 0 || max_n < 8)
-	{
-		return 0;
-	}
-	hipLaunchKernelGGL(k_tv_count, dim3((H + kTvHypChunk - 1) / kTvHypChunk, n_pairs, (max_n + kTvTile - 1) / kTvTile), dim3(256), 0,
-					   static_cast<hipStream_t>(stream), H, d_offsets, d_f1, d_f2, d_models, d_valid, threshold, d_counts);
-	return check_launch();
-}
-
-int launch_tv_winner_flags(int n_pairs, int H, int max_n, const int* d_offsets, const double* d_f1, const double* d_f2,
-						   const double* d_models, const int* d_valid, const int* d_winner, double threshold,
-						   unsigned char* d_flags, double* d_win_models, void* stream)
-{
-	if (n_pairs <= 0)
-	{
-		return 0;
-	}
-	hipLaunchKernelGGL(k_tv_winner_flags, dim3(max_n > 0 ? (max_n + 255) / 256 : 1, n_pairs), dim3(256), 0,
-					   static_cast<hipStream_t>(stream), H, d_offsets, d_f1, d_f2, d_models, d_valid, d_winner, threshold, d_flags,
-					   d_win_models);
-	return check_launch();
-}
-
-int launch_tv_scores(const double* model12, int n, const double* d_f1, const double* d_f2, double threshold, double* d_scores,
-					 unsigned char* d_flags, void* stream)
-{
-	if (n <= 0)
-	{
-		return 0;
-	}
-	TvModelArg m;
-	std::copy(model12, model12 + 12, m.m);
-	hipLaunchKernelGGL(k_tv_scores, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), m, n, d_f1, d_f2,
-					   threshold, d_scores, d_flags);
-	return check_launch();
-}
-
 int launch_tv_triangulate(int n_poses, const double* d_poses, int n, const int* d_pose_pair, const double* d_f1,
 						  const double* d_f2, double* d_points, void* stream)
 {
@@ -1917,43 +1877,46 @@ int launch_ap_hypotheses(int n_frames, int H, const int* d_offsets, const double
 	return check_launch();
 }
 
-int launch_ap_count(int n_frames, int H, int max_n, const int* d_offsets, const double* d_f, const double* d_points,
-					const double* d_models, const int* d_valid, double threshold, int* d_counts, void* stream)
+// what the two RANSAC paths share (ebo_ransac.inc)
+int launch_ransac_count(RansacKind kind, int n_groups, int H, int max_n, const int* d_offsets, const double* d_a, const double* d_b,
+						const double* d_models, const int* d_valid, double threshold, int* d_counts, void* stream)
 {
-	if (n_frames <= 0 || H <= 0 || max_n < 4)
+	const bool tv = kind == RansacKind::kTwoView;
+	if (n_groups <= 0 || H <= 0 || max_n < (tv ? TvProblem::kSample : ApProblem::kSample))
 	{
 		return 0;
 	}
-	hipLaunchKernelGGL(k_ap_count, dim3((H + kApHypChunk - 1) / kApHypChunk, n_frames, (max_n + kApTile - 1) / kApTile), dim3(256), 0,
-					   static_cast<hipStream_t>(stream), H, d_offsets, d_f, d_points, d_models, d_valid, threshold, d_counts);
+	hipLaunchKernelGGL(tv ? k_ransac_count<TvProblem> : k_ransac_count<ApProblem>,
+					   dim3((H + kRansacHypChunk - 1) / kRansacHypChunk, n_groups, (max_n + kRansacTile - 1) / kRansacTile), dim3(256), 0,
+					   static_cast<hipStream_t>(stream), H, d_offsets, d_a, d_b, d_models, d_valid, threshold, d_counts);
 	return check_launch();
 }
 
-int launch_ap_winner_flags(int n_frames, int H, int max_n, const int* d_offsets, const double* d_f, const double* d_points,
-						   const double* d_models, const int* d_valid, const int* d_winner, double threshold,
-						   unsigned char* d_flags, double* d_win_models, void* stream)
+int launch_ransac_winner_flags(RansacKind kind, int n_groups, int H, int max_n, const int* d_offsets, const double* d_a,
+							   const double* d_b, const double* d_models, const int* d_valid, const int* d_winner, double threshold,
+							   unsigned char* d_flags, double* d_win_models, void* stream)
 {
-	if (n_frames <= 0)
+	if (n_groups <= 0)
 	{
 		return 0;
 	}
-	hipLaunchKernelGGL(k_ap_winner_flags, dim3(max_n > 0 ? (max_n + 255) / 256 : 1, n_frames), dim3(256), 0,
-					   static_cast<hipStream_t>(stream), H, d_offsets, d_f, d_points, d_models, d_valid, d_winner, threshold, d_flags,
-					   d_win_models);
+	hipLaunchKernelGGL(kind == RansacKind::kTwoView ? k_ransac_winner_flags<TvProblem> : k_ransac_winner_flags<ApProblem>,
+					   dim3(max_n > 0 ? (max_n + 255) / 256 : 1, n_groups), dim3(256), 0, static_cast<hipStream_t>(stream), H, d_offsets,
+					   d_a, d_b, d_models, d_valid, d_winner, threshold, d_flags, d_win_models);
 	return check_launch();
 }
 
-int launch_ap_scores(const double* pose, int n, const double* d_f, const double* d_points, double threshold, double* d_scores,
-					 unsigned char* d_flags, void* stream)
+int launch_ransac_scores(RansacKind kind, const double* model12, int n, const double* d_a, const double* d_b, double threshold,
+						 double* d_scores, unsigned char* d_flags, void* stream)
 {
 	if (n <= 0)
 	{
 		return 0;
 	}
 	TvModelArg m;
-	std::copy(pose, pose + 12, m.m);
-	hipLaunchKernelGGL(k_ap_scores, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), m, n, d_f, d_points,
-					   threshold, d_scores, d_flags);
+	std::copy(model12, model12 + 12, m.m);
+	hipLaunchKernelGGL(kind == RansacKind::kTwoView ? k_ransac_scores<TvProblem> : k_ransac_scores<ApProblem>, dim3((n + 255) / 256),
+					   dim3(256), 0, static_cast<hipStream_t>(stream), m, n, d_a, d_b, threshold, d_scores, d_flags);
 	return check_launch();
 }
 

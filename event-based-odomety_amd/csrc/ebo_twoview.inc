@@ -1,7 +1,8 @@
-// ebo_twoview.inc — two-view geometry on the device: eight-point RANSAC hypotheses, their inlier counts, and the
-// per-point closed forms (scores for a given model, midpoint triangulation, the epipolar test).  Replaces what the
-// reference does serially in VisualOdometryFrontEnd::findInliersRansac (visual_odometry.cpp:288-341) and
-// triangulation.cpp:7-63.  Included inside ebo_kernels.hip's anonymous namespace, after ebo_camera.inc.  The rules
+// ebo_twoview.inc — two-view geometry on the device: eight-point RANSAC hypotheses and the per-point closed forms
+// (the score, midpoint triangulation, the epipolar test); the kernels that count and list a hypothesis's inliers are
+// ebo_ransac.inc's, shared with absolute pose.  Replaces what the reference does serially in
+// VisualOdometryFrontEnd::findInliersRansac (visual_odometry.cpp:288-341) and triangulation.cpp:7-63.  Included
+// inside ebo_kernels.hip's anonymous namespace, after ebo_camera.inc.  The rules
 // are written out in include/ebo.h ("two-view geometry"); tests/twoview_ref.py restates them in numpy.  Every float64
 // operation is rounded on its own (__dadd_rn / __dsub_rn / __dmul_rn / __ddiv_rn / __dsqrt_rn).
 
@@ -10,8 +11,6 @@ constexpr int kTvGroups = 16;         // hypotheses per 256-lane workgroup
 constexpr int kTvStride = 81 + 72 + 24 + 24;  // doubles of LDS per hypothesis: V, A (later the sample scores), f1, f2
 constexpr int kTvSweeps9 = 10;
 constexpr int kTvSweeps3 = 8;
-constexpr int kTvTile = 1024;         // correspondences of a pair staged in LDS at a time (48 KB)
-constexpr int kTvHypChunk = 8;        // hypotheses scored per workgroup of the counting kernel
 
 __device__ __forceinline__ double tv_dot3(double a0, double a1, double a2, double b0, double b1, double b2)
 {
@@ -88,40 +87,12 @@ __device__ __forceinline__ double tv_score(const TvPoseRT& T, const double (&f1)
 	return __dadd_rn(s1, s2);
 }
 
-// rule 3: splitmix64's finaliser, and the counter-based sampler built on it
+// rule 3: splitmix64's finaliser; the counter-based sampler built on it is ransac_sample<8> (ebo_ransac.inc)
 __device__ __forceinline__ unsigned long long tv_mix(unsigned long long z)
 {
 	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
 	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
 	return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ void tv_sample(unsigned long long seed, int pair, int h, int n, int (&out)[8])
-{
-	const unsigned long long G = 0x9E3779B97F4A7C15ull;
-	unsigned long long x = tv_mix(seed + G);
-	x = tv_mix((x ^ static_cast<unsigned long long>(pair)) + G);
-	x = tv_mix((x ^ static_cast<unsigned long long>(h)) + G);
-	int pos[8], val[8];
-#pragma unroll
-	for (int d = 0; d < 8; ++d)
-	{
-		const unsigned long long r = tv_mix((x ^ static_cast<unsigned long long>(d)) + G);
-		const int j = d + static_cast<int>(static_cast<unsigned int>(r >> 32) % static_cast<unsigned int>(n - d));
-		int vj = j, vd = d;
-#pragma unroll
-		for (int e = 0; e < 8; ++e)
-		{
-			if (e < d)  // later records override earlier ones
-			{
-				vj = (pos[e] == j) ? val[e] : vj;
-				vd = (pos[e] == d) ? val[e] : vd;
-			}
-		}
-		out[d] = vj;
-		pos[d] = j;
-		val[d] = vd;
-	}
 }
 
 // the rotation of rule 4 from (app, aqq, apq != 0): t, c, s
@@ -179,7 +150,19 @@ __device__ __forceinline__ void tv_cross(const double (&a)[3], const double (&b)
 	o[2] = __dsub_rn(__dmul_rn(a[0], b[1]), __dmul_rn(a[1], b[0]));
 }
 
+#include "ebo_ransac.inc"  // rule 3's sampler, and (kernels only) the counting, score and winner kernels
+
 #ifndef EBO_TWOVIEW_RULES_ONLY  // tools/two_view_serial.cpp compiles the rules above for the host and stops here
+
+// what ebo_ransac.inc's kernels need to know of this path
+struct TvProblem
+{
+	static constexpr int kSample = 8;
+	static __device__ __forceinline__ double score(const TvPoseRT& T, const double (&f1)[3], const double (&f2)[3])
+	{
+		return tv_score(T, f1, f2);
+	}
+};
 
 // Hypothesis kernel: one 16-lane group per (pair, hypothesis).  The 8 x 9 matrix A and the 9 x 9 matrix V of its
 // one-sided Jacobi iteration live in LDS; lane k of the group owns row k of both in every rotation (the element
@@ -214,7 +197,7 @@ __global__ void __launch_bounds__(256) k_tv_hypotheses(int nPairs, int H, const 
 	int smp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 	if (live)
 	{
-		tv_sample(seed, pair, h, n, smp);
+		ransac_sample<8>(seed, pair, h, n, smp);
 	}
 	if (l < 8)
 	{
@@ -470,150 +453,6 @@ __global__ void __launch_bounds__(256) k_tv_hypotheses(int nPairs, int H, const 
 		}
 		valid[g] = ok ? 1 : 0;
 	}
-}
-
-// Counting kernel: unit of work = (pair, hypothesis, correspondence).  A workgroup stages one tile of one pair's
-// bearing vectors in LDS and scores it against kTvHypChunk hypotheses, one wave per hypothesis at a time; a wave
-// counts its inliers with ballots and adds the integer to counts[] (zeroed before the launch): exact and order-free.
-// grid = (ceil(H / kTvHypChunk), nPairs, tiles of the largest pair)
-__global__ void __launch_bounds__(256) k_tv_count(int H, const int* __restrict__ offsets, const double* __restrict__ f1,
-												  const double* __restrict__ f2, const double* __restrict__ models,
-												  const int* __restrict__ valid, double threshold, int* __restrict__ counts)
-{
-	__shared__ double s1[3 * kTvTile];
-	__shared__ double s2[3 * kTvTile];
-	const int pair = blockIdx.y;
-	const long long base = offsets[pair];
-	const int n = offsets[pair + 1] - offsets[pair];
-	const int t0 = blockIdx.z * kTvTile;
-	if (n < 8 || t0 >= n)
-	{
-		return;  // the whole workgroup leaves together
-	}
-	const int nt = min(kTvTile, n - t0);
-	for (int e = threadIdx.x; e < 3 * nt; e += 256)
-	{
-		s1[e] = f1[3 * (base + t0) + e];
-		s2[e] = f2[3 * (base + t0) + e];
-	}
-	__syncthreads();
-	const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-	for (int hh = wave; hh < kTvHypChunk; hh += 4)
-	{
-		const int h = blockIdx.x * kTvHypChunk + hh;
-		if (h >= H)
-		{
-			break;
-		}
-		const long long g = static_cast<long long>(pair) * H + h;
-		if (!valid[g])
-		{
-			continue;
-		}
-		const TvPoseRT T = tv_load_pose(models + 12 * g);
-		int cnt = 0;
-		for (int i0 = 0; i0 < nt; i0 += 64)
-		{
-			const int i = i0 + lane;
-			bool in = false;
-			if (i < nt)
-			{
-				const double a1[3] = {s1[3 * i], s1[3 * i + 1], s1[3 * i + 2]};
-				const double a2[3] = {s2[3 * i], s2[3 * i + 1], s2[3 * i + 2]};
-				in = tv_score(T, a1, a2) < threshold;
-			}
-			cnt += __popcll(__ballot(in));
-		}
-		if (lane == 0 && cnt)
-		{
-			atomicAdd(counts + g, cnt);
-		}
-	}
-}
-
-struct TvModelArg
-{
-	double m[12];
-};
-
-__device__ __forceinline__ TvPoseRT tv_pose_of(const TvModelArg& a)
-{
-	TvPoseRT T;
-#pragma unroll
-	for (int i = 0; i < 3; ++i)
-	{
-#pragma unroll
-		for (int j = 0; j < 3; ++j)
-		{
-			T.R[i][j] = a.m[4 * i + j];
-		}
-		T.t[i] = a.m[4 * i + 3];
-	}
-	return T;
-}
-
-// one lane per correspondence: score and inlier flag for a given model (either output may be null)
-__global__ void __launch_bounds__(256) k_tv_scores(TvModelArg model, int n, const double* __restrict__ f1,
-												   const double* __restrict__ f2, double threshold,
-												   double* __restrict__ scores, unsigned char* __restrict__ flags)
-{
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n)
-	{
-		return;
-	}
-	const TvPoseRT T = tv_pose_of(model);
-	const size_t o = 3 * static_cast<size_t>(i);
-	const double a1[3] = {f1[o], f1[o + 1], f1[o + 2]};
-	const double a2[3] = {f2[o], f2[o + 1], f2[o + 2]};
-	const double s = tv_score(T, a1, a2);
-	if (scores)
-	{
-		scores[i] = s;
-	}
-	if (flags)
-	{
-		flags[i] = s < threshold ? 1 : 0;
-	}
-}
-
-// the winners' inlier flags, all pairs in one launch: grid = (ceil(largest pair / 256), nPairs).  winner[pair] < 0
-// (no hypothesis: fewer than 8 correspondences) clears the pair's flags.  Lane 0 of a pair's first workgroup copies
-// the winner's model to winModels[pair][12] (zeros when there is none).
-__global__ void __launch_bounds__(256) k_tv_winner_flags(int H, const int* __restrict__ offsets, const double* __restrict__ f1,
-														 const double* __restrict__ f2, const double* __restrict__ models,
-														 const int* __restrict__ valid, const int* __restrict__ winner,
-														 double threshold, unsigned char* __restrict__ flags,
-														 double* __restrict__ winModels)
-{
-	const int pair = blockIdx.y;
-	const long long base = offsets[pair];
-	const int n = offsets[pair + 1] - offsets[pair];
-	const int w = winner[pair];
-	const long long g = static_cast<long long>(pair) * H + (w < 0 ? 0 : w);
-	const bool have = w >= 0 && w < H && valid[g] != 0;
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i == 0)
-	{
-		for (int e = 0; e < 12; ++e)
-		{
-			winModels[12 * pair + e] = have ? models[12 * g + e] : 0.0;
-		}
-	}
-	if (i >= n)
-	{
-		return;
-	}
-	unsigned char f = 0;
-	if (have)
-	{
-		const TvPoseRT T = tv_load_pose(models + 12 * g);
-		const size_t o = 3 * static_cast<size_t>(base + i);
-		const double a1[3] = {f1[o], f1[o + 1], f1[o + 2]};
-		const double a2[3] = {f2[o], f2[o + 1], f2[o + 2]};
-		f = tv_score(T, a1, a2) < threshold ? 1 : 0;
-	}
-	flags[base + i] = f;
 }
 
 // one lane per correspondence, a pose pair per point: world point = pose1 * triangulate2(pose1^-1 * pose2, f1, f2)

@@ -57,7 +57,7 @@ std::vector<double> readAll(const char* path)
 bool solve(const double* f, const double* pts, int n, unsigned long long seed, int frame, int h, TvPoseRT& out)
 {
 	int smp[4];
-	ap_sample(seed, frame, h, n, smp);
+	ransac_sample<4>(seed, frame, h, n, smp);
 	double sf[4][3], sp[4][3];
 	for (int i = 0; i < 4; ++i)
 	{

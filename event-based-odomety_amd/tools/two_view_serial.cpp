@@ -53,7 +53,7 @@ std::vector<double> readAll(const char* path)
 bool solve(const double* f1, const double* f2, int n, unsigned long long seed, int pair, int h, TvPoseRT& out)
 {
 	int smp[8];
-	tv_sample(seed, pair, h, n, smp);
+	ransac_sample<8>(seed, pair, h, n, smp);
 	double S1[8][3], S2[8][3], A[8][9], V[9][9];
 	for (int i = 0; i < 8; ++i)
 	{

@@ -403,7 +403,7 @@ def make_scene(seed, n=200, outliers=0.3, noise_px=0.3, angle=0.4, dist=1.0):
 # the scenes of the GPU tests: (scene seed, n, outlier share, noise in pixels)
 SCENES = [(1, 200, 0.0, 0.3), (2, 200, 0.2, 0.3), (3, 200, 0.3, 0.3), (4, 40, 0.2, 0.3)]
 RANSAC_SEED = 7
-# the sizes of the score tests (wave and tile edges of k_ap_count's shape), scene seed = 100 + n
+# the sizes of the score tests (wave and tile edges of the counting kernel's shape), scene seed = 100 + n
 SCORE_SIZES = (1, 63, 64, 65, 1023, 1024, 1025, 2049, 10000)
 # the frames of the batched call: sizes, with one of 3 points and one of exactly 4; scene seed = 200 + position
 BATCH_SIZES = (200, 3, 75, 4, 130, 64)

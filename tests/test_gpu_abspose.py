@@ -179,6 +179,49 @@ def test_counts_winner_and_inliers_are_equal_integers(ebo, ref_runs, batch_runs,
                 assert np.array_equal(plain[i]["inliers"], want_inl) and plain[i]["winner"] == winner
 
 
+def test_counts_where_a_frame_spans_several_tiles(ebo):
+    """The counting kernel stages a frame in tiles of 1024 points, one workgroup per (tile, 8 hypotheses), all of them
+    adding into the frame's counts: frames of 1023, 1024, 1025 and 2049 points (one tile less one, one exactly, a second
+    tile of one, a third of one) and one of 3 (below the sample) in one call of 16 hypotheses.  The yardstick is the
+    restatement's score of every point under the DEVICE's own pose of each hypothesis: the per-point scores are
+    bit-equal to it (test_scores_and_flags_are_bit_equal), so the counts are equal integers with no allowance near the
+    threshold and without the restatement's hypothesis solver."""
+    sizes, H = (1023, 1024, 3, 1025, 2049), 16
+    scenes = [ap.make_scene(400 + k, n=n, outliers=0.2, noise_px=0.3) for k, n in enumerate(sizes)]
+    f = np.concatenate([sc["f"] for sc in scenes])
+    p = np.concatenate([sc["points"] for sc in scenes])
+    offsets = np.concatenate([[0], np.cumsum(sizes)])
+    prm = params(ebo, max_iterations=H)
+    with ebo.Context(loss=ebo.LOSS_VARIANCE) as c:
+        res, diag = c.absolute_pose_ransac(offsets, f, p, prm, diagnostics=True)
+        again, adiag = c.absolute_pose_ransac(offsets, f, p, prm, diagnostics=True)
+    beyond_first_tile = 0
+    for i, (sc, n) in enumerate(zip(scenes, sizes)):
+        models, counts, r = diag["models"][i], diag["counts"][i], res[i]
+        valid = np.abs(np.nan_to_num(models, nan=1.0)).reshape(H, -1).max(axis=1) > 0
+        assert np.array_equal(counts, adiag["counts"][i]) and same(models, adiag["models"][i])
+        assert (r["found"], r["winner"], r["iterations"], r["n_inliers"]) == (
+            again[i]["found"], again[i]["winner"], again[i]["iterations"], again[i]["n_inliers"])
+        assert np.array_equal(r["inliers"], again[i]["inliers"])
+        if n < 4:
+            assert not valid.any() and not counts.any()
+            assert (r["found"], r["winner"], r["iterations"], r["n_inliers"]) == (False, -1, 0, 0) and len(r["inliers"]) == 0
+            continue
+        inl = ap.inliers(ap.scores(models, sc["f"], sc["points"])) & valid[:, None]
+        want = inl.sum(axis=1).astype(np.int32)
+        print("n=%d: %d valid hypotheses, device counts %s, restatement under the device's poses %s" % (
+            n, int(valid.sum()), counts.tolist(), want.tolist()))
+        assert valid.any()
+        assert np.array_equal(counts, want)
+        assert not counts[~valid].any()
+        have = bool(np.abs(np.nan_to_num(r["model"], nan=1.0)).max() > 0)
+        want_inl = np.flatnonzero(ap.inliers(ap.scores(r["model"], sc["f"], sc["points"]))) if have else np.zeros(0, dtype=np.int64)
+        assert np.array_equal(r["inliers"], want_inl) and r["n_inliers"] == len(want_inl)
+        assert r["n_inliers"] == counts[r["winner"]] and same(r["model"], models[r["winner"]])
+        beyond_first_tile += int((inl[:, 1024:]).sum())
+    assert beyond_first_tile > 0   # otherwise the later tiles added nothing and this test shows nothing
+
+
 def test_device_form_matches_host_form(ebo, ref_runs):
     import torch
     sc, run = ref_runs[2]

@@ -225,6 +225,49 @@ def test_counts_winner_and_inliers_are_equal_integers(ebo, ref_runs, max_iterati
             assert np.array_equal(plain[i]["inliers"], want_inl) and plain[i]["winner"] == winner
 
 
+def test_counts_where_a_pair_spans_several_tiles(ebo):
+    """The counting kernel stages a pair in tiles of 1024 correspondences, one workgroup per (tile, 8 hypotheses), all of
+    them adding into the pair's counts: pairs of 1023, 1024, 1025 and 2049 correspondences (one tile less one, one
+    exactly, a second tile of one, a third of one) and one of 7 (below the sample) in one call of 16 hypotheses.  The
+    yardstick is the restatement's score of every correspondence under the DEVICE's own model of each hypothesis: the
+    per-point scores are bit-equal to it (test_per_point_forms_are_bit_equal), so the counts are equal integers with no
+    allowance near the threshold and without the restatement's hypothesis solver."""
+    sizes, H = (1023, 1024, 7, 1025, 2049), 16
+    scenes = [tv.make_scene(400 + k, n, 0.1, 0.3) for k, n in enumerate(sizes)]
+    f1 = np.concatenate([sc["f1"] for sc in scenes])
+    f2 = np.concatenate([sc["f2"] for sc in scenes])
+    offsets = np.concatenate([[0], np.cumsum(sizes)])
+    prm = ebo.two_view_params(seed=tv.RANSAC_SEED, max_iterations=H)
+    with ebo.Context(loss=ebo.LOSS_VARIANCE) as c:
+        res, diag = c.relative_pose_ransac(offsets, f1, f2, prm, diagnostics=True)
+        again, adiag = c.relative_pose_ransac(offsets, f1, f2, prm, diagnostics=True)
+    beyond_first_tile = 0
+    for i, (sc, n) in enumerate(zip(scenes, sizes)):
+        models, counts, r = diag["models"][i], diag["counts"][i], res[i]
+        valid = np.abs(np.nan_to_num(models, nan=1.0)).reshape(H, -1).max(axis=1) > 0
+        assert np.array_equal(counts, adiag["counts"][i]) and same(models, adiag["models"][i])
+        assert (r["found"], r["winner"], r["iterations"], r["n_inliers"]) == (
+            again[i]["found"], again[i]["winner"], again[i]["iterations"], again[i]["n_inliers"])
+        assert np.array_equal(r["inliers"], again[i]["inliers"])
+        if n < 8:
+            assert not valid.any() and not counts.any()
+            assert (r["found"], r["winner"], r["iterations"], r["n_inliers"]) == (False, -1, 0, 0) and len(r["inliers"]) == 0
+            continue
+        inl = tv.inliers(tv.scores(models, sc["f1"], sc["f2"])) & valid[:, None]
+        want = inl.sum(axis=1).astype(np.int32)
+        print("n=%d: %d valid hypotheses, device counts %s, restatement under the device's models %s" % (
+            n, int(valid.sum()), counts.tolist(), want.tolist()))
+        assert valid.any()
+        assert np.array_equal(counts, want)
+        assert not counts[~valid].any()
+        have = bool(np.abs(np.nan_to_num(r["model"], nan=1.0)).max() > 0)
+        want_inl = np.flatnonzero(tv.inliers(tv.scores(r["model"], sc["f1"], sc["f2"]))) if have else np.zeros(0, dtype=np.int64)
+        assert np.array_equal(r["inliers"], want_inl) and r["n_inliers"] == len(want_inl)
+        assert r["n_inliers"] == counts[r["winner"]] and same(r["model"], models[r["winner"]])
+        beyond_first_tile += int((inl[:, 1024:]).sum())
+    assert beyond_first_tile > 0   # otherwise the later tiles added nothing and this test shows nothing
+
+
 def test_device_form_matches_host_form(ebo, ref_runs):
     import torch
     sc, run = ref_runs[0]
