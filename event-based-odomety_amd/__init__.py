@@ -214,6 +214,9 @@ def lib():
         _lib.ebo_bundle_adjust_device.argtypes = _ba
         _lib.ebo_default_ba_opts.argtypes = [C.c_void_p]
         _lib.ebo_default_ba_opts.restype = None
+        _rr = [C.c_void_p, C.c_int] + [C.c_void_p] * 9
+        _lib.ebo_relative_pose_refine.argtypes = _rr
+        _lib.ebo_relative_pose_refine_device.argtypes = _rr
         _lib.ebo_absolute_pose_scores.argtypes = _sc
         _lib.ebo_absolute_pose_scores_device.argtypes = _sc
         _tr = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1276,6 +1279,58 @@ class Context:
         self._check(lib().ebo_bundle_adjust_device(self._h, n, _vp(fo), _vp(po), _vp(oo), p(d_poses), p(d_fixed), p(d_points),
                                                    p(d_of), p(d_op), p(d_uv), C.addressof(cam), C.c_double(huber),
                                                    1 if fix_points else 0, C.addressof(o), C.addressof(summ), p(d_trace)))
+        return [{f: getattr(summ[k], f) for f, _ in Summary._fields_} for k in range(n)]
+
+    # -- relative-pose refinement (five-variable LM over each pair's RANSAC inliers) ---------------------
+    def relative_pose_refine(self, pairs, opts=None, trace=False):
+        """ebo_relative_pose_refine over a list of pairs, each a dict of model float64 [3][4], f1 / f2 [n][3] and idx
+        int [m] (the listed inliers, indices within the pair).  -> list of dicts (model, summary = dict of the
+        ebo_summary fields, and with trace=True trace [max_num_iterations + 1][4])."""
+        o = opts if opts is not None else default_ba_opts()
+        n = len(pairs)
+        sizes = [np.asarray(p["f1"]).size // 3 for p in pairs]
+        off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(sizes)]), dtype=np.int32)
+        total = int(off[-1])
+        f1 = np.zeros((max(total, 1), 3))
+        f2 = np.zeros((max(total, 1), 3))
+        idx = np.zeros(max(total, 1), dtype=np.int32)
+        cnt = np.zeros(max(n, 1), dtype=np.int32)
+        models = np.zeros((max(n, 1), 12))
+        for k, p in enumerate(pairs):
+            f1[off[k]:off[k + 1]] = np.asarray(p["f1"], dtype=np.float64).reshape(-1, 3)
+            f2[off[k]:off[k + 1]] = np.asarray(p["f2"], dtype=np.float64).reshape(-1, 3)
+            li = np.asarray(p["idx"], dtype=np.int32).reshape(-1)
+            if len(li) > sizes[k]:
+                raise ValueError("a pair lists more inliers than it holds correspondences")
+            idx[off[k]:off[k] + len(li)] = li
+            cnt[k] = len(li)
+            models[k] = np.asarray(p["model"], dtype=np.float64).reshape(12)
+        summ = (Summary * max(n, 1))()
+        rows = int(o.max_num_iterations) + 1
+        tr = np.zeros((max(n, 1), max(rows, 1), 4)) if trace else None
+        self._check(lib().ebo_relative_pose_refine(self._h, n, _vp(off), _vp(f1), _vp(f2), _vp(models), _vp(cnt), _vp(idx),
+                                                   C.addressof(o), C.addressof(summ), _vp(tr) if trace else None))
+        out = []
+        for k in range(n):
+            d = dict(model=models[k].reshape(3, 4).copy(), summary={f: getattr(summ[k], f) for f, _ in Summary._fields_})
+            if trace:
+                d["trace"] = tr[k].copy()
+            out.append(d)
+        return out
+
+    def relative_pose_refine_device(self, offsets, d_f1, d_f2, d_models, n_inliers, d_inlier_idx, opts=None, d_trace=0):
+        """ebo_relative_pose_refine_device: host int32 offsets and inlier counts, device pointers as int; the models are
+        updated in place on the device.  -> list of summary dicts."""
+        o = opts if opts is not None else default_ba_opts()
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        cnt = np.ascontiguousarray(n_inliers, dtype=np.int32).reshape(-1)
+        n = len(off) - 1
+        if len(cnt) != n:
+            raise ValueError("n_inliers must hold one count per pair")
+        summ = (Summary * max(n, 1))()
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        self._check(lib().ebo_relative_pose_refine_device(self._h, n, _vp(off), p(d_f1), p(d_f2), p(d_models), _vp(cnt),
+                                                          p(d_inlier_idx), C.addressof(o), C.addressof(summ), p(d_trace)))
         return [{f: getattr(summ[k], f) for f, _ in Summary._fields_} for k in range(n)]
 
     def triangulate(self, poses, pose_pair, f1, f2):

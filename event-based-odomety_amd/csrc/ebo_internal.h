@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/ebo.h"
 #include "ebo_bundle.h"
+#include "ebo_relpose.h"
 
 namespace ebo
 {
@@ -560,5 +561,12 @@ struct BaTables
 // (the _device form cannot read the flags): up to 83.5 KB at 24 frames.  d_trace may be null
 int launch_bundle_adjust(int n_problems, int max_frames, const BaTables& t, const ebo_camera& cam, double huber, int fix_points,
 						 const ebo_solver_opts& o, ebo_summary* d_summaries, double* d_trace, void* stream);
+
+// relative-pose refinement (ebo_relpose.inc, ebo_relpose.cpp): pair p owns correspondences d_offsets[p] .. d_offsets[p + 1] - 1
+// of d_f1 / d_f2; its d_n_inliers[p] listed inliers and its slice of d_work (rp_work_doubles of d_offsets[n_pairs], ebo_relpose.h)
+// start at d_offsets[p] too.  d_trace may be null
+int launch_relpose_refine(int n_pairs, const int* d_offsets, const int* d_n_inliers, const double* d_f1, const double* d_f2,
+						  const int* d_inlier_idx, double* d_models, double* d_work, const ebo_solver_opts& o, ebo_summary* d_summaries,
+						  double* d_trace, void* stream);
 
 }  // namespace ebo

@@ -1270,6 +1270,7 @@ __global__ void __launch_bounds__(64) k_route(const uint32_t* __restrict__ xy, u
 #include "ebo_twoview.inc"
 #include "ebo_abspose.inc"
 #include "ebo_bundle.inc"
+#include "ebo_relpose.inc"
 #include "ebo_field.inc"
 #include "ebo_fieldtv.inc"
 #include "ebo_optimizer.inc"
@@ -1935,6 +1936,20 @@ int launch_bundle_adjust(int n_problems, int max_frames, const BaTables& t, cons
 	}
 	hipLaunchKernelGGL(k_bundle_adjust, dim3(n_problems), dim3(kBaLanes), lds, static_cast<hipStream_t>(stream), t, cam, huber,
 					   fix_points, o, d_summaries, d_trace);
+	return check_launch();
+}
+
+// relative-pose refinement (ebo_relpose.inc): one wave per pair
+int launch_relpose_refine(int n_pairs, const int* d_offsets, const int* d_n_inliers, const double* d_f1, const double* d_f2,
+						  const int* d_inlier_idx, double* d_models, double* d_work, const ebo_solver_opts& o, ebo_summary* d_summaries,
+						  double* d_trace, void* stream)
+{
+	if (n_pairs <= 0)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_relpose_refine, dim3(n_pairs), dim3(kRpLanes), 0, static_cast<hipStream_t>(stream), d_offsets, d_n_inliers, d_f1,
+					   d_f2, d_inlier_idx, d_models, d_work, o, d_summaries, d_trace);
 	return check_launch();
 }
 

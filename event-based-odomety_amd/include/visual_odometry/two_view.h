@@ -15,7 +15,8 @@
 //   * the relative pose comes from ebo_relative_pose_ransac (include/ebo.h "two-view geometry", rules 1-6), this
 //     project's own statement of eight-point RANSAC: parity with OpenGV is not claimed;
 //   * where the reference calls opengv::relative_pose::optimize_nonlinear the caller may plug a refinement in
-//     (setRefinement); there is none by default and the RANSAC model is used as it is;
+//     (setRefinement); there is none by default and the RANSAC model is used as it is; useDeviceRefinement() installs
+//     ebo_relative_pose_refine over the RANSAC inliers (relative_refinement.h);
 //   * absolute pose, bundle adjustment and the ground-truth alignment are not here.
 #pragma once
 
@@ -23,9 +24,11 @@
 #include <cmath>
 #include <cstdint>
 #include <functional>
+#include <memory>
 #include <vector>
 
 #include "../common/camera_model.h"
+#include "relative_refinement.h"
 #include "triangulation.h"
 
 namespace visual_odometry
@@ -61,6 +64,20 @@ class TwoViewInitializer
 	}
 
 	void setRefinement(Refinement refinement) { refinement_ = std::move(refinement); }
+	// the refinement after the RANSAC (visual_odometry.cpp:316-330) on the device, over the RANSAC inliers, with
+	// params.maxNumIterations; lastRefinement() is its summary
+	void useDeviceRefinement()
+	{
+		// the hook holds what it needs by value, so the initializer stays copyable; a copy shares the summary
+		ebo_ctx* ctx = ctx_;
+		const size_t maxNumIterations = params_.maxNumIterations;
+		std::shared_ptr<ebo_summary> summary = lastRefinement_;
+		refinement_ = [ctx, maxNumIterations, summary](const common::Pose3d& model, const bearingVectors_t& f1, const bearingVectors_t& f2,
+													   const std::vector<int>& inliers) {
+			return refineRelativePose(ctx, maxNumIterations, model, f1, f2, inliers, summary.get());
+		};
+	}
+	const ebo_summary& lastRefinement() const { return *lastRefinement_; }
 	// max_iterations, probability and seed of the RANSAC; the threshold follows VisualOdometryParams::ransacThreshold
 	ebo_two_view_params& ransacParams() { return ransac_; }
 	const ebo_two_view_result& lastRansac() const { return last_; }
@@ -220,6 +237,7 @@ class TwoViewInitializer
 	VisualOdometryParams params_;
 	ebo_two_view_params ransac_;
 	ebo_two_view_result last_{};
+	std::shared_ptr<ebo_summary> lastRefinement_ = std::make_shared<ebo_summary>();
 	Refinement refinement_;
 	MapLandmarks mapLandmarks_;
 	Keyframe start_, second_;

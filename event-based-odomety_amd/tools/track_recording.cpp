@@ -1,6 +1,6 @@
 // track_recording — the reference's feature-tracking experiment on a DAVIS240C recording directory, without OpenCV:
 //
-//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--odometry [--bundle-adjust] [--refine]]
+//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--odometry [--bundle-adjust] [--refine] [--refine-two-view]]
 //
 // DIR holds events.txt, images.txt + the frames (8-bit grey PNG), optionally groundtruth.txt / calib.txt.
 // --rectify: the events of every compensation window are undistorted with the recording's calib.txt as they are
@@ -13,6 +13,8 @@
 // --bundle-adjust, --refine (both need --odometry): the front end's optimize() after every added keyframe and the
 // refinement after localizeCamera's RANSAC, both through ebo_bundle_adjust (useDeviceBundleAdjustment,
 // useDeviceLocalizeRefinement).
+// --refine-two-view (needs --odometry): the refinement after the two-view RANSAC of initCameras through
+// ebo_relative_pose_refine (twoView().useDeviceRefinement()).
 // Writes OUT/trajectory.txt and OUT/final_cost.txt and prints one JSON line: frames, events, tracks (archived patches),
 // compensation windows, total ms (construction to the files written), ms per frame interval and Mevents/s.
 // Built by `make -C event-based-odomety_amd/csrc track_recording`.
@@ -29,7 +31,7 @@
 
 static int usage(const char* argv0)
 {
-	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--odometry [--bundle-adjust] [--refine]]\n", argv0);
+	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--odometry [--bundle-adjust] [--refine] [--refine-two-view]]\n", argv0);
 	return 2;
 }
 
@@ -39,7 +41,7 @@ int main(int argc, char** argv)
 	bool trackerExperiment = false;
 	size_t windowBatch = 1;
 	bool rectify = false;
-	bool odometry = false, bundleAdjust = false, refine = false;
+	bool odometry = false, bundleAdjust = false, refine = false, refineTwoView = false;
 	for (int i = 1; i < argc; ++i)
 	{
 		const std::string a = argv[i];
@@ -71,6 +73,10 @@ int main(int argc, char** argv)
 		{
 			refine = true;
 		}
+		else if (a == "--refine-two-view")
+		{
+			refineTwoView = true;
+		}
 		else if (a == "--window-batch" && i + 1 < argc)
 		{
 			char* end = nullptr;
@@ -86,7 +92,7 @@ int main(int argc, char** argv)
 			return usage(argv[0]);
 		}
 	}
-	if (dataset.empty() || out.empty() || ((bundleAdjust || refine) && !odometry))
+	if (dataset.empty() || out.empty() || ((bundleAdjust || refine || refineTwoView) && !odometry))
 	{
 		return usage(argv[0]);
 	}
@@ -128,6 +134,10 @@ int main(int argc, char** argv)
 				if (refine)
 				{
 					frontEnd->useDeviceLocalizeRefinement();
+				}
+				if (refineTwoView)
+				{
+					frontEnd->twoView().useDeviceRefinement();
 				}
 				hook = [&](const tracker::Patches& patches, const common::timestamp_t& t) {
 					visual_odometry::Keyframe keyframe(patches, t);

@@ -895,6 +895,78 @@ int ebo_triangulate_device(ebo_ctx* ctx, int n_poses, const double* d_poses, int
 int ebo_epipolar_inliers(ebo_ctx* ctx, const double* model, int n, const double* f1, const double* f2, double threshold,
 						 uint8_t* flags);
 
+/* ---- relative-pose refinement: five-variable Levenberg-Marquardt over a pair's RANSAC inliers ----------------
+ * What findInliersRansac does after its RANSAC through OpenGV's relative_pose::optimize_nonlinear
+ * (visual_odometry.cpp:316-330), stated as this project's own rules for MANY keyframe pairs in one call.  Parity with
+ * OpenGV is NOT claimed (INTEGRATION.md 7 lists the differences).  tests/relpose_ref.py restates every rule in numpy.
+ * Float64, one rounding per operation in the association written here, no contraction, only + - * / sqrt and
+ * comparisons, a comparison with a NaN is false, every sum in a stated order.  model, f1, f2, dot and cross are the
+ * two-view section's; B4, B6-B9 are the bundle adjustment's, further down.
+ *
+ * R1. Entry.  A pair with fewer than 5 listed inliers is not refined: iterations 0, termination 1, costs 0, the model
+ *     untouched.  When an entry of the model or of ANY bearing vector of the pair (listed or not) is not finite, when
+ *     a listed index is outside the pair, or when n = sqrt(dot(t, t)) is not > 0 or not finite: termination 2,
+ *     iterations 0, costs 0, the model returned bit for bit.  Otherwise t = t / n, entry by entry, is the start, and
+ *     unless its cost is not finite (B9: termination 2, the model returned bit for bit) the start is the first point
+ *     visited, so what comes back has a unit t even when no step is taken.
+ * R2. Tangent basis at a point (R, t):  k = the index of the smallest |t_k|, the first of equals;
+ *       w = (0, t2, -t1) for k = 0, (-t2, 0, t0) for k = 1, (t1, -t0, 0) for k = 2    (= cross(t, axis k));
+ *       e1 = w / sqrt(dot(w, w));  e2 = cross(t, e1).
+ * R3. Residual.  For listed inlier i, in list order, p, r1, q, r2 are those of rules 1-2 of the two-view section, in
+ *     their operations.  Its six residuals are the chords c = (f1 - r1, f2 - r2), rows 0 .. 5; their squared norm is
+ *     2 * score up to rounding.  No loss function: the list holds inliers only.
+ * R4. Variables and Jacobian.  Five variables (a, b, om_x, om_y, om_z), columns 0 .. 4.  J[k][s] = the derivative
+ *     of row k along variable s, by forward mode through every operation of R3, one derivative slot per variable;
+ *     .v is a quantity's value and .d its slot:
+ *       x * y: x.v * y.d + y.v * x.d;   c * x and x / c with c a constant (an entry of f1 or f2, a00, the 2 of
+ *       rule 1): c * x.d and x.d / c;   x / y: (x.d - (x.v / y.v) * y.d) / y.v;   sqrt(x): x.d / (2 * sqrt(x.v));
+ *       sums, differences and negations termwise (dot's in its association); f - r: -(r.d).
+ *     No term is left out because its slot is zero.  Seeds at the point (R, t) with R2's basis:
+ *       a: t.d = e1;  b: t.d = e2;  (R.d = 0)        om_x: R.d[i][:] = (0, R[i][2], -R[i][1]);
+ *       om_y: R.d[i][:] = (-R[i][2], 0, R[i][0]);  om_z: R.d[i][:] = (R[i][1], -R[i][0], 0);  (t.d = 0)
+ *     i.e. R hat(e_k).  Every entry is then multiplied by the scale of its column (R7): J[k][s] = c_k.d * scale_s.
+ * R5. Update by a step whose entries were first multiplied by their columns' scales, with R2's basis at (R, t):
+ *       t'_i = (t_i + (a * e1_i + b * e2_i)) / sqrt(1 + (a * a + b * b));
+ *       R'[i][j] = dot(R[i][:], C[:][j]) with C the matrix of B4 for om.
+ *     (e1, e2, t are orthonormal, so the divisor is the sum's length; written this way, like B4's quaternion, the
+ *     update is exactly the identity at a zero step.)  No sin / cos, no re-orthonormalisation.
+ * R6. Sums.  tree64(v): 64 partial sums, partial l = ((0 + v[l]) + v[l + 64]) + .. ; then for s = 32, 16, .., 1:
+ *     partial[i] = partial[i] + partial[i + s] for i < s; the result is partial[0].  With listed inlier i dealt to
+ *     partial i mod 64 and its rows taken in the order 0 .. 5, one product added at a time:
+ *       H[a][b] = tree64 of J[k][a] * J[k][b]  (b <= a; 15 sums),  g[a] = tree64 of J[k][a] * c_k,
+ *       cost = 0.5 * tree64 of c_k * c_k.
+ * R7. Scaling, damping, the step.  scale_s = 1 / (1 + sqrt(H[s][s])) from the sums at the start with all scales 1
+ *     (B6; opts->jacobi_scaling), fixed for the solve.  S = H with damp(H[a][a]) of B7 added to every diagonal entry;
+ *     S = L L^T, L y = g, L^T x = y in B8's words (5 rows); step = -x; a pivot that is not > 0 or not finite, or a
+ *     step entry that is not finite, makes the step invalid.
+ * R8. Trust region: B9 as it stands, with tree64 in place of tree, and
+ *       model cost change = -tree64 of mr_k * (c_k + mr_k / 2), rows as in R6,
+ *         mr_k = (((J[k][0] * step_0 + J[k][1] * step_1) + J[k][2] * step_2) + J[k][3] * step_3) + J[k][4] * step_4;
+ *       |x| = sqrt(tree64 of the squares of the model's 12 entries in array order), the step norm the same of
+ *         (x - candidate);   gradient norm = max over the 5 columns of |g_s / scale_s|.
+ *     R2's basis is taken anew at every point the solve moves to.  The result is the lowest-cost point visited.
+ *
+ * ebo_relative_pose_refine: offsets, f1, f2 as for ebo_relative_pose_ransac; models double [n_pairs][3][4], updated
+ *   in place; pair p's list is inlier_idx[offsets[p] .. offsets[p] + n_inliers[p]), indices WITHIN the pair in any
+ *   order: ebo_relative_pose_ransac's layout (model, n_inliers and inlier_offset of its results), so the call chains
+ *   straight off it.  One ebo_summary per pair (num_evals_jac counts Jacobian evaluations, num_evals_cost candidate
+ *   evaluations); trace_or_null in ebo_bundle_adjust's format, double [n_pairs][opts->max_num_iterations + 1][4].
+ *   opts as ebo_default_ba_opts fills them; opts->mode is not read.  The returned t has unit length.  A pair's result
+ *   depends neither on the other pairs of the call nor on the run.  Limits: 65535 correspondences per pair, 65535
+ *   pairs.  EBO_ERR_ARG beyond them and for an index outside its pair, offsets that decrease or do not start at 0,
+ *   an n_inliers that is negative or beyond its pair's size, a negative max_num_iterations, a needed pointer NULL.
+ *   EBO_ERR_STATE while a graph is being recorded.  Synchronous.
+ * ebo_relative_pose_refine_device: device pointers for f1, f2, inlier_idx, models and the trace; offsets, n_inliers
+ *   and the summaries stay host arrays.  It cannot look at the indices: a pair with one out of range is not solved
+ *   (R1: termination 2, its model untouched); the kernel checks before it starts.
+ * ebo_two_view_timing brackets both: slot [0] the kernel, [4] the whole call, the others 0. */
+int ebo_relative_pose_refine(ebo_ctx* ctx, int n_pairs, const int* offsets, const double* f1, const double* f2, double* models,
+							 const int* n_inliers, const int* inlier_idx, const ebo_solver_opts* opts, ebo_summary* summaries,
+							 double* trace_or_null);
+int ebo_relative_pose_refine_device(ebo_ctx* ctx, int n_pairs, const int* offsets, const double* d_f1, const double* d_f2,
+									double* d_models, const int* n_inliers, const int* d_inlier_idx, const ebo_solver_opts* opts,
+									ebo_summary* summaries, double* d_trace_or_null);
+
 /* ---- absolute pose: three-point RANSAC on (bearing vector, landmark) pairs ----------------------------
  * What VisualOdometryFrontEnd::localizeCamera (visual_odometry.cpp:212-286) does through OpenGV's
  * AbsolutePoseSacProblem(KNEIP), stated as this project's own rules (OpenGV's source is not part of the reference
