@@ -111,6 +111,12 @@ class Summary(C.Structure):
     ]
 
 
+class AlignResult(C.Structure):
+    """ebo_align_result: one segment's alignment and the reference's ErrorMetricValue fields."""
+    _fields_ = [("scale", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3), ("rmse", C.c_double),
+                ("mean", C.c_double), ("min", C.c_double), ("max", C.c_double), ("count", C.c_int32), ("status", C.c_int32)]
+
+
 def default_ba_opts(**over):
     """ebo_default_ba_opts (Ceres' Solver::Options defaults) as a SolverOpts; keyword arguments override fields."""
     o = SolverOpts()
@@ -217,6 +223,9 @@ def lib():
         _rr = [C.c_void_p, C.c_int] + [C.c_void_p] * 9
         _lib.ebo_relative_pose_refine.argtypes = _rr
         _lib.ebo_relative_pose_refine_device.argtypes = _rr
+        _al = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ebo_align_sim3.argtypes = _al
+        _lib.ebo_align_sim3_device.argtypes = _al
         _lib.ebo_absolute_pose_scores.argtypes = _sc
         _lib.ebo_absolute_pose_scores_device.argtypes = _sc
         _tr = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1332,6 +1341,44 @@ class Context:
         self._check(lib().ebo_relative_pose_refine_device(self._h, n, _vp(off), p(d_f1), p(d_f2), p(d_models), _vp(cnt),
                                                           p(d_inlier_idx), C.addressof(o), C.addressof(summ), p(d_trace)))
         return [{f: getattr(summ[k], f) for f, _ in Summary._fields_} for k in range(n)]
+
+    # -- trajectory alignment (Sim3 / SE3 of estimated centres onto ground truth, and the ATE) -------------
+    @staticmethod
+    def _align_out(res, n):
+        return [dict(scale=np.float64(r.scale), R=np.array(r.R[:], dtype=np.float64).reshape(3, 3),
+                     t=np.array(r.t[:], dtype=np.float64), rmse=np.float64(r.rmse), mean=np.float64(r.mean),
+                     min=np.float64(r.min), max=np.float64(r.max), count=int(r.count), status=int(r.status))
+                for r in res[:n]]
+
+    def align_sim3(self, data, model, segments, fix_scale=False):
+        """ebo_align_sim3: data (the ground-truth centres) and model (the estimated centres) float64 [n][3]; segments a
+        list of (begin, end) over both, which may overlap.  The fit is data ~ s R model + t.  -> one dict per segment:
+        scale, R [3][3], t [3], rmse, mean, min, max, count, status (0 aligned, 1 fewer than 3 points, 2 a non-finite
+        input, 3 degenerate)."""
+        data = np.ascontiguousarray(data, dtype=np.float64).reshape(-1, 3)
+        model = np.ascontiguousarray(model, dtype=np.float64).reshape(-1, 3)
+        if len(data) != len(model):
+            raise ValueError("data and model must hold the same number of points")
+        seg = np.asarray(segments, dtype=np.int32).reshape(-1, 2)
+        sb, se = np.ascontiguousarray(seg[:, 0]), np.ascontiguousarray(seg[:, 1])
+        n = len(seg)
+        res = (AlignResult * max(n, 1))()
+        self._check(lib().ebo_align_sim3(self._h, len(data), _vp(data) if len(data) else None,
+                                         _vp(model) if len(model) else None, n, _vp(sb) if n else None,
+                                         _vp(se) if n else None, 1 if fix_scale else 0, C.addressof(res)))
+        return self._align_out(res, n)
+
+    def align_sim3_device(self, n_points, d_data, d_model, segments, fix_scale=False):
+        """ebo_align_sim3_device: device pointers as int for data and model; the segments and the results stay on the
+        host.  -> as align_sim3."""
+        seg = np.asarray(segments, dtype=np.int32).reshape(-1, 2)
+        sb, se = np.ascontiguousarray(seg[:, 0]), np.ascontiguousarray(seg[:, 1])
+        n = len(seg)
+        res = (AlignResult * max(n, 1))()
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        self._check(lib().ebo_align_sim3_device(self._h, int(n_points), p(d_data), p(d_model), n, _vp(sb) if n else None,
+                                                _vp(se) if n else None, 1 if fix_scale else 0, C.addressof(res)))
+        return self._align_out(res, n)
 
     def triangulate(self, poses, pose_pair, f1, f2):
         """ebo_triangulate: poses float64 [n_poses][3][4] camera-to-world, pose_pair int [n][2] -> world points [n][3]."""

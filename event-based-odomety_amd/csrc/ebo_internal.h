@@ -12,6 +12,7 @@
 #include "../../include/ebo.h"
 #include "ebo_bundle.h"
 #include "ebo_relpose.h"
+#include "ebo_align.h"
 
 namespace ebo
 {
@@ -568,5 +569,10 @@ int launch_bundle_adjust(int n_problems, int max_frames, const BaTables& t, cons
 int launch_relpose_refine(int n_pairs, const int* d_offsets, const int* d_n_inliers, const double* d_f1, const double* d_f2,
 						  const int* d_inlier_idx, double* d_models, double* d_work, const ebo_solver_opts& o, ebo_summary* d_summaries,
 						  double* d_trace, void* stream);
+
+// trajectory alignment (ebo_align.inc, ebo_align.cpp): segment g covers points d_seg_begin[g] .. d_seg_end[g] - 1 of d_data and
+// d_model (double [n_points][3]); one result per segment
+int launch_align_sim3(int n_points, const double* d_data, const double* d_model, int n_segments, const int* d_seg_begin,
+					  const int* d_seg_end, int fix_scale, ebo_align_result* d_results, void* stream);
 
 }  // namespace ebo

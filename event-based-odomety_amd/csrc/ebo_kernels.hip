@@ -1271,6 +1271,7 @@ __global__ void __launch_bounds__(64) k_route(const uint32_t* __restrict__ xy, u
 #include "ebo_abspose.inc"
 #include "ebo_bundle.inc"
 #include "ebo_relpose.inc"
+#include "ebo_align.inc"
 #include "ebo_field.inc"
 #include "ebo_fieldtv.inc"
 #include "ebo_optimizer.inc"
@@ -1950,6 +1951,19 @@ int launch_relpose_refine(int n_pairs, const int* d_offsets, const int* d_n_inli
 	}
 	hipLaunchKernelGGL(k_relpose_refine, dim3(n_pairs), dim3(kRpLanes), 0, static_cast<hipStream_t>(stream), d_offsets, d_n_inliers, d_f1,
 					   d_f2, d_inlier_idx, d_models, d_work, o, d_summaries, d_trace);
+	return check_launch();
+}
+
+// trajectory alignment (ebo_align.inc): one wave per segment
+int launch_align_sim3(int n_points, const double* d_data, const double* d_model, int n_segments, const int* d_seg_begin,
+					  const int* d_seg_end, int fix_scale, ebo_align_result* d_results, void* stream)
+{
+	if (n_segments <= 0)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_align_sim3, dim3(n_segments), dim3(kRpLanes), 0, static_cast<hipStream_t>(stream), n_points, d_data, d_model,
+					   d_seg_begin, d_seg_end, fix_scale, d_results);
 	return check_launch();
 }
 

@@ -17,7 +17,8 @@
 //   * where the reference calls opengv::relative_pose::optimize_nonlinear the caller may plug a refinement in
 //     (setRefinement); there is none by default and the RANSAC model is used as it is; useDeviceRefinement() installs
 //     ebo_relative_pose_refine over the RANSAC inliers (relative_refinement.h);
-//   * absolute pose, bundle adjustment and the ground-truth alignment are not here.
+//   * absolute pose, bundle adjustment and the ground-truth alignment are not here: they are
+//     VisualOdometryFrontEnd's (visual_odometry.h, bundle_adjustment.h, aligner.h).
 #pragma once
 
 #include <algorithm>

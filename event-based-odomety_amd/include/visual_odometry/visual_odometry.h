@@ -25,13 +25,19 @@
 //   * deleteLandmarks moves the landmarks whose last observation went to storedLandmarks_ in ascending track id (the
 //     reference walks an unordered_map);
 //   * withoutAdd_, which the reference leaves uninitialised, starts at 0;
-//   * syncGtAndImage, the ground-truth alignment and the log lines are not here.
+//   * the ground truth is opt-in: with setGroundTruthSamples the gt_ bookkeeping of :62-71 runs, and with
+//     useDeviceAlignment() the alignment of :83-97 through ebo_align_sim3 (aligner.h; include/ebo.h "trajectory
+//     alignment", S1-S7, this project's own statement: parity with Eigen's JacobiSVD is not claimed).  The reference
+//     indexes gt_[i] by keyframe position even when a keyframe had no ground truth, which reads out of range; here a
+//     keyframe without a synced pose is left out of the pairing.  Without the two calls nothing of it runs;
+//   * the log lines are not here.
 #pragma once
 
 #include <list>
 #include <map>
 #include <utility>
 
+#include "aligner.h"
 #include "bundle_adjustment.h"
 #include "two_view.h"
 
@@ -77,6 +83,24 @@ class VisualOdometryFrontEnd
 			return refinePose(ctx_, params_.huberLoss, params_.maxNumIterations, pose, f, points, inliers, &lastRefinement_);
 		};
 	}
+	// visual_odometry.cpp:563-567; from here on every added keyframe is synced against the samples (:62-71)
+	void setGroundTruthSamples(const common::GroundTruth& groundTruthSamples)
+	{
+		groundTruthSamples_ = groundTruthSamples;
+		useGroundTruth_ = true;
+	}
+	// visual_odometry.cpp:522-561
+	std::optional<common::Pose3d> syncGtAndImage(const common::timestamp_t& timestamp) const
+	{
+		return syncGroundTruth(groundTruthSamples_, timestamp);
+	}
+	// the alignment after the optimizer (:83-97) on the device, once more than 5 keyframes exist
+	void useDeviceAlignment() { deviceAlignment_ = true; }
+	// of the last candidate that was aligned; status 1 and the identity before that
+	const Alignment& lastAlignment() const { return lastAlignment_; }
+	// the reference's getGtPoses(): the synced poses relative to the first, in keyframe order; after an alignment
+	// sim.inverse() * each of them
+	std::vector<common::Pose3d> const& alignedGroundTruth() const { return gtAligned_; }
 	const ebo_summary& lastBundleAdjustment() const { return lastBundle_; }
 	const ebo_summary& lastRefinement() const { return lastRefinement_; }
 	// the two-view layer that initCameras goes through (its refinement and RANSAC parameters are set there)
@@ -94,7 +118,7 @@ class VisualOdometryFrontEnd
 		return static_cast<double>(threshold);
 	}
 
-	// visual_odometry.cpp:52-104 without the ground truth and the log
+	// visual_odometry.cpp:52-104 without the log; the ground truth only when it was asked for
 	void newKeyframeCandidate(Keyframe& keyframe)
 	{
 		Match match;
@@ -105,11 +129,61 @@ class VisualOdometryFrontEnd
 			withoutAdd_++;
 			return;
 		}
+		if (useGroundTruth_)
+		{
+			const auto poseGt = syncGtAndImage(keyframe.timestamp);
+			if (poseGt.has_value())
+			{
+				if (gt_.empty())
+				{
+					zeroGt_ = poseGt.value();
+				}
+				gt_[static_cast<size_t>(keyframe.timestamp.count())] = zeroGt_.inverse() * poseGt.value();
+				gtAligned_.push_back(zeroGt_.inverse() * poseGt.value());
+			}
+		}
 		deleteKeyframe();
 		addKeyframe(keyframe, match);
 		if (optimizer_)
 		{
 			optimizer_(activeFrames_, mapLandmarks_);
+		}
+		if (deviceAlignment_)
+		{
+			alignToGroundTruth();
+		}
+	}
+
+	// visual_odometry.cpp:78-97: stored and active keyframes against their synced ground-truth poses, by their centres
+	void alignToGroundTruth()
+	{
+		if (storedFrames_.size() + activeFrames_.size() <= 5 || gt_.empty())
+		{
+			return;
+		}
+		std::vector<common::Vector3d> reference, cameras;
+		const auto pair = [&](const Keyframe& kf) {
+			const auto it = gt_.find(static_cast<size_t>(kf.timestamp.count()));
+			if (it != gt_.end())
+			{
+				reference.push_back(it->second.translation());
+				cameras.push_back(kf.pose.translation());
+			}
+		};
+		for (const auto& kf : storedFrames_)
+		{
+			pair(kf);
+		}
+		for (const auto& kf : activeFrames_)
+		{
+			pair(kf.second);
+		}
+		lastAlignment_ = alignPoints(ctx_, reference, cameras);
+		const common::Sim3 back = lastAlignment_.sim.inverse();
+		gtAligned_.clear();
+		for (const auto& kf : gt_)
+		{
+			gtAligned_.push_back(back * kf.second);
 		}
 	}
 
@@ -356,5 +430,13 @@ class VisualOdometryFrontEnd
 	std::vector<std::pair<tracker::TrackId, common::Vector3d>> storedLandmarks_;
 	size_t withoutAdd_ = 0;
 	Match match_;
+
+	bool useGroundTruth_ = false;
+	bool deviceAlignment_ = false;
+	common::GroundTruth groundTruthSamples_;
+	std::map<size_t, common::Pose3d> gt_;  // by keyframe timestamp, relative to the first synced pose
+	std::vector<common::Pose3d> gtAligned_;
+	common::Pose3d zeroGt_;
+	Alignment lastAlignment_;
 };
 }  // namespace visual_odometry

@@ -1,6 +1,6 @@
 // track_recording — the reference's feature-tracking experiment on a DAVIS240C recording directory, without OpenCV:
 //
-//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--odometry [--bundle-adjust] [--refine] [--refine-two-view]]
+//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--ate]]
 //
 // DIR holds events.txt, images.txt + the frames (8-bit grey PNG), optionally groundtruth.txt / calib.txt.
 // --rectify: the events of every compensation window are undistorted with the recording's calib.txt as they are
@@ -15,6 +15,13 @@
 // useDeviceLocalizeRefinement).
 // --refine-two-view (needs --odometry): the refinement after the two-view RANSAC of initCameras through
 // ebo_relative_pose_refine (twoView().useDeviceRefinement()).
+// --ate (needs --odometry and a groundtruth.txt with samples): at the end of the run every keyframe is synced against the
+// ground truth (visual_odometry::syncGroundTruth; a keyframe outside the samples' time span takes no part), and ONE
+// batched call (visual_odometry::alignPrefixes, ebo_align_sim3) aligns every prefix of 3 .. K keyframes of the final
+// trajectory: OUT/ate.txt gets "k rmse mean min max" per prefix, in the ground truth's unit of length, and
+// OUT/groundtruth_aligned.txt the synced poses relative to the first, taken into the estimate's frame by the inverse of
+// the last alignment (timestamp and [R | t] row by row).  The last line of ate.txt is printed with its status: a prefix
+// that cannot be aligned (a ground truth along a straight line is status 3) has zeros in its line.
 // Writes OUT/trajectory.txt and OUT/final_cost.txt and prints one JSON line: frames, events, tracks (archived patches),
 // compensation windows, total ms (construction to the files written), ms per frame interval and Mevents/s.
 // Built by `make -C event-based-odomety_amd/csrc track_recording`.
@@ -31,7 +38,7 @@
 
 static int usage(const char* argv0)
 {
-	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--odometry [--bundle-adjust] [--refine] [--refine-two-view]]\n", argv0);
+	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--ate]]\n", argv0);
 	return 2;
 }
 
@@ -41,7 +48,7 @@ int main(int argc, char** argv)
 	bool trackerExperiment = false;
 	size_t windowBatch = 1;
 	bool rectify = false;
-	bool odometry = false, bundleAdjust = false, refine = false, refineTwoView = false;
+	bool odometry = false, bundleAdjust = false, refine = false, refineTwoView = false, ate = false;
 	for (int i = 1; i < argc; ++i)
 	{
 		const std::string a = argv[i];
@@ -77,6 +84,10 @@ int main(int argc, char** argv)
 		{
 			refineTwoView = true;
 		}
+		else if (a == "--ate")
+		{
+			ate = true;
+		}
 		else if (a == "--window-batch" && i + 1 < argc)
 		{
 			char* end = nullptr;
@@ -96,6 +107,11 @@ int main(int argc, char** argv)
 	{
 		return usage(argv[0]);
 	}
+	if (ate && !odometry)
+	{
+		std::fprintf(stderr, "track_recording: --ate evaluates the odometry's trajectory and needs --odometry\n");
+		return 2;
+	}
 	try
 	{
 		const auto t0 = std::chrono::steady_clock::now();
@@ -104,6 +120,15 @@ int main(int argc, char** argv)
 		p.trackerExperiment = trackerExperiment;
 		p.windowBatch = windowBatch;
 		const auto recording = std::make_shared<tools::Davis240cRecording>(dataset);
+		common::GroundTruth groundTruth;
+		if (ate)
+		{
+			groundTruth = recording->getGroundTruth();
+			if (groundTruth.empty())
+			{
+				throw std::runtime_error("--ate needs " + dataset + "/groundtruth.txt with at least one sample");
+			}
+		}
 		if (rectify)
 		{
 			p.cameraModelParams = recording->getCalibration();
@@ -179,6 +204,66 @@ int main(int argc, char** argv)
 					line(kf.second);
 				}
 				std::fclose(f);
+				if (ate)
+				{
+					// the reference's gt_ bookkeeping (visual_odometry.cpp:62-71) over the final trajectory
+					std::vector<common::Vector3d> reference, cameras;
+					std::vector<std::pair<common::timestamp_t, common::Pose3d>> synced;
+					common::Pose3d zero;
+					const auto sync = [&](const visual_odometry::Keyframe& kf) {
+						const auto pose = visual_odometry::syncGroundTruth(groundTruth, kf.timestamp);
+						if (pose.has_value())
+						{
+							if (synced.empty())
+							{
+								zero = pose.value();
+							}
+							synced.emplace_back(kf.timestamp, zero.inverse() * pose.value());
+							reference.push_back(synced.back().second.translation());
+							cameras.push_back(kf.pose.translation());
+						}
+					};
+					for (const auto& kf : frontEnd->getStoredFrames())
+					{
+						sync(kf);
+					}
+					for (const auto& kf : frontEnd->getActiveFrames())
+					{
+						sync(kf.second);
+					}
+					if (synced.size() < 3)
+					{
+						throw std::runtime_error("--ate: fewer than 3 keyframes lie within the ground truth's time span");
+					}
+					const auto prefixes = visual_odometry::alignPrefixes(odometryCtx, reference, cameras, 3);
+					FILE* fa = std::fopen((out + "/ate.txt").c_str(), "w");
+					FILE* fg = std::fopen((out + "/groundtruth_aligned.txt").c_str(), "w");
+					if (!fa || !fg)
+					{
+						throw std::runtime_error("cannot write " + out + "/ate.txt or groundtruth_aligned.txt");
+					}
+					for (const auto& a : prefixes)
+					{
+						std::fprintf(fa, "%.0f %.17g %.17g %.17g %.17g\n", a.ate.count, a.ate.rmse, a.ate.mean, a.ate.min, a.ate.max);
+					}
+					const common::Sim3 back = prefixes.back().sim.inverse();
+					for (const auto& g : synced)
+					{
+						double m[12];
+						(back * g.second).toArray(m);
+						std::fprintf(fg, "%lld", static_cast<long long>(g.first.count()));
+						for (const double v : m)
+						{
+							std::fprintf(fg, " %.17g", v);
+						}
+						std::fprintf(fg, "\n");
+					}
+					std::fclose(fa);
+					std::fclose(fg);
+					const auto& last = prefixes.back();
+					std::printf("ate: %.0f %.17g %.17g %.17g %.17g (status %d)\n", last.ate.count, last.ate.rmse, last.ate.mean, last.ate.min,
+								last.ate.max, last.status);
+				}
 				landmarks = frontEnd->getMapLandmarks().landmarks.size() + frontEnd->getStoredLandmarks().size();
 			}
 		}

@@ -967,6 +967,64 @@ int ebo_relative_pose_refine_device(ebo_ctx* ctx, int n_pairs, const int* offset
 									double* d_models, const int* n_inliers, const int* d_inlier_idx, const ebo_solver_opts* opts,
 									ebo_summary* summaries, double* d_trace_or_null);
 
+/* ---- trajectory alignment: Sim3 / SE3 alignment of estimated camera centres to ground truth, and the ATE ------
+ * What newKeyframeCandidate does through align_cameras_sim3 / align_points_sim3 (aligner.cpp:27-114, called at
+ * visual_odometry.cpp:83-97) for all keyframes so far after every new keyframe, stated as this project's own rules for
+ * MANY trajectory segments in one call.  Parity with Eigen's JacobiSVD is NOT claimed (INTEGRATION.md 7 lists the
+ * differences).  tests/align_ref.py restates every rule in numpy.  Float64, one rounding per operation in the
+ * association written here, no contraction, only + - * / sqrt and comparisons, a comparison with a NaN is false,
+ * every sum in a stated order.  dot, cross and jacobi(M, sweeps) are the two-view section's, tree64 is R6's.
+ * `data` holds the ground-truth centres d_i and `model` the estimated centres m_i; the fit is
+ * data ~ s * R * model + t, the reference's direction.  A segment has n points, i counted from its start.
+ *
+ * S1. Entry.  n < 3: status 1.  A coordinate of the segment that is not finite, in either array: status 2.  In both
+ *     cases, and for status 3 below: scale 1, R the identity, t = 0, rmse = mean = min = max = 0, count = n.
+ * S2. Centroids.  With point i dealt to partial i mod 64:  cd_a = tree64 of d_a / double(n);  cm_a the same of m_a.
+ * S3. Centred sums.  dc = d - cd, mc = m - cm, entry by entry.  W[a][b] = tree64 of dc_a * mc_b (9 sums);
+ *     nm = tree64 of (mc0 * mc0 + mc1 * mc1) + mc2 * mc2.  Centred first, as the reference does: no raw moments, so
+ *     a trajectory far from the origin loses no digits.
+ * S4. Singular vectors.  G[j][k] = dot(W[:][j], W[:][k]);  (d, V) = jacobi(G, 8), ordered descending with their
+ *     columns by the compare-exchanges (0,1) (1,2) (0,1) of rule 4 (a swap only when strictly smaller).  Status 3
+ *     unless d1 > 0, d1 finite, d1 > d0 * 2^-46 (128 ulps of d0, what the iteration's rounding leaves of an exact
+ *     zero: a second singular value below 2^-23 of the first, a cloud thinner than about 1 : 2900, is a line to the
+ *     digits G carries and the rotation about it is not determined), nm > 0 and nm finite.
+ * S5. Rotation from the top two pairs only.  u0_i = dot(W[i][:], v0); n0 = sqrt(dot(u0, u0)); u0 = u0 / n0;
+ *     u1_i = dot(W[i][:], v1); h = dot(u0, u1); u1 = u1 - h * u0; n1 = sqrt(dot(u1, u1)); u1 = u1 / n1.  Status 3
+ *     unless n0 and n1 are > 0 and finite.  u2 = cross(u0, u1); v2 = cross(v0, v1);
+ *       R[i][j] = (u0_i * v0_j + u1_i * v1_j) + u2_i * v2_j.
+ *     The determinant is +1 by construction: this is the reference's diag(1, 1, +-1) reflection guard, and the
+ *     smallest singular pair is never read, so a planar trajectory is well conditioned.
+ * S6. Scale and translation.  s = (the nine products R[a][b] * W[a][b] added one at a time from 0 in row-major
+ *     order) / nm, which is the sum of dot(dc, R mc) over the points by S3's sums; s = 1 with fix_scale.
+ *     t_i = cd_i - s * dot(R[i][:], cm).
+ * S7. Errors.  r_k = d_k - (s * dot(R[k][:], m) + t_k);  q = dot(r, r);  e = sqrt(q), per point.
+ *     rmse = sqrt(tree64 of q / double(n));  mean = tree64 of e / double(n);  min and max over the same tree: a
+ *     partial starts at DBL_MAX (min) or 0 (max) and takes e when e is strictly smaller / larger, partial[i] takes
+ *     partial[i + s] likewise.  count = n.
+ *
+ * ebo_align_sim3: data and model are double [n_points][3]; segment g covers points seg_begin[g] .. seg_end[g] - 1 of
+ *   BOTH arrays.  Segments may overlap and may be prefixes of one another; an empty segment is status 1.  fix_scale
+ *   non-zero is the SE3 alignment of metric trajectories.  One ebo_align_result per segment; status 0 aligned, 1 fewer
+ *   than 3 points, 2 a non-finite input, 3 degenerate.  A segment's result depends neither on the other segments of
+ *   the call nor on the run.  Limits: 2^24 points per segment, 65535 segments.  EBO_ERR_ARG beyond them and for a
+ *   needed pointer that is NULL, a negative count, seg_end < seg_begin, a segment outside [0, n_points].
+ *   EBO_ERR_STATE while a graph is being recorded.  Synchronous.
+ * ebo_align_sim3_device: device pointers for data and model; seg_begin, seg_end and the results stay host arrays.
+ * ebo_two_view_timing brackets both: slot [0] the kernel, [4] the whole call, the others 0. */
+typedef struct ebo_align_result
+{
+	double scale;
+	double R[9]; /* row-major */
+	double t[3];
+	double rmse, mean, min, max; /* the reference's ErrorMetricValue */
+	int32_t count;
+	int32_t status;
+} ebo_align_result;
+int ebo_align_sim3(ebo_ctx* ctx, int n_points, const double* data, const double* model, int n_segments, const int* seg_begin,
+				   const int* seg_end, int fix_scale, ebo_align_result* results);
+int ebo_align_sim3_device(ebo_ctx* ctx, int n_points, const double* d_data, const double* d_model, int n_segments,
+						  const int* seg_begin, const int* seg_end, int fix_scale, ebo_align_result* results);
+
 /* ---- absolute pose: three-point RANSAC on (bearing vector, landmark) pairs ----------------------------
  * What VisualOdometryFrontEnd::localizeCamera (visual_odometry.cpp:212-286) does through OpenGV's
  * AbsolutePoseSacProblem(KNEIP), stated as this project's own rules (OpenGV's source is not part of the reference
