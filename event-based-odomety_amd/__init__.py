@@ -1119,6 +1119,58 @@ class Context:
         self._check(lib().ebo_rectification_map(self._h, _dp(m), _vp(lut)))
         return m, lut
 
+    def camera_project(self, cam, xyz):
+        """CameraModel::project for many points: float64 [n][3] camera-frame points -> float64 [n][2] pixels."""
+        cam = camera(cam)
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        out = np.zeros((len(xyz), 2))
+        self._check(lib().ebo_camera_project(self._h, C.byref(cam), len(xyz), _dp(xyz), _dp(out)))
+        return out
+
+    def camera_project_device(self, cam, n, d_xyz, d_uv):
+        """The same on device arrays (pointers as int), asynchronous on the context's stream."""
+        cam = camera(cam)
+        self._check(lib().ebo_camera_project_device(self._h, C.byref(cam), int(n), C.c_void_p(int(d_xyz)),
+                                                    C.c_void_p(int(d_uv))))
+
+    def fit_rectified_camera(self, cam):
+        """-> the Camera (zero distortion) into which the sensor's undistorted border fits exactly."""
+        cam = camera(cam)
+        out = Camera()
+        self._check(lib().ebo_fit_rectified_camera(self._h, C.byref(cam), C.byref(out)))
+        return out
+
+    def set_rectification_camera(self, cam, rectified):
+        """set_rectification with an explicit rectified camera (zero distortion)."""
+        cam, rectified = camera(cam), camera(rectified)
+        self._check(lib().ebo_set_rectification_camera(self._h, C.byref(cam), C.byref(rectified)))
+
+    def rectified_camera(self):
+        """The rectified Camera of the rectification that is set."""
+        out = Camera()
+        self._check(lib().ebo_rectified_camera(self._h, C.byref(out)))
+        return out
+
+    def rectification_source_map(self):
+        """-> float64 [h][w][2]: where in the raw frame each pixel of the rectified frame is sampled."""
+        m = np.zeros((self.params.image_h, self.params.image_w, 2))
+        self._check(lib().ebo_rectification_source_map(self._h, _dp(m)))
+        return m
+
+    def rectify_image(self, image):
+        """uint8 [h][w] raw frame -> uint8 [h][w] rectified frame (bilinear, constant border 0)."""
+        h, w = self.params.image_h, self.params.image_w
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        if img.shape != (h, w):
+            raise ValueError("rectify_image: the image must be uint8 [%d][%d]" % (h, w))
+        out = np.zeros((h, w), dtype=np.uint8)
+        self._check(lib().ebo_rectify_image(self._h, _vp(img), _vp(out)))
+        return out
+
+    def rectify_image_device(self, d_image, d_out):
+        """The same on device arrays (pointers as int), asynchronous on the context's stream."""
+        self._check(lib().ebo_rectify_image_device(self._h, C.c_void_p(int(d_image)), C.c_void_p(int(d_out))))
+
     # -- two-view geometry (eight-point RANSAC, triangulation, the epipolar test) ---------------------
     def relative_pose_ransac(self, offsets, f1, f2, params=None, diagnostics=False, device=False):
         """ebo_relative_pose_ransac over len(offsets) - 1 keyframe pairs.  f1, f2: float64 [total][3] unit bearing

@@ -167,6 +167,7 @@ struct ebo_ctx
 	Dev<int> d_rect_bad;  // k_rectify_map's error bits
 	std::vector<int16_t> rect_lut;   // host copy for the host counting sort, fetched on its first use
 	bool rect_set = false;
+	ebo_camera rect_cam = {}, rect_out = {};  // the (camera, rectified camera) pair of the call that set it
 
 	std::vector<Unit> units;       // [Wn][P+1], stray unit last in each window
 	std::vector<int64_t> unit_tref;

@@ -509,9 +509,21 @@ struct CameraConsts
 {
 	double fx, fy, cx, cy, k1, k2, k3, p1, p2;
 };
+// the pinhole part of a rectified camera (its distortion is zero by definition)
+struct RectifiedConsts
+{
+	double fx, fy, cx, cy;
+};
 int launch_camera_unproject(const CameraConsts& k, int n, const double* d_uv, double* d_bearing, void* stream);
+int launch_camera_project(const CameraConsts& k, int n, const double* d_xyz, double* d_uv, void* stream);
 // d_map: double [h][w][2], d_lut: int16 [h][w][2], *d_bad: error bits (zeroed here)
-int launch_rectify_map(const CameraConsts& k, int w, int h, double* d_map, void* d_lut, int* d_bad, void* stream);
+int launch_rectify_map(const CameraConsts& k, const RectifiedConsts& r, int w, int h, double* d_map, void* d_lut, int* d_bad,
+					   void* stream);
+// d_extremes: xmin, xmax, ymin, ymax of the undistorted border pixels; *d_bad: 1 when one of them is not finite
+int launch_rectify_fit(const CameraConsts& k, int w, int h, double* d_extremes, int* d_bad, void* stream);
+// d_img / d_out: uint8 [h][w] (null together: the source map alone); d_src: double [h][w][2] or null
+int launch_rectify_image(const CameraConsts& k, const RectifiedConsts& r, int w, int h, const uint8_t* d_img, uint8_t* d_out,
+						 double* d_src, void* stream);
 
 // two-view geometry (ebo_twoview.inc, ebo_twoview.cpp).  models: [n_pairs * H][3][4]; d_samples may be null.
 int launch_tv_hypotheses(int n_pairs, int H, const int* d_offsets, const double* d_f1, const double* d_f2, uint64_t seed,

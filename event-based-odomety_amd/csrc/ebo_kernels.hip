@@ -1811,15 +1811,43 @@ int launch_camera_unproject(const CameraConsts& k, int n, const double* d_uv, do
 	return check_launch();
 }
 
-int launch_rectify_map(const CameraConsts& k, int w, int h, double* d_map, void* d_lut, int* d_bad, void* stream)
+int launch_camera_project(const CameraConsts& k, int n, const double* d_xyz, double* d_uv, void* stream)
+{
+	if (n <= 0)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_camera_project, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), k, n, d_xyz,
+					   d_uv);
+	return check_launch();
+}
+
+int launch_rectify_fit(const CameraConsts& k, int w, int h, double* d_extremes, int* d_bad, void* stream)
+{
+	hipLaunchKernelGGL(k_rectify_fit, dim3(1), dim3(kFitThreads), 0, static_cast<hipStream_t>(stream), k, w, h, d_extremes,
+					   d_bad);
+	return check_launch();
+}
+
+int launch_rectify_image(const CameraConsts& k, const RectifiedConsts& r, int w, int h, const uint8_t* d_img, uint8_t* d_out,
+						 double* d_src, void* stream)
+{
+	const dim3 grid((w + kRectTileW - 1) / kRectTileW, (h + kRectTileH - 1) / kRectTileH);
+	hipLaunchKernelGGL(k_rectify_image, grid, dim3(kRectTileW, kRectTileH), 0, static_cast<hipStream_t>(stream), k, r, w, h,
+					   d_img, d_out, d_src);
+	return check_launch();
+}
+
+int launch_rectify_map(const CameraConsts& k, const RectifiedConsts& r, int w, int h, double* d_map, void* d_lut, int* d_bad,
+					   void* stream)
 {
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	if (hipMemsetAsync(d_bad, 0, sizeof(int), s) != hipSuccess)
 	{
 		return -2;
 	}
-	hipLaunchKernelGGL(k_rectify_map, dim3((w * h + 255) / 256), dim3(256), 0, s, k, w, h, d_map, static_cast<short2*>(d_lut),
-					   d_bad);
+	hipLaunchKernelGGL(k_rectify_map, dim3((w * h + 255) / 256), dim3(256), 0, s, k, r, w, h, d_map,
+					   static_cast<short2*>(d_lut), d_bad);
 	return check_launch();
 }
 

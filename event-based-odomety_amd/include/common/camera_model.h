@@ -5,6 +5,8 @@
 //   cam.project(p)          // Vec3 in the camera frame -> Vec2 pixel
 //   cam.unproject(px)       // Vec2 pixel -> unit bearing Vec3 (ten fixed-point iterations, as the reference)
 //   cam.unprojectBatch(ctx, corners)   // the same for many pixels on the device (ebo_camera_unproject)
+//   cam.projectBatch(ctx, points)      // project for many points on the device (ebo_camera_project)
+//   common::fitRectifiedCamera(ctx, params)   // the zero-distortion camera that keeps the context's sensor in view
 //
 // The arithmetic is the rule written out in include/ebo.h ("camera model"), operation by operation, so that
 // CameraModel<double> compiled with -ffp-contract=off gives the bits of the device kernels and of
@@ -46,6 +48,24 @@ struct CameraModelParams
 inline ebo_camera toEboCamera(const CameraModelParams<double>& p)
 {
 	return ebo_camera{p.fx, p.fy, p.cx, p.cy, p.k1, p.k2, p.k3, p.p1, p.p2};
+}
+
+// The rectified camera fitted to the context's image size (include/ebo.h: ebo_fit_rectified_camera, rule C3): zero
+// distortion, and the undistorted border of the sensor spans it exactly along the tighter axis.
+inline CameraModelParams<double> fitRectifiedCamera(ebo_ctx* ctx, const CameraModelParams<double>& p)
+{
+	const ebo_camera cam = toEboCamera(p);
+	ebo_camera r{};
+	if (ebo_fit_rectified_camera(ctx, &cam, &r) != EBO_OK)
+	{
+		throw std::runtime_error(std::string("common::fitRectifiedCamera: ") + ebo_last_error(ctx));
+	}
+	CameraModelParams<double> out;
+	out.fx = r.fx;
+	out.fy = r.fy;
+	out.cx = r.cx;
+	out.cy = r.cy;
+	return out;
 }
 
 // Eigen::Matrix<Scalar, N, 1> stand-in
@@ -150,6 +170,22 @@ class CameraModel
 		if (rc != EBO_OK)
 		{
 			throw std::runtime_error(std::string("common::CameraModel::unprojectBatch: ") + ebo_last_error(ctx));
+		}
+		return out;
+	}
+
+	// project for many points in one launch on the context's device (include/ebo.h: ebo_camera_project)
+	std::vector<Vec2> projectBatch(ebo_ctx* ctx, const std::vector<Vec3>& points) const
+	{
+		static_assert(std::is_same<Scalar, double>::value, "the device kernel is float64");
+		static_assert(sizeof(Vec2) == 2 * sizeof(double) && sizeof(Vec3) == 3 * sizeof(double), "packed arrays");
+		std::vector<Vec2> out(points.size());
+		const ebo_camera cam = toEboCamera(param_);
+		const int rc = ebo_camera_project(ctx, &cam, static_cast<int>(points.size()), points.empty() ? nullptr : points[0].data(),
+										  out.empty() ? nullptr : out[0].data());
+		if (rc != EBO_OK)
+		{
+			throw std::runtime_error(std::string("common::CameraModel::projectBatch: ") + ebo_last_error(ctx));
 		}
 		return out;
 	}

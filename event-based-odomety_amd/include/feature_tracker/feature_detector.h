@@ -160,6 +160,8 @@ class FeatureDetector
 	}
 
 	void setFrontEndHooks(const FrontEndHooks& hooks) { hooks_ = hooks; }
+	// the hooks in use, for a caller that wraps them (for instance to look at the image each one is handed)
+	const FrontEndHooks& frontEndHooks() const { return hooks_; }
 
 	// Installs FrontEndHooks backed by this detector's own device context: ebo_good_features with the reference's
 	// maxCorners_ (W*H / (2*patchExtent+1)^2), mask_ (a border of patchExtent), qualityLevel, minDistance, blockSize
@@ -235,11 +237,14 @@ class FeatureDetector
 		}
 		flushPatches();
 		guarded([&] {
-			extractPatchesImpl(image);
+			// rectifyFrames: the frame is remapped once and every hook sees the rectified image
+			common::ImageSample rectified;
+			const common::ImageSample& frame = rectifyFrames_ ? (rectified = rectifiedFrame(image)) : image;
+			extractPatchesImpl(frame);
 			// flowEstimator_->addImage / getFlowPatches (flow_estimator.cpp:16-85)
 			if (hooks_.addImage)
 			{
-				hooks_.addImage(image.value);
+				hooks_.addImage(frame.value);
 			}
 			if (imageCounter_ < 2)
 			{
@@ -299,7 +304,10 @@ class FeatureDetector
 			return;
 		}
 		flushPatches();
-		guarded([&] { extractPatchesImpl(image); });
+		guarded([&] {
+			common::ImageSample rectified;
+			extractPatchesImpl(rectifyFrames_ ? (rectified = rectifiedFrame(image)) : image);
+		});
 	}
 
 	// feature_detector.cpp:568-583
@@ -316,8 +324,9 @@ class FeatureDetector
 
 	// feature_detector.cpp:585-619: the reference's per-event call (DetectorParams::eventBatch: the event is kept
 	// and the patches are brought up to date in chunks; every reader sees them current)
-	void updatePatches(const common::EventSample& event)
+	void updatePatches(const common::EventSample& rawEvent)
 	{
+		const common::EventSample event = rectifyFrames_ ? rectifiedEvent(rawEvent) : rawEvent;
 		if (params_.eventBatch <= 1)
 		{
 			guarded([&] { tracked_->updatePatches(event); });
@@ -334,6 +343,16 @@ class FeatureDetector
 	void updatePatches(const std::vector<common::EventSample>& chunk)
 	{
 		flushPatches();
+		if (rectifyFrames_)
+		{
+			std::vector<common::EventSample> rectified(chunk);
+			for (common::EventSample& e : rectified)
+			{
+				e = rectifiedEvent(e);
+			}
+			guarded([&] { tracked_->updatePatches(rectified); });
+			return;
+		}
 		guarded([&] { tracked_->updatePatches(chunk); });
 	}
 	// brings the tracked patches up to the last event handed to updatePatches(event)
@@ -624,7 +643,7 @@ class FeatureDetector
 				batchCtx_ = nullptr;
 				callError = ebo_last_error(nullptr);
 			}
-			else if (rectify_ && (rc = ebo_set_rectification(batchCtx_, &rectifyCamera_)) != EBO_OK)
+			else if (rectify_ && (rc = ebo_set_rectification_camera(batchCtx_, &rectifyCamera_, &rectifiedCamera_)) != EBO_OK)
 			{
 				callError = ebo_last_error(batchCtx_);
 				ebo_destroy(batchCtx_);
@@ -731,6 +750,7 @@ class FeatureDetector
 				rectify_ = false;
 				rectify_ = applyRectification();
 			}
+			rectifyFrames_ = rectifyFrames_ && rectify_ && fetchRectificationTable();
 		}
 		reset();
 	}
@@ -739,17 +759,75 @@ class FeatureDetector
 	// Rectify events at load (include/ebo.h: ebo_set_rectification): every window this detector compensates or
 	// integrates afterwards -- compensateEventsContrast, integrateEvents, compensateWindows -- is bucketed through the
 	// camera's rectification table, on the detector's own context and on the batch context.  The tracked patches and the
-	// image front end stay in raw coordinates (frames are not rectified).  A calibration the library refuses (fx or
-	// fy zero, a map outside the record range) is reported through the error policy and leaves no rectification set.
+	// image front end stay in raw coordinates unless rectifyFrames is switched on.  A calibration the library refuses
+	// (fx or fy zero, a map outside the record range) is reported through the error policy and leaves no rectification
+	// set.  The rectified camera keeps fx fy cx cy.
 	void setRectification(const common::CameraModelParams<double>& camera)
 	{
-		rectifyCamera_ = common::toEboCamera(camera);
-		rectify_ = false;  // (stays false when the error policy throws from here)
-		rectify_ = applyRectification();
+		common::CameraModelParams<double> same;
+		same.fx = camera.fx;
+		same.fy = camera.fy;
+		same.cx = camera.cx;
+		same.cy = camera.cy;
+		setRectification(camera, same);
 	}
+	// The same into an explicit rectified camera (include/ebo.h: ebo_set_rectification_camera; zero distortion), for
+	// instance common::fitRectifiedCamera's, which keeps the whole sensor in view.
+	void setRectification(const common::CameraModelParams<double>& camera, const common::CameraModelParams<double>& rectifiedCamera)
+	{
+		rectifyCamera_ = common::toEboCamera(camera);
+		rectifiedCamera_ = common::toEboCamera(rectifiedCamera);
+		rectify_ = false;  // (stays false when the error policy throws from here)
+		const bool frames = rectifyFrames_;
+		rectifyFrames_ = false;
+		rectify_ = applyRectification();
+		rectifyFrames_ = frames && rectify_ && fetchRectificationTable();
+	}
+	// the rectified camera of the rectification that is set (all zero when none is)
+	common::CameraModelParams<double> rectifiedCamera() const
+	{
+		common::CameraModelParams<double> r;
+		if (rectify_)
+		{
+			r.fx = rectifiedCamera_.fx;
+			r.fy = rectifiedCamera_.fy;
+			r.cx = rectifiedCamera_.cx;
+			r.cy = rectifiedCamera_.cy;
+		}
+		return r;
+	}
+	// Rectify frames too (include/ebo.h: ebo_rectify_image): newImage / extractPatches remap the frame once and hand the
+	// rectified image to every hook, and updatePatches routes a copy of each event whose (x, y) went through the
+	// rectification table (a raw coordinate outside the sensor is left alone, as the loaders leave it), so that tracker,
+	// front end and compensation share one pinhole geometry.  getEvents() stays raw: the compensation path rectifies at
+	// load with the same table, and no event is rectified twice.  Needs a rectification to be set, and is allowed only
+	// before the first newImage (the LK pyramid of an older image would be in the other geometry): otherwise
+	// EBO_ERR_STATE through the error policy.
+	void rectifyFrames(bool on)
+	{
+		if (on == rectifyFrames_)
+		{
+			status_ = EBO_OK;
+			lastError_.clear();
+			return;
+		}
+		if (imageCounter_ > 0)
+		{
+			fail(EBO_ERR_STATE, "rectifyFrames: only before the first newImage");
+			return;
+		}
+		if (on && !rectify_)
+		{
+			fail(EBO_ERR_STATE, "rectifyFrames: no rectification is set");
+			return;
+		}
+		rectifyFrames_ = on && fetchRectificationTable();
+	}
+	bool rectifyingFrames() const { return rectifyFrames_; }
 	void clearRectification()
 	{
 		rectify_ = false;
+		rectifyFrames_ = false;
 		if (batchCtx_)
 		{
 			ebo_clear_rectification(batchCtx_);
@@ -768,12 +846,48 @@ class FeatureDetector
 	// the rectification of setRectification on the contexts that exist now (the batch context is made on first use)
 	bool applyRectification()
 	{
-		if (batchCtx_ && ebo_set_rectification(batchCtx_, &rectifyCamera_) != EBO_OK)
+		int rc = EBO_OK;
+		if (batchCtx_ && (rc = ebo_set_rectification_camera(batchCtx_, &rectifyCamera_, &rectifiedCamera_)) != EBO_OK)
 		{
-			fail(EBO_ERR_RANGE, ebo_last_error(batchCtx_));
+			fail(rc, ebo_last_error(batchCtx_));
 			return false;
 		}
-		return check(ctx_ ? ebo_set_rectification(ctx_, &rectifyCamera_) : EBO_OK);
+		return check(ctx_ ? ebo_set_rectification_camera(ctx_, &rectifyCamera_, &rectifiedCamera_) : EBO_OK);
+	}
+	// rectifyFrames: the host copy of the table that updatePatches reads, fetched once per rectification
+	bool fetchRectificationTable()
+	{
+		rectifyTable_.assign(static_cast<size_t>(params_.imageSize.height) * params_.imageSize.width * 2, 0);
+		return check(ctx_ ? ebo_rectification_map(ctx_, nullptr, rectifyTable_.data()) : EBO_ERR_NO_DEVICE);
+	}
+	common::EventSample rectifiedEvent(const common::EventSample& raw) const
+	{
+		common::EventSample e = raw;
+		const int w = params_.imageSize.width, h = params_.imageSize.height;
+		const int x = raw.value.point.x, y = raw.value.point.y;
+		if (x >= 0 && x < w && y >= 0 && y < h)
+		{
+			const size_t i = 2 * (static_cast<size_t>(y) * w + x);
+			e.value.point.x = rectifyTable_[i];
+			e.value.point.y = rectifyTable_[i + 1];
+		}
+		return e;
+	}
+	common::ImageSample rectifiedFrame(const common::ImageSample& image)
+	{
+		const int w = params_.imageSize.width, h = params_.imageSize.height;
+		std::vector<uint8_t> tmp;
+		const uint8_t* raw = greyPixels(image.value, tmp);
+#ifdef EBO_HAVE_OPENCV
+		common::Image8 out(h, w, CV_8U);
+		uint8_t* dst = out.ptr<uint8_t>(0);
+#else
+		common::Image8 out(h, w);
+		uint8_t* dst = out.data.data();
+#endif
+		check(ebo_rectify_image(ctx_, raw, dst));
+		throwIfFailed();
+		return common::ImageSample(out, image.timestamp);
 	}
 
 	// :418-431 the reference stores the flows at the patch corners of its motion field
@@ -1057,6 +1171,9 @@ class FeatureDetector
 	std::string firstBatchError_;
 	bool rectify_ = false;        // setRectification: re-applied to every context made afterwards
 	ebo_camera rectifyCamera_{};
+	ebo_camera rectifiedCamera_{};  // the rectified camera of setRectification (K of rectifyCamera_ for the one-argument form)
+	bool rectifyFrames_ = false;  // rectifyFrames: frames are remapped and routed events go through rectifyTable_
+	std::vector<int16_t> rectifyTable_;  // host copy of the table, int16 [h][w][2]
 };
 
 }  // namespace tracker

@@ -47,6 +47,11 @@ struct EvaluatorParams
 	// (FeatureDetector::setRectification: events are undistorted as they are loaded).  With all-zero parameters
 	// that is an error through the detector's error policy, not a silent no-op.
 	bool rectifyEvents = false;
+	// true (implies rectifyEvents): frames are rectified too (FeatureDetector::rectifyFrames), into rectifiedCamera;
+	// tracker, image front end and compensation then share one pinhole geometry.  An all-zero rectifiedCamera means
+	// the one fitted to the sensor (common::fitRectifiedCamera), which keeps every corner in view.
+	bool rectifyFrames = false;
+	common::CameraModelParams<double> rectifiedCamera;
 };
 
 class EventPump
@@ -58,7 +63,29 @@ class EventPump
 	EventPump(tracker::FeatureDetector& tracker, const EvaluatorParams& params = EvaluatorParams())
 		: tracker_(tracker), params_(params)
 	{
-		if (params_.rectifyEvents)
+		if (params_.rectifyFrames)
+		{
+			common::CameraModelParams<double> r = params_.rectifiedCamera;
+			if (r.fx == 0 && r.fy == 0 && r.cx == 0 && r.cy == 0)
+			{
+				// a calibration the fit refuses leaves r all zero, which setRectification reports through the error policy
+				const ebo_camera cam = common::toEboCamera(params_.cameraModelParams);
+				ebo_camera fitted{};
+				if (tracker_.handle() && ebo_fit_rectified_camera(tracker_.handle(), &cam, &fitted) == EBO_OK)
+				{
+					r.fx = fitted.fx;
+					r.fy = fitted.fy;
+					r.cx = fitted.cx;
+					r.cy = fitted.cy;
+				}
+			}
+			tracker_.setRectification(params_.cameraModelParams, r);
+			if (tracker_.rectifying())
+			{
+				tracker_.rectifyFrames(true);
+			}
+		}
+		else if (params_.rectifyEvents)
 		{
 			tracker_.setRectification(params_.cameraModelParams);
 		}

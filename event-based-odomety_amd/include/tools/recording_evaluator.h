@@ -17,7 +17,8 @@
 // the unbatched order).  The visual odometry is not owned here (it stays the user's front end): where the reference
 // calls visualOdometry_->newKeyframeCandidate, the keyframe hook receives the patches and the image's timestamp, and
 // savePoses / setGroundTruthSamples belong to the VO's owner.  EvaluatorParams has the reference's fields, plus
-// windowBatch and rectifyEvents (the events of every window are undistorted with cameraModelParams as they are loaded).
+// windowBatch, rectifyEvents (the events of every window are undistorted with cameraModelParams as they are loaded) and
+// rectifyFrames / rectifiedCamera (frames are remapped too, so tracks and corners are in rectified pixels).
 #pragma once
 
 #include <cstdio>

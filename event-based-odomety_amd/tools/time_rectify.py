@@ -1,5 +1,6 @@
 """What rectifying events at load costs (include/ebo.h: ebo_set_rectification), measured in ONE process:
-the same call with and without a rectification set, alternating, after a warm-up; device times from HIP events
+the same call without a rectification, with the rectified camera that keeps K and with the fitted rectified camera
+(ebo_fit_rectified_camera: no event leaves the sensor), alternating, after a warm-up; device times from HIP events
 (ebo_timer_begin / _end on the context's stream), wall times where the call is host-bound.
 
 usage: time_rectify.py [--step ingest|images|setup|all] [--windows 128] [--events 200000] [--reps 21]
@@ -48,15 +49,24 @@ def stream(config, windows, events, distinct=16):
     return ev, offsets, gt, all8, t_base[pick], off, np.stack([gt[w] for w in pick])
 
 
+MODES = ("plain", "same K", "fitted")
+
+
+def set_mode(ctx, cam, mode):
+    if mode == "plain":
+        ctx.clear_rectification()
+    elif mode == "same K":
+        ctx.set_rectification(cam)
+    else:
+        ctx.set_rectification_camera(cam, ctx.fit_rectified_camera(cam))
+
+
 def alternate(ctx, cam, fn, reps, device_clock=True):
-    """median ms of fn() with no rectification and with one, alternating; the switch is outside the clock"""
-    out = {False: [], True: []}
+    """median ms of fn() in the three modes, alternating; the switch is outside the clock"""
+    out = {m: [] for m in MODES}
     for rep in range(reps + 2):
-        for rectify in (False, True):
-            if rectify:
-                ctx.set_rectification(cam)
-            else:
-                ctx.clear_rectification()
+        for rectify in MODES:
+            set_mode(ctx, cam, rectify)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             if device_clock:
@@ -67,8 +77,7 @@ def alternate(ctx, cam, fn, reps, device_clock=True):
             wall = (time.perf_counter() - t0) * 1e3
             if rep >= 2:  # two warm-up rounds
                 out[rectify].append(ms if device_clock else wall)
-    a, b = statistics.median(out[False]), statistics.median(out[True])
-    return a, b
+    return tuple(statistics.median(out[m]) for m in MODES)
 
 
 def report(**kw):
@@ -88,10 +97,11 @@ def step_ingest(args):
     for name, fn in (("ebo_set_windows8_device (resident)", lambda: ctx.set_windows8(d8.data_ptr(), t_base, off, device=True)),
                      ("ebo_set_windows8 (pinned host, PCIe included)", lambda: ctx.set_windows8(pin8.data_ptr(), t_base, off))):
         for clock in (True, False):
-            a, b = alternate(ctx, cam, fn, args.reps, device_clock=clock)
+            a, b, f = alternate(ctx, cam, fn, args.reps, device_clock=clock)
             report(step="ingest", call=name, clock="hip events" if clock else "wall", windows=args.windows, events=n,
-                   ms_plain=round(a, 4), ms_rectified=round(b, 4), ratio=round(b / a, 4),
-                   gev_s_plain=round(n / a / 1e6, 2), gev_s_rectified=round(n / b / 1e6, 2))
+                   ms_plain=round(a, 4), ms_rectified=round(b, 4), ms_fitted=round(f, 4), ratio=round(b / a, 4),
+                   ratio_fitted=round(f / a, 4), gev_s_plain=round(n / a / 1e6, 2), gev_s_rectified=round(n / b / 1e6, 2),
+                   gev_s_fitted=round(n / f / 1e6, 2))
     ctx.close()
 
 
@@ -108,9 +118,8 @@ def step_images(args):
     d_img = torch.zeros((windows, h, w), dtype=torch.float64, device="cuda")
     cam = lens(w, h)
     times = {}
-    for rectify in (False, True):
-        if rectify:
-            ctx.set_rectification(cam)
+    for rectify in MODES:
+        set_mode(ctx, cam, rectify)
         ctx.set_windows8(d8.data_ptr(), t_base, off, device=True)
         stray = sum(ctx.window_info(k)[1] - sum(ctx.patch_info(p, k)[0] for p in range(ctx.P)) for k in range(windows))
         ms = []
@@ -120,16 +129,18 @@ def step_images(args):
             ms.append(ctx.timer_end())
         times[rectify] = (statistics.median(ms[2:]), stray)
     report(step="images", call="ebo_count_image_device (warped)", windows=windows, events=n,
-           ms_plain=round(times[False][0], 4), ms_rectified=round(times[True][0], 4),
-           ratio=round(times[True][0] / times[False][0], 4), stray_events_plain=int(times[False][1]),
-           stray_events_rectified=int(times[True][1]))
+           ms_plain=round(times["plain"][0], 4), ms_rectified=round(times["same K"][0], 4),
+           ms_fitted=round(times["fitted"][0], 4), ratio=round(times["same K"][0] / times["plain"][0], 4),
+           ratio_fitted=round(times["fitted"][0] / times["plain"][0], 4), stray_events_plain=int(times["plain"][1]),
+           stray_events_rectified=int(times["same K"][1]), stray_events_fitted=int(times["fitted"][1]))
     # ebo_compensate_windows: the generated windows themselves (24-byte host records), wall clock
     few = min(len(offsets) - 1, 8)
     sub, suboff = ev[:int(offsets[few])], offsets[:few + 1]
     opts = ebo.default_solver(mode=ebo.SOLVE_INDEPENDENT, max_num_iterations=10)
-    a, b = alternate(ctx, cam, lambda: ctx.compensate_windows(sub, suboff, opts), max(3, args.reps // 4), device_clock=False)
+    a, b, f = alternate(ctx, cam, lambda: ctx.compensate_windows(sub, suboff, opts), max(3, args.reps // 4), device_clock=False)
     report(step="images", call="ebo_compensate_windows (independent, 10 iterations)", windows=few, events=len(sub),
-           ms_plain=round(a, 3), ms_rectified=round(b, 3), ratio=round(b / a, 4))
+           ms_plain=round(a, 3), ms_rectified=round(b, 3), ms_fitted=round(f, 3), ratio=round(b / a, 4),
+           ratio_fitted=round(f / a, 4))
     ctx.close()
 
 

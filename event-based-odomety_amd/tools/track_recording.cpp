@@ -1,10 +1,14 @@
 // track_recording — the reference's feature-tracking experiment on a DAVIS240C recording directory, without OpenCV:
 //
-//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--ate]]
+//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--ate]]
 //
 // DIR holds events.txt, images.txt + the frames (8-bit grey PNG), optionally groundtruth.txt / calib.txt.
 // --rectify: the events of every compensation window are undistorted with the recording's calib.txt as they are
 // loaded (tools::EvaluatorParams::rectifyEvents); frames and tracked patches stay in raw coordinates.  The
+// --rectify-frames: frames are rectified too (tools::EvaluatorParams::rectifyFrames), into the camera fitted to the
+// sensor (common::fitRectifiedCamera), so tracks, front end and compensation share one pinhole geometry;
+// OUT/calib_rectified.txt gets that camera in calib.txt's form (fx fy cx cy 0 0 0 0 0), and with --odometry the front
+// end is given it instead of the lens calibration: the tracks are already undistorted.  The
 // recording is played through tools::Replayer into tools::Evaluator::replay (tools/recording_evaluator.h; the files
 // equal those of per-event callbacks).
 // --odometry: visual_odometry::VisualOdometryFrontEnd (visual_odometry/visual_odometry.h) runs as the keyframe hook on a
@@ -38,7 +42,7 @@
 
 static int usage(const char* argv0)
 {
-	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--ate]]\n", argv0);
+	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--ate]]\n", argv0);
 	return 2;
 }
 
@@ -47,7 +51,7 @@ int main(int argc, char** argv)
 	std::string dataset, out;
 	bool trackerExperiment = false;
 	size_t windowBatch = 1;
-	bool rectify = false;
+	bool rectify = false, rectifyFrames = false;
 	bool odometry = false, bundleAdjust = false, refine = false, refineTwoView = false, ate = false;
 	for (int i = 1; i < argc; ++i)
 	{
@@ -67,6 +71,10 @@ int main(int argc, char** argv)
 		else if (a == "--rectify")
 		{
 			rectify = true;
+		}
+		else if (a == "--rectify-frames")
+		{
+			rectifyFrames = true;
 		}
 		else if (a == "--odometry")
 		{
@@ -134,6 +142,12 @@ int main(int argc, char** argv)
 			p.cameraModelParams = recording->getCalibration();
 			p.rectifyEvents = true;
 		}
+		if (rectifyFrames)
+		{
+			p.cameraModelParams = recording->getCalibration();
+			p.rectifyEvents = true;
+			p.rectifyFrames = true;
+		}
 		size_t events = 0, frames = 0, tracks = 0, windows = 0, keyframes = 0, landmarks = 0;
 		ebo_ctx* odometryCtx = nullptr;
 		if (odometry)
@@ -150,7 +164,33 @@ int main(int argc, char** argv)
 			tools::Evaluator::KeyframeHook hook;
 			if (odometry)
 			{
-				frontEnd.reset(new visual_odometry::VisualOdometryFrontEnd(odometryCtx, recording->getCalibration(),
+				hook = [&](const tracker::Patches& patches, const common::timestamp_t& t) {
+					visual_odometry::Keyframe keyframe(patches, t);
+					frontEnd->newKeyframeCandidate(keyframe);
+				};
+			}
+			tools::Evaluator evaluator(p, hook);
+			common::CameraModelParams<double> odometryCamera = recording->getCalibration();
+			if (rectifyFrames)
+			{
+				if (!evaluator.detector().rectifyingFrames())
+				{
+					throw std::runtime_error("--rectify-frames: " + evaluator.detector().lastError());
+				}
+				// the tracks are in rectified pixels: unprojecting them with the lens model would undistort them twice
+				odometryCamera = evaluator.detector().rectifiedCamera();
+				FILE* f = std::fopen((out + "/calib_rectified.txt").c_str(), "w");
+				if (!f)
+				{
+					throw std::runtime_error("cannot write " + out + "/calib_rectified.txt");
+				}
+				std::fprintf(f, "%.17g %.17g %.17g %.17g 0 0 0 0 0\n", odometryCamera.fx, odometryCamera.fy, odometryCamera.cx,
+							 odometryCamera.cy);
+				std::fclose(f);
+			}
+			if (odometry)
+			{
+				frontEnd.reset(new visual_odometry::VisualOdometryFrontEnd(odometryCtx, odometryCamera,
 																		   visual_odometry::VisualOdometryParams()));
 				if (bundleAdjust)
 				{
@@ -164,12 +204,7 @@ int main(int argc, char** argv)
 				{
 					frontEnd->twoView().useDeviceRefinement();
 				}
-				hook = [&](const tracker::Patches& patches, const common::timestamp_t& t) {
-					visual_odometry::Keyframe keyframe(patches, t);
-					frontEnd->newKeyframeCandidate(keyframe);
-				};
 			}
-			tools::Evaluator evaluator(p, hook);
 			tools::Replayer replayer(recording);
 			evaluator.replay(replayer);
 			evaluator.finish();

@@ -712,7 +712,8 @@ int ebo_lk_track(ebo_ctx* ctx, int n, const float* prev_xy, float* next_xy, uint
  *   project(x, y, z) (:49-77):   xP = x / z, yP = y / z; r2 = xP * xP + yP * yP; rad = radial(r2);
  *                                xDist = xP * rad + tangential(p1, p2, xP, yP, r2);
  *                                yDist = yP * rad + tangential(p2, p1, yP, xP, r2); (fx * xDist + cx, fy * yDist + cy)
- *                                (host only: common::CameraModel in the C++ facade; nothing on the device calls it yet)
+ *                                (ebo_camera_project and the frame remap below; common::CameraModel in the C++
+ *                                facade is the same rule on the host)
  *
  * ebo_camera_unproject: n points uv [n][2] -> unit bearing vectors bearing_out [n][3], host float64 arrays
  *   (replaces the per-corner cameraModel_->unproject calls of visual_odometry.cpp:234,367,369,516,518);
@@ -735,12 +736,52 @@ int ebo_lk_track(ebo_ctx* ctx, int n, const float* prev_xy, float* next_xy, uint
  *   the events with their coordinates replaced on the host, with no rectification set; everything after the load
  *   (objective, solves, count images) then works in rectified geometry.
  *   It affects the NEXT load, never the windows already resident.
- *   NOT rectified: ebo_route_set_events and the tracker objective (they align events with frame gradients, and
- *   frames stay raw), ebo_patch_integrate*, the float32 motion field of EBO_COUNT_FIELD, and ebo_set_patches,
+ *   NOT rectified: ebo_route_set_events and the tracker objective (they align events with frame gradients; a caller
+ *   that rectifies its frames with ebo_rectify_image hands them rectified events), ebo_patch_integrate*, the float32 motion field of EBO_COUNT_FIELD, and ebo_set_patches,
  *   which returns EBO_ERR_UNSUPPORTED while a rectification is set instead of silently ignoring it.
  * ebo_clear_rectification: later loads read raw coordinates again, exactly as a context that never had one.
  * ebo_rectification_map: copies out the map and / or the table of the rectification that is set (either pointer may
- *   be NULL); EBO_ERR_STATE when none is set. */
+ *   be NULL); EBO_ERR_STATE when none is set.
+ *
+ * Rectified frames and a fitted rectified camera.  These rules are this project's own (the reference rectifies
+ * nothing); tests/rectify_ref.py restates them.  w, h are the context's image size; (w-1), (h-1) are exact doubles.
+ * C1. A rectified camera r is an ebo_camera whose k1 k2 p1 p2 are all zero (k3 is ignored, as everywhere).  Any other
+ *     value: EBO_ERR_ARG.  r.fx or r.fy not finite or zero: EBO_ERR_RANGE.
+ * C2. Forward map into r:  (xOpt, yOpt) = undistort_cam(x, y); u = r.fx * xOpt + r.cx; v = r.fy * yOpt + r.cy; the table
+ *     is (round(u), round(v)), half away from zero, with the refusals of ebo_set_rectification, which is this rule
+ *     with r = (cam.fx, cam.fy, cam.cx, cam.cy).
+ * C3. Fit.  Needs w >= 2, h >= 2, cam.fx > 0, cam.fy > 0 (else EBO_ERR_RANGE).  xmin, xmax, ymin, ymax = the extremes
+ *     of undistort_cam over the border pixels (rows 0 and h-1, columns 0 and w-1).
+ *       ex = xmax - xmin; dx = fx * ex; sx = (w-1) / dx;    ey = ymax - ymin; dy = fy * ey; sy = (h-1) / dy;
+ *       s = min(sx, sy); r.fx = s * fx; r.fy = s * fy;
+ *       tx = xmax + xmin; mx = r.fx * tx; nx = (w-1) - mx; r.cx = nx / 2;     r.cy likewise from ymax, ymin, r.fy, h.
+ *     EBO_ERR_RANGE when a border pixel's undistorted coordinate is not finite or an extent is not positive.  The
+ *     border's image then spans exactly the sensor along the tighter axis and is centred along the other.  The fit
+ *     does not promise that no interior pixel leaves the sensor; the tests show it for the calibrations in use.
+ * C4. Source map.  For the output pixel (x', y'):  xn = (x' - r.cx) / r.fx; yn = (y' - r.cy) / r.fy;
+ *     (us, vs) = project_cam(xn, yn, 1).
+ * C5. Remap: bilinear, constant border 0.  If not (us > -1 and us < w and vs > -1 and vs < h) -- tested in double,
+ *     before any conversion to an integer, so a NaN falls here too -- the output is 0.  Otherwise
+ *       x0 = floor(us); y0 = floor(vs); a = us - x0; b = vs - y0; ia = 1 - a; ib = 1 - b;
+ *       p00 p10 p01 p11 = the bytes at (x0, y0) (x0+1, y0) (x0, y0+1) (x0+1, y0+1) as doubles, 0 outside the image;
+ *       top = ia * p00 + a * p10; bot = ia * p01 + a * p11; val = ib * top + b * bot   (each product and sum rounded)
+ *     and the output is round(val), half away from zero, as uint8.
+ * C6. project for many points: the project rule above on xyz [n][3] -> uv [n][2].  Not validated: z = 0 gives what
+ *     the rule gives.
+ *
+ * ebo_fit_rectified_camera: C3 for `cam` on the context's image size; rectified_out gets fx fy cx cy and zeros.
+ * ebo_set_rectification_camera: ebo_set_rectification with an explicit rectified camera (C1, C2): it affects the
+ *   next load, a refused call leaves no rectification set, EBO_ERR_STATE while recording, the same loaders read
+ *   through the table, and ebo_set_patches stays refused while it is set.  The context keeps the (cam, rectified) pair.
+ * ebo_rectified_camera: the rectified camera of the rectification that is set; EBO_ERR_STATE when none is.
+ * ebo_rectification_source_map: C4 for every output pixel, double [image_h][image_w][2]; EBO_ERR_STATE when none is set.
+ * ebo_rectify_image: C5 on a host uint8 [image_h][image_w] frame, synchronous; the _device form takes device
+ *   pointers and runs asynchronously on the context's stream (d_image == d_out: EBO_ERR_ARG).  EBO_ERR_STATE when no
+ *   rectification is set.  Every tap load is predicated on its own in-image test: no map reads outside the frame.
+ * ebo_camera_project: C6 on host arrays, synchronous; the _device form on device arrays, asynchronous.
+ * All of them return EBO_ERR_STATE while a graph is being recorded.  ebo_route_set_events, ebo_patch_integrate* and
+ * EBO_COUNT_FIELD stay un-rectified: a caller who rectifies frames rectifies the events it routes itself (the C++
+ * facade's FeatureDetector::rectifyFrames does, through a host copy of the table). */
 typedef struct ebo_camera
 {
 	double fx, fy, cx, cy, k1, k2, k3, p1, p2;
@@ -750,6 +791,14 @@ int ebo_camera_unproject_device(ebo_ctx* ctx, const ebo_camera* cam, int n, cons
 int ebo_set_rectification(ebo_ctx* ctx, const ebo_camera* cam);
 int ebo_clear_rectification(ebo_ctx* ctx);
 int ebo_rectification_map(ebo_ctx* ctx, double* map_xy_f64_out, int16_t* lut_i16_out);
+int ebo_fit_rectified_camera(ebo_ctx* ctx, const ebo_camera* cam, ebo_camera* rectified_out);
+int ebo_set_rectification_camera(ebo_ctx* ctx, const ebo_camera* cam, const ebo_camera* rectified);
+int ebo_rectified_camera(ebo_ctx* ctx, ebo_camera* out);
+int ebo_rectification_source_map(ebo_ctx* ctx, double* map_xy_f64_out);
+int ebo_rectify_image(ebo_ctx* ctx, const uint8_t* image, uint8_t* out);
+int ebo_rectify_image_device(ebo_ctx* ctx, const uint8_t* d_image, uint8_t* d_out);
+int ebo_camera_project(ebo_ctx* ctx, const ebo_camera* cam, int n, const double* xyz, double* uv_out);
+int ebo_camera_project_device(ebo_ctx* ctx, const ebo_camera* cam, int n, const double* d_xyz, double* d_uv_out);
 
 /* ---- two-view geometry: eight-point RANSAC, triangulation, the epipolar test -------------------
  * What VisualOdometryFrontEnd::initCameras / findInliersRansac (visual_odometry.cpp:176-210, 288-341) and
