@@ -30,6 +30,13 @@ EvalConsts make_consts(const ebo_ctx* c)
 	}
 	k.fix_bias = std::ldexp(1.5, kexp);
 	k.fix_scale = std::ldexp(1.0, kexp - 52);
+	// the taps' encoding (fix_form.h): subnormal products wherever every scaled weight stays a normal number
+	const int guardExp = static_cast<int>(ab_size("EBO_FIX_GUARD_EXP", kFixGuardExp));  // (A/B build, tests: trip the rule)
+	const bool subOk = fix_subnormal_ok(k.norm, kexp, guardExp);
+	const char* form = ab_env("EBO_FIX_FORM");  // (A/B build: "bias" = the fma + subtract form in the same kernels)
+	k.fix_form = !subOk ? kFixBiasedGuard : (form && !std::strcmp(form, "bias")) ? kFixBiasedAb : kFixSubnormal;
+	k.fix_pre_x = subOk ? fix_pre_x(k.norm) : 0.0;
+	k.fix_pre_y = subOk ? fix_pre_y(kexp) : 0.0;
 	k.image_w = c->prm.image_w;
 	k.image_h = c->prm.image_h;
 	k.patch_w = c->prm.patch_w;

@@ -22,11 +22,12 @@
 // What binds is the instruction count per tap (a straightforward version of this algorithm took ~1000
 // VALU instructions per event by its PMC profile), hence:
 //   * interior fast path: an event whose 7x7 footprint lies inside the band (almost all
-//     of them) runs unpredicated loops: per tap  v_fma_f64 + v_sub_u32 + ds_add_u64
+//     of them) runs unpredicated loops: per tap  v_mul_f64 + ds_add_u64
 //     with immediate offsets (scatter) /  ds_read_b64 + 2 v_fma_f64 (gather);
-//   * the fixed-point value is  fma(wx, wy, bias): the exact product is rounded ONCE
-//     onto the 2^-52 grid; bias = 1.5 * 2^k has a zero low dword, so removing it is a
-//     32-bit subtract on the high dword;
+//   * the fixed-point value is the bit pattern of the SUBNORMAL product of the two pre-scaled
+//     weights (value_tap): the exact product is rounded ONCE onto the 2^(k-52) grid.  Where the
+//     weights can be tiny (sigma < 1) it is  fma(wx, wy, bias): bias = 1.5 * 2^k has a zero low
+//     dword, so removing it is a 32-bit subtract on the high dword (fix_tap);
 //   * exp on [-1, 1] without range reduction (degree-12 Taylor on x/4, two squarings)
 //     when sigma >= 1 (the reference's sigma is 1).
 
@@ -81,6 +82,15 @@ __device__ __forceinline__ unsigned long long fix_tap(double wx, double wy, doub
 	const unsigned int lo = static_cast<unsigned int>(__double2loint(b));
 	const unsigned long long q = (static_cast<unsigned long long>(hi) << 32) | lo;
 	return (!SMALL && q == 0ull && wx * wy > 0.0) ? 1ull : q;
+}
+
+// The scatter's tap.  sub: wx and wy carry the prefactors 2^-511 norm and 2^-(511 + k) (unit_fix_grid), their product is
+// subnormal and its bit pattern is the fixed-point word: ONE v_mul_f64, rounded once to nearest even onto the same grid
+// as the biased form, so the same word (fix_form.h; the kernels run with f64 denormals on, float_denorm_mode_16_64 = 3).
+template <bool SMALL, bool SUB>
+__device__ __forceinline__ unsigned long long value_tap(double wx, double wy, double bias, int biasHi)
+{
+	return SUB ? static_cast<unsigned long long>(__double_as_longlong(wx * wy)) : fix_tap<SMALL>(wx, wy, bias, biasHi);
 }
 
 // What a device-resident solve keeps of an evaluation for the NEXT one (k_solve_independent; in LDS behind the
@@ -224,9 +234,15 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 	const int ty0 = y0 + tile * R;
 	const int ty1 = min(ty0 + R, y1 + 1);
 	const int maxRows = max(capDoubles / cols, 1);
-	double fixBias, fixScale;
-	unit_fix_grid(c, nEv, fixBias, fixScale);
+	double fixBias, fixScale, preX, preY;
+	unit_fix_grid(c, nEv, fixBias, fixScale, preX, preY);
 	const int biasHi = __double2hiint(fixBias);
+	// sigma >= 1: the scatter's taps are subnormal products (value_tap); the A/B build keeps the biased form behind a switch
+#ifdef EBO_AB
+	const bool subTaps = SMALL && c.fix_form == kFixSubnormal;
+#else
+	constexpr bool subTaps = SMALL;
+#endif
 
 	for (int sy0 = ty0; sy0 < ty1; sy0 += maxRows)
 	{
@@ -260,43 +276,59 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 			}
 			const int colLo = pxc - 3 - x0;
 			double wx[7], wy[7];
-			axis_taps3<SMALL>(fx, c.norm, c, wx);
-			axis_taps3<SMALL>(fy, 1.0, c, wy);
-			if (rowLo >= 0 && rowLo + 6 < srows && colLo >= 0 && colLo + 6 < bw)
-			{
-				unsigned long long* p = imgq + rowLo * cols + colLo;
-#pragma unroll
-				for (int j = 0; j < 7; ++j)
+			axis_taps3<SMALL>(fx, subTaps ? preX : c.norm, c, wx);
+			axis_taps3<SMALL>(fy, subTaps ? preY : 1.0, c, wy);
+			// (the form is a compile-time constant of the tap loops; only the A/B build holds both)
+			auto taps = [&](auto form) {
+				constexpr bool SUB = decltype(form)::value;
+				if (rowLo >= 0 && rowLo + 6 < srows && colLo >= 0 && colLo + 6 < bw)
 				{
+					unsigned long long* p = imgq + __mul24(rowLo, cols) + colLo;  // (both far below 2^24: not the quarter-rate v_mul_lo_u32)
 #pragma unroll
-					for (int i = 0; i < 7; ++i)
+					for (int j = 0; j < 7; ++j)
 					{
-						atomicAdd(p + i, fix_tap<SMALL>(wx[i], wy[j], fixBias, biasHi));
-					}
-					p += cols;
-				}
-			}
-			else
-			{
 #pragma unroll
-				for (int j = 0; j < 7; ++j)
-				{
-					const int row = rowLo + j;
-					if (row < 0 || row >= srows)
-					{
-						continue;
-					}
-#pragma unroll
-					for (int i = 0; i < 7; ++i)
-					{
-						const int col = colLo + i;
-						if (col >= 0 && col < bw)
+						for (int i = 0; i < 7; ++i)
 						{
-							atomicAdd(&imgq[row * cols + col], fix_tap<SMALL>(wx[i], wy[j], fixBias, biasHi));
+							atomicAdd(p + i, value_tap<SMALL, SUB>(wx[i], wy[j], fixBias, biasHi));
+						}
+						p += cols;
+					}
+				}
+				else
+				{
+#pragma unroll
+					for (int j = 0; j < 7; ++j)
+					{
+						const int row = rowLo + j;
+						if (row < 0 || row >= srows)
+						{
+							continue;
+						}
+#pragma unroll
+						for (int i = 0; i < 7; ++i)
+						{
+							const int col = colLo + i;
+							if (col >= 0 && col < bw)
+							{
+								atomicAdd(&imgq[row * cols + col], value_tap<SMALL, SUB>(wx[i], wy[j], fixBias, biasHi));
+							}
 						}
 					}
 				}
+			};
+#ifdef EBO_AB
+			if (subTaps)
+			{
+				taps(std::true_type{});
 			}
+			else
+			{
+				taps(std::false_type{});
+			}
+#else
+			taps(std::integral_constant<bool, subTaps>{});
+#endif
 		});
 		__syncthreads();
 		EDGE_TICK(18);
@@ -363,7 +395,7 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 					sumW += wx[i];
 					sumA = fma(wx[i], fma(g, static_cast<double>(i - 3), -gfx), sumA);
 				}
-				const double* rowp = img + rowLo * cols + colLo;
+				const double* rowp = img + __mul24(rowLo, cols) + colLo;
 #pragma unroll
 				for (int j = 0; j < 7; ++j)
 				{

@@ -4,6 +4,7 @@
 
 #include "ab_env.h"
 #include "count_plan.h"
+#include "fix_form.h"
 
 #include <stddef.h>
 #include <stdint.h>
@@ -123,9 +124,12 @@ struct EvalConsts
 	double ck1, ck2, ck3; // exp(hs * k^2), k = 1..3 (factored 1-D Gaussian taps)
 	double fix_bias;      // 1.5 * 2^k: adding it aligns a tap value to the fixed-point grid (k of norm alone;
 	double fix_scale;     // 2^(k-52): value of one fixed-point unit              a unit raises it: unit_fix_grid)
+	double fix_pre_x;     // norm * 2^-511 and 2^-(511 + k): the prefactors of the two axes' weights whose product is the
+	double fix_pre_y;     // SUBNORMAL double with the tap's fixed-point word as its bit pattern (fix_form.h; 0 if not used)
 	int32_t image_w, image_h;
 	int32_t patch_w, patch_h;
 	int32_t npx, npy;
+	int32_t fix_form;     // kFixSubnormal, kFixBiasedGuard or (A/B build) kFixBiasedAb: fix_form.h
 	uint32_t inv_pw, inv_ph; // floor(2^32 / patch_w) + 1 (resp. patch_h): x / patch_w == umulhi(x, inv_pw) for 0 <= x < 2^15, patch_w >= 2
 };
 

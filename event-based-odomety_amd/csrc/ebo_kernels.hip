@@ -396,16 +396,29 @@ __device__ __forceinline__ bool warp_event(uint64_t rec, int rx, int ry, int rw,
 // The fixed-point grid of one unit's value image: make_consts' exponent k (from norm alone) raised until the
 // unit's events cannot fill a pixel, n_ev * norm < 2^(11 + k) (a pixel wraps at 2^(12 + k)).  Units below that
 // keep make_consts' grid, and its bits.
-__device__ __forceinline__ void unit_fix_grid(const EvalConsts& c, uint32_t nEv, double& bias, double& scale)
+// preX, preY: the prefactors of the subnormal form of a tap (fix_form.h) on the same grid -- preY is halved wherever the
+// bias is doubled.  Uniform over the workgroup: preX is a kernel argument (scalar); preY takes the uniform vector register
+// pair the bias held in the scatter (forced into scalars with readfirstlane, k_eval3<true> spills one at its 106).
+__device__ __forceinline__ void unit_fix_grid(const EvalConsts& c, uint32_t nEv, double& bias, double& scale, double& preX,
+											  double& preY)
 {
 	bias = c.fix_bias;  // 1.5 * 2^k
 	scale = c.fix_scale;
+	preY = c.fix_pre_y;
 	const double top = static_cast<double>(nEv) * c.norm * (1.5 / 2048.0);  // n_ev * norm >= 2^(11 + k) <=> top >= bias
 	while (top >= bias)
 	{
 		bias *= 2.0;
 		scale *= 2.0;
+		preY *= 0.5;
 	}
+	preX = c.fix_pre_x;
+}
+
+__device__ __forceinline__ void unit_fix_grid(const EvalConsts& c, uint32_t nEv, double& bias, double& scale)
+{
+	double preX, preY;
+	unit_fix_grid(c, nEv, bias, scale, preX, preY);
 }
 
 // w[k] = pre * exp(hs (k-3-f)^2), k = 0..6, from three exps.
@@ -1307,7 +1320,7 @@ int launch_eval_variance(const EvalLaunch& L, void* stream)
 		return 0;
 	}
 	const dim3 grid(L.n_units * L.tiles, L.flow_sets);
-	auto kern = (L.c.inv_sigsq <= 1.0) ? k_eval3<true> : k_eval3<false>;
+	auto kern = (L.c.inv_sigsq <= 1.0 && L.c.fix_form != kFixBiasedGuard) ? k_eval3<true> : k_eval3<false>;
 	if (allow_big_lds(kern, L.lds_bytes))
 	{
 		return -2;
@@ -2235,7 +2248,7 @@ int launch_solve_independent(const SolveLaunch& L, void* stream)
 	{
 		return 0;
 	}
-	const bool smallExp = L.c.inv_sigsq <= 1.0;
+	const bool smallExp = L.c.inv_sigsq <= 1.0 && L.c.fix_form != kFixBiasedGuard;
 	auto kern = smallExp ? k_solve_independent<true> : k_solve_independent<false>;
 	if (allow_big_lds(kern, L.lds_bytes))
 	{
