@@ -761,6 +761,20 @@ class Context:
         self._check(lib().ebo_lds_rates(self._h, out))
         return float(out[0]), float(out[1])
 
+    def unit_records(self, w, b):
+        """diagnostic: the packed records of one unit as they lie in device memory -> np.uint64[n]
+        (b = 0 .. P-1 the grid patches, P the stray bucket; after set_patches w = 0 and b = the patch index)"""
+        f = lib().ebo_unit_records
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        n = C.c_size_t()
+        rc = f(self._h, int(w), int(b), None, C.c_size_t(0), C.byref(n))
+        if rc and not (rc == ERR_ARG and n.value > 0):
+            self._check(rc)
+        out = np.zeros(n.value, dtype=np.uint64)
+        if n.value:
+            self._check(f(self._h, int(w), int(b), _vp(out), C.c_size_t(n.value), C.byref(n)))
+        return out
+
     def stream_yardstick_device(self, d_image):
         """diagnostic: the bytes of a count-image launch with no work; returns the bytes moved"""
         n = C.c_uint64()

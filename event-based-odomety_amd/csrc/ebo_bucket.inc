@@ -5,13 +5,16 @@
 //
 // Input: raw 24-byte ebo_event records (the layout of common::EventSample) of n windows,
 // window w = raw[offsets[w] .. offsets[w+1]), time ordered.  Output: the packed 8-byte
-// records grouped by unit + the unit table, exactly what the host path produces, except
-// that the order INSIDE a unit is the arrival order of the scatter's atomics.  That
-// order is immaterial: a unit's reference time is the int32-truncated mean of its
-// earliest and latest event time (events are time ordered, so first/last == min/max),
-// and the evaluation kernels accumulate in exact fixed point (commutative).
+// records grouped by unit + the unit table, exactly what the host path produces, the order
+// INSIDE a unit included: the canonical order of order_deal.h (k_bucket_canon below), units
+// above kSortMax events in list order.  A unit's reference time is the int32-truncated mean
+// of its EARLIEST and LATEST event time: the functor's front / back (contrast_functor.h:18-20)
+// for a time-ordered window, and the same number for any permutation of a window that is
+// not -- the host path (set_windows_host) takes it the same way.  The window's reference
+// time is the mean of its first and last LISTED event time (feature_detector.cpp:305-306).
 //
-// Three launches: count (+ per-bucket min/max time), scan (unit table), scatter (pack).
+// Five launches: count (+ per-bucket min/max time and per-chunk histograms), scan (unit table),
+// chunk scan (first ranks), scatter (pack, stable), canon (canonical order).
 // Error bits in *flag: 1 coordinate range, 2 mid-time beyond int32, 4 dt beyond int32.
 
 struct RawEvent

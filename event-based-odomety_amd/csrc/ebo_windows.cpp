@@ -492,7 +492,7 @@ static int set_windows_host(ebo_ctx* c, const ebo_event* ev, const size_t* offse
 	std::vector<WindowInfo> wins(n_windows);
 	c->h_packed.resize(total);
 	std::vector<uint32_t> cnt(P + 1), cur(P + 1);
-	std::vector<int64_t> first(P + 1), last(P + 1), tlo(P + 1), thi(P + 1);
+	std::vector<int64_t> tlo(P + 1), thi(P + 1);
 	std::vector<int32_t> maxdt(units.size(), 0);
 	size_t base = 0;
 	for (int w = 0; w < n_windows; ++w)
@@ -530,10 +530,8 @@ static int set_windows_host(ebo_ctx* c, const ebo_event* ev, const size_t* offse
 			const int b = bucket_of(we[i]);
 			if (cnt[b] == 0)
 			{
-				first[b] = we[i].t_us;
 				tlo[b] = thi[b] = we[i].t_us;
 			}
-			last[b] = we[i].t_us;
 			tlo[b] = std::min(tlo[b], we[i].t_us);
 			thi[b] = std::max(thi[b], we[i].t_us);
 			cnt[b]++;
@@ -555,7 +553,9 @@ static int set_windows_host(ebo_ctx* c, const ebo_event* ev, const size_t* offse
 				u.ry = static_cast<int16_t>(y);
 				u.rw = static_cast<int16_t>(rw);
 				u.rh = static_cast<int16_t>(rh);
-				if (cnt[b] > 0 && !mid_timestamp(first[b], last[b], tu))
+				// earliest / latest stamp, as k_bucket_scan: the functor's front / back (contrast_functor.h:18-20)
+				// whenever the window is time-ordered, and independent of the list order when it is not
+				if (cnt[b] > 0 && !mid_timestamp(tlo[b], thi[b], tu))
 				{
 					return c->fail(EBO_ERR_RANGE, "patch mid-time outside int32 microseconds");
 				}
@@ -599,8 +599,9 @@ static int set_windows_host(ebo_ctx* c, const ebo_event* ev, const size_t* offse
 								 (static_cast<uint64_t>(static_cast<uint32_t>(static_cast<int32_t>(dt))) << 32);
 			c->h_packed[base + cur[b]++] = rec;
 		}
-		// canonical order inside a unit (as k_bucket_sort): both bucketing paths then
-		// hand identical arrays to the kernels
+		// canonical order inside a unit (as k_bucket_canon): both bucketing paths then hand identical arrays
+		// to the kernels, whatever the order of the list -- except a unit above 8192 events, which keeps the
+		// order of the list on both paths and so follows the list
 		for (int b = 0; b <= P; ++b)
 		{
 			const Unit& u = units[static_cast<size_t>(w) * (P + 1) + b];
@@ -840,6 +841,41 @@ int ebo_patch_info(const ebo_ctx* c, int window, int patch, int32_t* n_events, i
 	if (active) *active = (c->units[i].flags & kUnitActive) ? 1 : 0;
 	if (t_ref_us) *t_ref_us = c->unit_tref[i];
 	return EBO_OK;
+}
+
+int ebo_unit_records(ebo_ctx* c, int window, int bucket, uint64_t* out, size_t cap, size_t* n)
+{
+	if (!c)
+	{
+		return EBO_ERR_ARG;
+	}
+	if (c->capturing)
+	{
+		return c->fail(EBO_ERR_STATE, kNotWhileRecording);
+	}
+	const int buckets = c->custom_n ? c->custom_n : c->P + 1;  // the stray bucket is a window's last unit
+	if (window < 0 || window >= c->n_windows || (c->custom_n && window != 0) || bucket < 0 || bucket >= buckets || !n)
+	{
+		return c->fail(EBO_ERR_ARG, "ebo_unit_records: no such window or bucket, or a null count");
+	}
+	const Unit& u = c->units[c->unit_index(window, bucket)];
+	*n = u.n_ev;
+	if (u.n_ev > cap || (u.n_ev && !out))
+	{
+		return c->fail(EBO_ERR_ARG, "ebo_unit_records: the unit holds more records than cap (*n says how many)");
+	}
+	if (u.n_ev == 0)
+	{
+		return EBO_OK;
+	}
+	(void)hipSetDevice(c->prm.device);
+	int rc = c->hip(hipStreamSynchronize(c->stream), "sync before the record read-back");
+	if (rc == EBO_OK)
+	{
+		rc = c->hip(hipMemcpy(out, c->d_events.get() + u.ev_off, static_cast<size_t>(u.n_ev) * sizeof(uint64_t), hipMemcpyDeviceToHost),
+					"D2H unit records");
+	}
+	return rc;
 }
 
 }  // extern "C"

@@ -176,7 +176,12 @@ int ebo_patch_rect(const ebo_ctx* ctx, int px, int py, int* x, int* y, int* w, i
 /* Load one window (the `events` list R2/R3/R4 receive), time-ordered as given.
  * The host buckets events by patch keeping their order (R2 :348-355), computes
  * the window's and each patch's reference time (:305-306, contrast_functor.h:18-20),
- * packs 8 B/event and uploads.  Replaces any previous window(s). */
+ * packs 8 B/event and uploads.  Replaces any previous window(s).
+ * For a window that is not time-ordered, a patch's reference time is the mid of its earliest and latest
+ * stamp, which is the reference's front / back whenever the window is ordered; the window's own reference time
+ * stays the mid of the first and last LISTED stamp.  Inside a patch the records are kept in one canonical order
+ * (csrc/order_deal.h), so every result is independent of the order of the list -- except for a patch of more
+ * than 8192 events, whose records keep the order of the list. */
 int ebo_set_window(ebo_ctx* ctx, const ebo_event* ev, size_t n);
 /* Batch of independent windows: window w = ev[offsets[w] .. offsets[w+1]). */
 int ebo_set_windows(ebo_ctx* ctx, const ebo_event* ev, const size_t* offsets, int n_windows);
@@ -421,6 +426,13 @@ int ebo_edge_work_stats(ebo_ctx* ctx, const double* d_flows, int want_jac, uint6
  * per CU, 42 footprints per lane, best of three; tools/microbench/lds_atomics.hip "7x7 taps, any base"): the rates the
  * scatter and the gather pass of the variance evaluation are priced against.  Synchronous. */
 int ebo_lds_rates(ebo_ctx* ctx, double* gops);
+
+/* Diagnostic (tests/test_gpu_bucket_edges.py): the packed 8-byte records of ONE unit as they lie in device memory, in
+ * their order there -- lo word x:15 | polarity:1 | y:15 | 0, hi word uint32(int32(t_ref(unit) - t)).  bucket = 0 .. P-1
+ * for the grid patches of `window` and P for its stray bucket; after ebo_set_patches window = 0 and bucket = the patch
+ * index.  *n receives the unit's size.  EBO_ERR_ARG for a bad index, a null pointer or cap < *n (*n is still set then);
+ * EBO_ERR_STATE while a graph is being recorded.  Synchronous; changes nothing. */
+int ebo_unit_records(ebo_ctx* ctx, int window, int bucket, uint64_t* out, size_t cap, size_t* n);
 
 /* Diagnostic (bench.py): the traffic of ebo_count_image_device with no work -- every packed event of the
  * loaded windows read once (16-byte loads), every pixel of d_image [Wn][image_h][image_w] written once
