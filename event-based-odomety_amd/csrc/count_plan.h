@@ -127,6 +127,10 @@ inline CountPlan plan_count_image(const CountShape& S)
 			for (int ty = tyMin; ty <= H / 8; ty = (ty < 4 ? ty + 1 : ty * 2))
 			{
 				const int th = (H + ty - 1) / ty;
+				if (th * (ty - 1) > H)
+				{
+					continue;  // fewer tiles of this height cover the image: the last ones would start below it
+				}
 				const double visits = (tx > 1 ? (tw + 2 * Rx) / tw : 1.0) * (ty > 1 ? (th + 2 * Ry) / th : 1.0);
 				const double idle = std::max(1.0, 512.0 / (static_cast<double>(S.windows) * tx * ty));
 				const double cost = visits * idle;

@@ -1,7 +1,8 @@
 // The count-image launch plan (csrc/count_plan.h) on the CPU: (a) the full plan of a written-down list of shapes
 // against a table, (b) over a grid of modes, sensors, batch sizes and window sizes with default knobs, the kernels
 // reached are exactly the ones launch_count_image (csrc/ebo_kernels.hip) can launch, (c) every plan fits the device:
-// LDS <= 160 KB, grid > 0, a block of whole waves <= 1024 lanes.  Run by tests/test_count_plan.py.
+// LDS <= 160 KB, grid > 0, a block of whole waves <= 1024 lanes, every tile of a tile grid starts inside the image.  Run by
+// tests/test_count_plan.py.
 //   count_plan_test          check (a), (b), (c); prints "all passed"
 //   count_plan_test --print  the rows of (a) as the current code plans them (to renew the table on purpose)
 #include "../../event-based-odomety_amd/csrc/count_plan.h"
@@ -100,6 +101,118 @@ const std::set<std::string> kLaunchable = {
 // BASELINE.md's configurations (synth.CONFIGS)
 const Geometry kC0{"C0", 240, 180, 20, 20}, kC1{"C1", 240, 180, 240, 180}, kC2{"C2", 240, 180, 30, 22},
 	kC3{"C3", 346, 260, 21, 16}, kC4{"C4", 1280, 720, 40, 22};
+
+// A shape with every A/B knob a GPU test of tests/test_gpu_count_edges.py sets; the forced tile pitch and block go into
+// the row's label (row() prints EBO_COUNT_LDS_KB only).
+CountShape edge(const Geometry& g, int mode, int windows, uint64_t n, bool stray, int impl, int ldsKb = 0, int tileW = 0,
+				int tileH = 0, int block = 0)
+{
+	CountShape s = shape(g, mode, windows, n, stray, impl, ldsKb);
+	s.tile_w = static_cast<size_t>(tileW);
+	s.tile_h = static_cast<size_t>(tileH);
+	s.block = block;
+	return s;
+}
+
+struct EdgeRow
+{
+	std::string label;
+	CountShape s;
+};
+
+// count_cases.py's sensors
+const Geometry kTieSmall{"ties 241x181/8x6", 241, 181, 8, 6}, kTieWide{"ties 16383x8/32x4", 16383, 8, 32, 4},
+	kTieTall{"ties 8x16383/4x32", 8, 16383, 4, 32}, kFine{"ties 240x180/3x3", 240, 180, 3, 3},
+	kPile{"64x48/16x12", 64, 48, 16, 12}, kStore{"store 61x43/20x21", 61, 43, 20, 21};
+
+// The store forms: 61 x 43 pixels (odd: the second of three windows starts 8 bytes off a 16-byte boundary) in bands of an
+// odd number of rows -- band 0 has an odd pixel count and an aligned start, band 1 an odd start -- on every path that
+// stores rows from packed counters: impl 1 and 3 (warped, field), 4 (warped), 2 (un-warped).
+std::vector<EdgeRow> storeRows()
+{
+	std::vector<EdgeRow> rows;
+	for (int mode : {1, 2})
+	{
+		rows.push_back({kStore.name, edge(kStore, mode, 3, 5299, true, 1, 3)});
+		rows.push_back({kStore.name, edge(kStore, mode, 3, 5299, true, 3, 3)});
+	}
+	rows.push_back({kStore.name, edge(kStore, 1, 3, 5299, true, 4, 2)});
+	rows.push_back({kStore.name, edge(kStore, 0, 3, 5299, false, 2, 3)});
+	return rows;
+}
+
+std::vector<EdgeRow> edgeRows()
+{
+	std::vector<EdgeRow> rows;
+	auto add = [&](const std::string& label, const CountShape& s) { rows.push_back({label, s}); };
+	auto tiled = [](const char* name, int tw, int th, int block) {
+		return std::string(name) + " tile" + std::to_string(tw) + "x" + std::to_string(th) + " block" + std::to_string(block);
+	};
+	// the tie ladders on every forced path: warped 0, 1, 3, 4, 5 (and 5 with 8 x 8 tiles, one-patch tiles and 64-lane
+	// workgroups), field 0, 1, 3
+	struct Tie
+	{
+		const Geometry* g;
+		int windows;
+		uint64_t n;
+	};
+	for (const Tie& t : {Tie{&kTieSmall, 3, 674}, Tie{&kTieWide, 2, 338}, Tie{&kTieTall, 2, 338}})
+	{
+		for (int impl : {0, 1, 3, 4, 5})
+		{
+			add(t.g->name, edge(*t.g, 1, t.windows, t.n, false, impl));
+		}
+		for (int impl : {0, 1, 3})
+		{
+			add(t.g->name, edge(*t.g, 2, t.windows, t.n, false, impl));
+		}
+	}
+	add(tiled(kTieSmall.name, 8, 8, 0), edge(kTieSmall, 1, 3, 674, false, 5, 0, 8, 8));
+	add(tiled(kTieSmall.name, 8, 6, 64), edge(kTieSmall, 1, 3, 674, false, 5, 0, 8, 6, 64));
+	// ... on the plan the shipped library makes by itself: tiles, unit waves, the whole-window LDS image
+	add("ties C2x24", edge(kC2, 1, 24, 182, false, -1));
+	add("ties fine x32", edge(kFine, 1, 32, 98, false, -1));
+	add("ties C2x64 field", edge(kC2, 2, 64, 66, false, -1));
+	// the seams: row bands of 25 / 25 / 23 rows (impl 1, 3, 4 at 12 KB), the tiles impl 5 chooses for 8 windows (30 x 23),
+	// tiles of 8 x 8 and of one patch
+	add("seams C2x3 0x25", edge(kC2, 1, 3, 380, false, 1, 12));
+	add("seams C2x3 0x25", edge(kC2, 1, 3, 380, false, 3, 12));
+	add("seams C2x3 0x23", edge(kC2, 1, 3, 380, false, 4, 12));
+	add("seams C2x8 30x23", edge(kC2, 1, 8, 380, false, 5));
+	add(tiled("seams C2x10", 8, 8, 0), edge(kC2, 1, 10, 380, false, 5, 0, 8, 8));
+	add(tiled("seams C2x3", 30, 22, 0), edge(kC2, 1, 3, 380, false, 5, 0, 30, 22));
+	// pile-ups on one pixel: 65535 events in a window (16-bit counters full), 65536 and more (32-bit); 1 KB bands
+	for (uint64_t n : {65535u, 65536u, 70000u})
+	{
+		for (int impl : {0, 1, 3, 4, 5})
+		{
+			add("pileup " + std::to_string(n), edge(kPile, 1, 1, n, false, impl, 1));
+		}
+		for (int impl : {0, 1, 3})
+		{
+			add("pileup " + std::to_string(n), edge(kPile, 2, 1, n, false, impl, 1));
+		}
+		add("pileup " + std::to_string(n), edge(kPile, 0, 1, n, false, 2, 1));
+	}
+	// k_count_tiles's 16-bit rule: the target pixel inside a tile (16 x 12) and on a tile's first column and row (24 x 18)
+	for (uint64_t n : {65531u, 65540u, 65534u})
+	{
+		add(tiled("tile limit", 16, 12, 0) + " " + std::to_string(n), edge(kPile, 1, 1, n, false, 5, 0, 16, 12));
+		add(tiled("tile limit", 24, 18, 0) + " " + std::to_string(n), edge(kPile, 1, 1, n, false, 5, 0, 24, 18));
+	}
+	// test_count_image_more_than_65535_events_per_window in the warped and field modes
+	for (int impl : {1, 2, 5})
+	{
+		add("wide C2x1 90000", shape(kC2, 1, 1, 90000, false, impl));
+		add("wide C2x1 90000", shape(kC2, 2, 1, 90000, false, impl));
+	}
+	// the store forms (storeRows)
+	for (const EdgeRow& e : storeRows())
+	{
+		rows.push_back(e);
+	}
+	return rows;
+}
 
 std::vector<std::string> goldenRows()
 {
@@ -203,6 +316,11 @@ std::vector<std::string> goldenRows()
 	add("half integer C0", shape(kC0, 1, 1, 36));
 	add("batch C0x3", shape(kC0, 1, 3, 9000));
 	add("graph C2x4", shape(kC2, 1, 4, 20000));
+	// tests/test_gpu_count_edges.py (the cases of tests/count_cases.py)
+	for (const EdgeRow& e : edgeRows())
+	{
+		add(e.label, e.s);
+	}
 	return rows;
 }
 
@@ -270,19 +388,36 @@ int main(int argc, char** argv)
 					}
 					for (bool stray : {false, true})
 					{
-						const CountShape s = shape(g, mode, wn, n, stray);
-						const CountPlan p = plan_count_image(s);
-						++nPlans;
-						for (const std::string& k : kernels(s, p))
+						// the default plan, and (warped) the tiles forced: small batches make them split finest
+						for (int impl : {-1, 5})
 						{
-							reached.insert(k);
-						}
-						const bool ok = p.lds <= 160 * 1024 && p.grid_x > 0 && p.grid_y > 0 && p.block >= 64 &&
-										p.block <= 1024 && p.block % 64 == 0 && p.lds_hist <= 160 * 1024 &&
-										p.lds_scatter <= 160 * 1024 && (p.kind != kCountScatter || p.convert_blocks > 0);
-						if (!ok)
-						{
-							fail("invariant: " + row(g.name, s));
+							if (impl == 5 && (mode != 1 || stray))
+							{
+								continue;
+							}
+							const CountShape s = shape(g, mode, wn, n, stray, impl);
+							const CountPlan p = plan_count_image(s);
+							++nPlans;
+							if (impl < 0)
+							{
+								for (const std::string& k : kernels(s, p))
+								{
+									reached.insert(k);
+								}
+							}
+							// every tile of the grid starts inside the image (the last one may be empty), and the grid covers it
+							const bool tilesOk = p.kind != kCountTiles ||
+												 (p.tile_w > 0 && p.tile_h > 0 && (p.tiles_x - 1) * p.tile_w < g.w &&
+												  p.tiles_x * p.tile_w >= g.w && (p.tiles_y - 1) * p.tile_h <= g.h &&
+												  p.tiles_y * p.tile_h >= g.h);
+							const bool ok = p.lds <= 160 * 1024 && p.grid_x > 0 && p.grid_y > 0 && p.block >= 64 &&
+											p.block <= 1024 && p.block % 64 == 0 && p.lds_hist <= 160 * 1024 &&
+											p.lds_scatter <= 160 * 1024 && (p.kind != kCountScatter || p.convert_blocks > 0) &&
+											tilesOk;
+							if (!ok)
+							{
+								fail("invariant: " + row(g.name, s));
+							}
 						}
 					}
 				}
@@ -302,6 +437,28 @@ int main(int argc, char** argv)
 		{
 			fail("planned but not launchable: " + k);
 		}
+	}
+	// (d) the store-form shapes give every path a band with an odd pixel count at an aligned start, a band with an odd
+	// start, and a second window at an odd pixel offset
+	std::set<int> storeImpls;
+	for (const EdgeRow& e : storeRows())
+	{
+		const CountPlan p = plan_count_image(e.s);
+		const CountKind want = e.s.impl == 1 ? kCountWindowLds : e.s.impl == 2 ? kCountBands : e.s.impl == 3 ? kCountSorted : kCountUnits;
+		const int bandRows = p.kind == kCountBands ? p.prb * e.s.patch_h : p.rows_per_band;
+		const int nBands = p.kind == kCountBands ? p.n_regular + 1 : p.bands;
+		const bool ok = p.kind == want && p.u16 && e.s.windows > 1 && (e.s.image_w * e.s.image_h) % 2 == 1 &&
+						(bandRows * e.s.image_w) % 2 == 1 && nBands >= 2 && bandRows < e.s.image_h &&
+						(p.kind != kCountBands || p.col_tiles == 1);
+		if (!ok)
+		{
+			fail("store forms: " + row(e.label.c_str(), e.s));
+		}
+		storeImpls.insert(e.s.impl);
+	}
+	if (storeImpls != std::set<int>{1, 2, 3, 4})
+	{
+		fail("store forms: not every implementation has a shape");
 	}
 	std::printf("%zu golden rows, %zu plans, %zu kernels reached\n", rows.size(), nPlans, reached.size());
 	if (failures)

@@ -64,6 +64,19 @@ def test_count_image_more_than_65535_events_per_window(ebo_ab, orc, synth, monke
         img = c.count_image(ebo.COUNT_INTEGRATED)[0]
         assert img[13, 11] >= 70000
         assert np.array_equal(img, orc.integrate_events(ev, 240, 180))
+        # the warped and field images, which impl 1 (32-bit whole-window bands) and impl 5 (warped: the 32-bit half-tile
+        # slices, patch 0 alone holds more than 65535 events) serve: patch 0 and the field at the pile's pixel stand
+        # still, so the pile stays where it is; everything else moves
+        rng = np.random.RandomState(9)
+        flows = rng.uniform(-2, 2, (c.P, 2))
+        flows[0] = 0.0
+        field = rng.uniform(-2, 2, (180, 240, 2)).astype(np.float32)
+        field[13, 11] = 0.0
+        warped = c.count_image(ebo.COUNT_WARPED, flows)[0]
+        byfield = c.count_image(ebo.COUNT_FIELD, field)[0]
+        assert warped[13, 11] >= 70000 and byfield[13, 11] >= 70000
+        assert np.array_equal(warped, orc.final_count_image(ev, _prm(orc, c), flows))
+        assert np.array_equal(byfield, orc.compensate_events_field(ev, 240, 180, field))
 
 
 @pytest.mark.parametrize("lds_kb", ["12", "24", "150"])
