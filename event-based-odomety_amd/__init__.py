@@ -775,6 +775,25 @@ class Context:
             self._check(f(self._h, int(w), int(b), _vp(out), C.c_size_t(n.value), C.byref(n)))
         return out
 
+    def launch_order(self):
+        """diagnostic: the launch-order table as it lies in device memory -> np.uint32[units]"""
+        f = lib().ebo_launch_order
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        n = C.c_size_t()
+        rc = f(self._h, None, C.c_size_t(0), C.byref(n))
+        if rc and not (rc == ERR_ARG and n.value > 0):
+            self._check(rc)
+        out = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            self._check(f(self._h, _vp(out), C.c_size_t(n.value), C.byref(n)))
+        return out
+
+    def eval_launch_shape(self, want_jac=True):
+        """diagnostic: (row tiles per unit, lanes per workgroup, flow sets) of the variance evaluation's launch"""
+        v = [C.c_int() for _ in range(3)]
+        self._check(lib().ebo_eval_launch_shape(self._h, int(want_jac), *[C.byref(a) for a in v]))
+        return tuple(a.value for a in v)
+
     def stream_yardstick_device(self, d_image):
         """diagnostic: the bytes of a count-image launch with no work; returns the bytes moved"""
         n = C.c_uint64()

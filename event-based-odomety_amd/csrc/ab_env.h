@@ -12,6 +12,7 @@
 #pragma once
 
 #include <cstdlib>
+#include <cstring>
 
 namespace ebo_ab
 {
@@ -29,6 +30,18 @@ inline size_t ab_size(const char* name, size_t dflt)
 	}
 	return static_cast<size_t>(std::strtoull(v, nullptr, 10));
 }
+// EBO_EVAL_ORDER = index | light: the launch-order table a load builds (launch_order.h: 1 the identity, 2 lightest
+// first; anything else, and always in the shipped build, 0 = heaviest first).  Read when windows or patches are loaded.
+inline int ab_launch_order()
+{
+	const char* v = ab_env("EBO_EVAL_ORDER");
+	if (!v)
+	{
+		return 0;
+	}
+	return std::strcmp(v, "index") == 0 ? 1 : std::strcmp(v, "light") == 0 ? 2 : 0;
+}
 }  // namespace ebo_ab
 using ebo_ab::ab_env;
+using ebo_ab::ab_launch_order;
 using ebo_ab::ab_size;

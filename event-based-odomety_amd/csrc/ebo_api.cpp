@@ -400,6 +400,10 @@ int run_eval_edge(ebo_ctx* c, const double* d_flows, int want_jac, double* d_out
 	return EBO_OK;
 }
 
+// The shape of a variance evaluation's launch: flow sets, workgroup size, LDS capacity and row tiles.  It follows the
+// context's geometry and the number of flow slots only, never the data (ebo_eval_launch_shape reports it).
+int eval_launch_shape(ebo_ctx* c, int want_jac, EvalLaunch& L);
+
 int run_eval_device(ebo_ctx* c, const double* d_flows, int want_jac, double* d_out)
 {
 	if (c->n_windows == 0)
@@ -410,14 +414,37 @@ int run_eval_device(ebo_ctx* c, const double* d_flows, int want_jac, double* d_o
 	{
 		return run_eval_edge(c, d_flows, want_jac, d_out);
 	}
-	const bool central = want_jac && c->prm.grad == EBO_GRAD_CENTRAL;
 	EvalLaunch L;
+	int rc = eval_launch_shape(c, want_jac, L);
+	if (rc)
+	{
+		return rc;
+	}
 	L.d_modes = c->modes_active;
 	L.live = c->live_active;
 	L.d_events = c->d_events;
 	L.d_units = c->d_units;
-	L.n_units = static_cast<int>(c->units.size());
+	L.d_order = c->d_order;
 	L.d_flows = d_flows;
+	rc = c->grow(c->d_partials, static_cast<size_t>(L.flow_sets) * L.n_units * L.tiles * kPartialStride, "hipMalloc partials");
+	if (rc)
+	{
+		return rc;
+	}
+	L.d_partials = c->d_partials;
+	L.d_out = d_out;
+	L.c = make_consts(c);
+	if (launch_eval_variance(L, c->stream))
+	{
+		return c->hip(hipGetLastError(), "eval launch");
+	}
+	return EBO_OK;
+}
+
+int eval_launch_shape(ebo_ctx* c, int want_jac, EvalLaunch& L)
+{
+	const bool central = want_jac && c->prm.grad == EBO_GRAD_CENTRAL;
+	L.n_units = static_cast<int>(c->units.size());
 	L.n_flow = static_cast<int>(c->n_flows());
 	L.flow_sets = central ? 5 : 1;
 	L.channels = (want_jac && !central) ? 3 : 1;
@@ -472,18 +499,6 @@ int run_eval_device(ebo_ctx* c, const double* d_flows, int want_jac, double* d_o
 		}
 	}
 	L.tiles = std::max(1, std::min(t, 64));
-	rc = c->grow(c->d_partials, static_cast<size_t>(L.flow_sets) * L.n_units * L.tiles * kPartialStride, "hipMalloc partials");
-	if (rc)
-	{
-		return rc;
-	}
-	L.d_partials = c->d_partials;
-	L.d_out = d_out;
-	L.c = make_consts(c);
-	if (launch_eval_variance(L, c->stream))
-	{
-		return c->hip(hipGetLastError(), "eval launch");
-	}
 	return EBO_OK;
 }
 
@@ -865,6 +880,7 @@ int run_solve_device(ebo_ctx* c, const ebo_solver_opts* o, double* d_flows_out, 
 	SolveLaunch L;
 	L.d_events = c->d_events;
 	L.d_units = c->d_units;
+	L.d_order = c->d_order;
 	L.n_units = static_cast<int>(c->units.size());
 	// k_solve_independent runs three waves per SIMD (152-166 VGPRs since round 3: one next_step() site in the
 	// solver; 205 and two waves before), i.e. 12 waves per CU.  By the canvas of the regular patch, as the
@@ -1358,6 +1374,7 @@ int ebo_create(const ebo_params* p, ebo_ctx** out)
 	int rc = c->hip(e, what);
 	if (rc == EBO_OK) rc = c->grow(c->d_events, c->cap_events, what);
 	if (rc == EBO_OK) rc = c->grow(c->d_units, nu, what);
+	if (rc == EBO_OK) rc = c->grow(c->d_order, nu, what);  // (its only allocation: loads check the capacity, never grow it)
 	if (rc == EBO_OK) rc = c->grow(c->d_unit_maxdt, nu, what);
 	if (rc == EBO_OK) rc = c->grow(c->d_flows, nf * 2, what);
 	if (rc == EBO_OK) rc = c->grow(c->d_out, nf * 3, what);
@@ -1415,6 +1432,7 @@ void ebo_destroy(ebo_ctx* c)
 		(void)hipStreamSynchronize(c->stream);
 	}
 	(void)ebo_comm_destroy(c);
+	if (c->order_done) hipEventDestroy(c->order_done);
 	if (c->ev0) hipEventDestroy(c->ev0);
 	if (c->ev1) hipEventDestroy(c->ev1);
 	for (hipEvent_t e : c->tv_ev)
@@ -1437,6 +1455,12 @@ int ebo_set_stream(ebo_ctx* c, void* hip_stream)
 	if (c->capturing)
 	{
 		return c->fail(EBO_ERR_STATE, kNotWhileRecording);
+	}
+	if (c->order_done)
+	{
+		// the last load's launch-order upload may still be on its way on the old stream (ebo_windows.cpp)
+		(void)hipSetDevice(c->prm.device);
+		(void)hipEventSynchronize(c->order_done);
 	}
 	if (c->own_stream && c->stream)
 	{
@@ -1515,6 +1539,27 @@ int ebo_eval_device(ebo_ctx* c, const double* d_flows, int want_jac, double* d_o
 		return c->fail(EBO_ERR_ARG, "null device pointer");
 	}
 	return run_eval_device(c, d_flows, want_jac, d_out);
+}
+
+int ebo_eval_launch_shape(ebo_ctx* c, int want_jac, int* tiles, int* block, int* flow_sets)
+{
+	if (!c)
+	{
+		return EBO_ERR_ARG;
+	}
+	if (c->n_windows == 0 || c->prm.loss != EBO_LOSS_VARIANCE)
+	{
+		return c->fail(EBO_ERR_STATE, "ebo_eval_launch_shape: needs loaded windows and the variance loss");
+	}
+	EvalLaunch L;
+	const int rc = eval_launch_shape(c, want_jac, L);
+	if (rc == EBO_OK)
+	{
+		if (tiles) *tiles = L.tiles;
+		if (block) *block = L.block;
+		if (flow_sets) *flow_sets = L.flow_sets;
+	}
+	return rc;
 }
 
 int ebo_contrast_image(ebo_ctx* c, int window, int patch, const double* flow, int channels,

@@ -111,6 +111,7 @@ struct ebo_ctx
 
 	Dev<uint64_t> d_events;
 	Dev<Unit> d_units;
+	Dev<uint32_t> d_order;  // [units] the order in which a launch hands them to workgroups, heaviest first (launch_order.h); rewritten by every load
 	Dev<int32_t> d_unit_maxdt;  // [units] max |t_ref(window) - t| over the unit's events (count kernels' displacement bound)
 	Dev<double> d_flows;
 	Dev<double> d_out;
@@ -158,6 +159,7 @@ struct ebo_ctx
 	Dev<void> d_raw;  // raw 24-byte (or compact 8-byte) events staged for device bucketing
 	hipStream_t copy_stream = nullptr;  // uploads of ebo_set_windows / ebo_set_windows8, overlapped with the bucketing
 	hipEvent_t copy_done[8] = {};
+	hipEvent_t order_done = nullptr;  // behind the device path's upload of d_order, which the load does not wait for (ebo_windows.cpp)
 	Dev<void> d_bucket;  // bucketing scratch
 	Dev<unsigned int> d_chunk_hist;  // per-chunk bucket histograms / first ranks of the stable scatter
 	// ebo_set_rectification (ebo_camera.cpp): the sensor's rectification table and map; rect_set selects the

@@ -538,7 +538,8 @@ __global__ void __launch_bounds__(512, SMALL ? 4 : 3) k_eval3(const uint64_t* __
 												const double* __restrict__ flows, int tiles, int wantJac,
 												int capDoubles, double fdStep, double* __restrict__ partials,
 												double* __restrict__ out, EvalConsts c,
-												const unsigned char* __restrict__ modes, LiveWindows live)
+												const unsigned char* __restrict__ modes, LiveWindows live,
+												const uint32_t* __restrict__ order)
 {
 	extern __shared__ double lds[];
 	int unit = blockIdx.x / tiles;
@@ -553,8 +554,16 @@ __global__ void __launch_bounds__(512, SMALL ? 4 : 3) k_eval3(const uint64_t* __
 		unit = (ent >> 2) * live.upw + (unit - k * live.upw);
 		liveMode = ent & 3;
 	}
+	else
+	{
+		// a launch over every unit hands them out heaviest first (launch_order.h): workgroups start in blockIdx
+		// order, and the last to start should be the shortest-lived.  One scalar load; which workgroup evaluates a
+		// unit changes nothing in what it computes.
+		unit = static_cast<int>(order[unit]);
+	}
 	const Unit u = units[unit];
-	double* part = partials + ((static_cast<size_t>(set) * gridDim.x) + blockIdx.x) * kPartialStride;
+	// (by unit, not by blockIdx: k_combine_variance reads a unit's tiles at [set][unit][tile])
+	double* part = partials + ((static_cast<size_t>(set) * gridDim.x) + static_cast<size_t>(unit) * tiles + tile) * kPartialStride;
 	const bool fused = (tiles == 1 && gridDim.y == 1);
 	if (!(u.flags & kUnitActive))
 	{

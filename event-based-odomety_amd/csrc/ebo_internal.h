@@ -117,6 +117,7 @@ struct EvalLaunch
 {
 	const uint64_t* d_events;
 	const Unit* d_units;
+	const uint32_t* d_order = nullptr;  // [n_units] launch order of the units (launch_order.h); a launch without it is refused
 	int n_units;           // patch units only (strays excluded)
 	const double* d_flows; // [flow sets][n_flow][2]
 	int n_flow;            // flows per flow set (= Wn * P)
@@ -234,6 +235,7 @@ struct SolveLaunch
 {
 	const uint64_t* d_events;
 	const Unit* d_units;
+	const uint32_t* d_order = nullptr;  // [n_units] launch order of the units (launch_order.h)
 	int n_units;
 	int cap_doubles;
 	int block;

@@ -866,10 +866,10 @@ template <bool SMALL>
 __global__ void __launch_bounds__(512) k_solve_independent(const uint64_t* __restrict__ events,
 									const Unit* __restrict__ units, int capDoubles,
 									double* __restrict__ flowsOut, int32_t* __restrict__ stats,
-									EvalConsts c, SolveConsts o, int noReuse)
+									EvalConsts c, SolveConsts o, int noReuse, const uint32_t* __restrict__ order)
 {
 	extern __shared__ double lds[];
-	const Unit u = units[blockIdx.x];
+	const Unit u = units[order[blockIdx.x]];  // heaviest first (launch_order.h): n_ev is the known part of a solve's length
 	const uint64_t* ev = events + u.ev_off;
 	int iteration = 0, evalsCost = 0, evalsJac = 0, termination = 0;
 	double best0 = 0.0, best1 = 0.0;
@@ -1319,6 +1319,10 @@ int launch_eval_variance(const EvalLaunch& L, void* stream)
 	{
 		return 0;
 	}
+	if (!L.d_order)
+	{
+		return -2;  // no launch without the units' order table
+	}
 	const dim3 grid(L.n_units * L.tiles, L.flow_sets);
 	auto kern = (L.c.inv_sigsq <= 1.0 && L.c.fix_form != kFixBiasedGuard) ? k_eval3<true> : k_eval3<false>;
 	if (allow_big_lds(kern, L.lds_bytes))
@@ -1333,7 +1337,7 @@ int launch_eval_variance(const EvalLaunch& L, void* stream)
 	}
 	hipLaunchKernelGGL(kern, live.n > 0 ? dim3(live.n * live.upw) : grid, dim3(L.block), L.lds_bytes, s, L.d_events, L.d_units,
 					   L.d_flows, L.tiles, L.channels == 3 ? 1 : 0, L.cap_doubles, L.fd_step,
-					   L.d_partials, L.d_out, L.c, fusedPath ? L.d_modes : nullptr, live);
+					   L.d_partials, L.d_out, L.c, fusedPath ? L.d_modes : nullptr, live, L.d_order);
 	if (check_launch())
 	{
 		return -2;
@@ -2248,6 +2252,10 @@ int launch_solve_independent(const SolveLaunch& L, void* stream)
 	{
 		return 0;
 	}
+	if (!L.d_order)
+	{
+		return -2;  // no launch without the units' order table
+	}
 	const bool smallExp = L.c.inv_sigsq <= 1.0 && L.c.fix_form != kFixBiasedGuard;
 	auto kern = smallExp ? k_solve_independent<true> : k_solve_independent<false>;
 	if (allow_big_lds(kern, L.lds_bytes))
@@ -2255,7 +2263,7 @@ int launch_solve_independent(const SolveLaunch& L, void* stream)
 		return -2;
 	}
 	hipLaunchKernelGGL(kern, dim3(L.n_units), dim3(L.block), L.lds_bytes, s, L.d_events,
-					   L.d_units, L.cap_doubles, L.d_flows_out, L.d_stats, L.c, L.s, ab_env("EBO_SOLVE_NO_REUSE") ? 1 : 0);
+					   L.d_units, L.cap_doubles, L.d_flows_out, L.d_stats, L.c, L.s, ab_env("EBO_SOLVE_NO_REUSE") ? 1 : 0, L.d_order);
 	return check_launch();
 }
 

@@ -2,6 +2,7 @@
 // ebo_set_patches) and the per-window / per-patch queries: device bucketing (ebo_bucket.inc) by
 // default, the host counting sort for A/B and for grids too fine for the device histogram.
 #include "ebo_ctx.h"
+#include "launch_order.h"
 
 using namespace ebo;
 
@@ -24,6 +25,29 @@ void canonical_order(uint64_t* p, uint32_t n)
 		r += st;
 		r = r >= n ? r - n : r;
 	}
+}
+
+// The launch-order table of the units a load is about to install (launch_order.h): filled into `staging` and its
+// upload ISSUED on the context's stream, beside d_units.  Nothing waits here.  `staging` has to stay as it is until the
+// stream has passed the copy: the host paths issue it before the one synchronisation they end with anyway; the device
+// path, which knows the units only after its synchronisation, hands a block of its page-locked mirror that nothing
+// writes before the next load's synchronisation, marks the copy with order_done and returns -- everything that reads the
+// table is ordered behind the copy on the same stream (ebo_set_stream waits for the mark before it changes streams).
+// d_order is sized with d_units by ebo_create and never moves: a recorded graph holds its address.
+int upload_launch_order(ebo_ctx* c, const std::vector<Unit>& units, uint32_t* staging)
+{
+	if (units.empty())
+	{
+		return EBO_OK;
+	}
+	if (units.size() > c->d_order.cap())
+	{
+		return c->fail(EBO_ERR_STATE, "more units than the context's launch-order table holds");
+	}
+	fill_launch_order(&units[0].n_ev, &units[0].flags, sizeof(Unit), units.size(), kUnitActive, staging,
+					  static_cast<LaunchOrderKind>(ab_launch_order()));
+	return c->hip(hipMemcpyAsync(c->d_order, staging, units.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream),
+				  "H2D launch order");
 }
 }  // namespace
 
@@ -105,7 +129,8 @@ static int set_windows_on_device(ebo_ctx* c, const void* d_raw, const size_t* of
 	// staged one by one by the runtime: 0.176 -> 0.131 ms for a 15 k-event window)
 	const size_t tail = bT + bW + 256;  // unit tref | window tref | flag, contiguous in the scratch block
 	const size_t pUnits = al(nUnits * sizeof(Unit));
-	const size_t pinNeed = bOff + pUnits + tail + bW;
+	const size_t pOrder = bOff + pUnits + tail + bW;  // the launch-order table's staging, behind everything else
+	const size_t pinNeed = pOrder + al(nUnits * sizeof(uint32_t));
 	int rcp = c->grow(c->pin_bucket, pinNeed, "hipHostMalloc bucket mirror");
 	if (rcp)
 	{
@@ -242,6 +267,20 @@ static int set_windows_on_device(ebo_ctx* c, const void* d_raw, const size_t* of
 		wins[w].n_events = offsets[w + 1] - offsets[w];
 	}
 	(void)total;
+	int rco = upload_launch_order(c, units, reinterpret_cast<uint32_t*>(pin + pOrder));
+	if (rco == EBO_OK && !c->order_done)
+	{
+		rco = c->hip(hipEventCreateWithFlags(&c->order_done, hipEventDisableTiming), "launch-order event");
+	}
+	if (rco == EBO_OK)
+	{
+		rco = c->hip(hipEventRecord(c->order_done, c->stream), "launch-order event");
+	}
+	if (rco)
+	{
+		c->n_windows = 0;
+		return rco;
+	}
 	c->units.swap(units);
 	++c->units_gen;
 	c->unit_tref.swap(utref);
@@ -632,6 +671,11 @@ static int set_windows_host(ebo_ctx* c, const ebo_event* ev, const size_t* offse
 								   hipMemcpyHostToDevice, c->stream),
 					"H2D unit time spans");
 	}
+	std::vector<uint32_t> order(units.size());
+	if (rc == EBO_OK)
+	{
+		rc = upload_launch_order(c, units, order.data());
+	}
 	if (rc == EBO_OK)
 	{
 		rc = c->hip(hipStreamSynchronize(c->stream), "sync after upload");
@@ -776,6 +820,11 @@ int ebo_set_patches(ebo_ctx* c, const ebo_event* ev, const size_t* offsets, cons
 								   hipMemcpyHostToDevice, c->stream),
 					"H2D units");
 	}
+	std::vector<uint32_t> order(units.size());
+	if (rc == EBO_OK)
+	{
+		rc = upload_launch_order(c, units, order.data());
+	}
 	if (rc == EBO_OK)
 	{
 		rc = c->hip(hipStreamSynchronize(c->stream), "sync after upload");
@@ -874,6 +923,34 @@ int ebo_unit_records(ebo_ctx* c, int window, int bucket, uint64_t* out, size_t c
 	{
 		rc = c->hip(hipMemcpy(out, c->d_events.get() + u.ev_off, static_cast<size_t>(u.n_ev) * sizeof(uint64_t), hipMemcpyDeviceToHost),
 					"D2H unit records");
+	}
+	return rc;
+}
+
+int ebo_launch_order(ebo_ctx* c, uint32_t* out, size_t cap, size_t* n)
+{
+	if (!c)
+	{
+		return EBO_ERR_ARG;
+	}
+	if (c->capturing)
+	{
+		return c->fail(EBO_ERR_STATE, kNotWhileRecording);
+	}
+	if (!n || c->n_windows == 0)
+	{
+		return c->fail(EBO_ERR_ARG, "ebo_launch_order: nothing loaded, or a null count");
+	}
+	*n = c->units.size();
+	if (*n > cap || (*n && !out))
+	{
+		return c->fail(EBO_ERR_ARG, "ebo_launch_order: the table holds more entries than cap (*n says how many)");
+	}
+	(void)hipSetDevice(c->prm.device);
+	int rc = c->hip(hipStreamSynchronize(c->stream), "sync before the table read-back");
+	if (rc == EBO_OK && *n)
+	{
+		rc = c->hip(hipMemcpy(out, c->d_order.get(), *n * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H launch order");
 	}
 	return rc;
 }

@@ -434,6 +434,18 @@ int ebo_lds_rates(ebo_ctx* ctx, double* gops);
  * EBO_ERR_STATE while a graph is being recorded.  Synchronous; changes nothing. */
 int ebo_unit_records(ebo_ctx* ctx, int window, int bucket, uint64_t* out, size_t cap, size_t* n);
 
+/* Diagnostic (tests/test_gpu_launch_order.py): the launch-order table as it lies in device memory -- entry q is the index
+ * (window * (P + 1) + bucket; after ebo_set_patches the patch index) of the unit that workgroup q of a variance evaluation
+ * or a device-resident solve takes: descending event count of the active units, every other unit behind them, ties by
+ * index.  *n receives the number of units.  EBO_ERR_ARG with nothing loaded, a null count or cap < *n (*n is still set
+ * then); EBO_ERR_STATE while a graph is being recorded.  Synchronous; changes nothing. */
+int ebo_launch_order(ebo_ctx* ctx, uint32_t* out, size_t cap, size_t* n);
+
+/* Diagnostic (same test): the shape ebo_eval / ebo_eval_device give the variance evaluation of the loaded units -- row
+ * tiles per unit, lanes per workgroup, flow sets (5 with EBO_GRAD_CENTRAL and a Jacobian, else 1).  Any pointer may be
+ * null.  Launches nothing.  EBO_ERR_STATE with nothing loaded or the edge loss. */
+int ebo_eval_launch_shape(ebo_ctx* ctx, int want_jac, int* tiles, int* block, int* flow_sets);
+
 /* Diagnostic (bench.py): the traffic of ebo_count_image_device with no work -- every packed event of the
  * loaded windows read once (16-byte loads), every pixel of d_image [Wn][image_h][image_w] written once
  * (16-byte stores, all 0.0) -- as the in-run yardstick of the HBM-bound count kernels: what a plain stream
