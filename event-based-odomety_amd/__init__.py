@@ -117,6 +117,13 @@ class AlignResult(C.Structure):
                 ("mean", C.c_double), ("min", C.c_double), ("max", C.c_double), ("count", C.c_int32), ("status", C.c_int32)]
 
 
+class RpeResult(C.Structure):
+    """ebo_rpe_result: one (segment, delta) unit's relative pose error, translation then rotation."""
+    _fields_ = [("trans_rmse", C.c_double), ("trans_mean", C.c_double), ("trans_min", C.c_double), ("trans_max", C.c_double),
+                ("rot_rmse", C.c_double), ("rot_mean", C.c_double), ("rot_min", C.c_double), ("rot_max", C.c_double),
+                ("count", C.c_int32), ("status", C.c_int32)]
+
+
 def default_ba_opts(**over):
     """ebo_default_ba_opts (Ceres' Solver::Options defaults) as a SolverOpts; keyword arguments override fields."""
     o = SolverOpts()
@@ -226,6 +233,9 @@ def lib():
         _al = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.ebo_align_sim3.argtypes = _al
         _lib.ebo_align_sim3_device.argtypes = _al
+        _rpe = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ebo_trajectory_rpe.argtypes = _rpe
+        _lib.ebo_trajectory_rpe_device.argtypes = _rpe
         _lib.ebo_absolute_pose_scores.argtypes = _sc
         _lib.ebo_absolute_pose_scores_device.argtypes = _sc
         _tr = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1464,6 +1474,62 @@ class Context:
         self._check(lib().ebo_align_sim3_device(self._h, int(n_points), p(d_data), p(d_model), n, _vp(sb) if n else None,
                                                 _vp(se) if n else None, 1 if fix_scale else 0, C.addressof(res)))
         return self._align_out(res, n)
+
+    # -- relative pose error (the drift per step of an estimated trajectory, beside the ATE) -----------------
+    RPE_FIELDS = ("trans_rmse", "trans_mean", "trans_min", "trans_max", "rot_rmse", "rot_mean", "rot_min", "rot_max")
+
+    @staticmethod
+    def _rpe_args(segments, deltas, scales):
+        seg = np.asarray(segments, dtype=np.int32).reshape(-1, 2)
+        sb, se = np.ascontiguousarray(seg[:, 0]), np.ascontiguousarray(seg[:, 1])
+        dl = np.ascontiguousarray(deltas, dtype=np.int32).reshape(-1)
+        sc = None
+        if scales is not None:
+            sc = np.ascontiguousarray(scales, dtype=np.float64).reshape(-1)
+            if len(sc) != len(seg):
+                raise ValueError("one scale per segment")
+        return sb, se, dl, sc
+
+    @classmethod
+    def _rpe_out(cls, res, n, deltas):
+        nd = len(deltas)
+        out = []
+        for u in range(n * nd):
+            r = res[u]
+            d = {f: np.float64(getattr(r, f)) for f in cls.RPE_FIELDS}
+            d.update(count=int(r.count), status=int(r.status), segment=u // nd, delta=int(deltas[u % nd]))
+            out.append(d)
+        return out
+
+    def trajectory_rpe(self, gt, est, segments, deltas, scales=None):
+        """ebo_trajectory_rpe: gt (the ground-truth poses) and est (the estimated poses) float64 [n][3][4], camera to
+        world; segments a list of (begin, end) over both, which may overlap; deltas the steps (>= 1) every segment is
+        evaluated at; scales one factor per segment for the estimate's translations (None: 1).  -> one dict per
+        (segment, delta), segment-major: trans_rmse, trans_mean, trans_min, trans_max, rot_rmse, rot_mean, rot_min,
+        rot_max (radians), count (pairs), status (0 evaluated, 1 no pair, 2 a non-finite input), segment, delta."""
+        gt = np.ascontiguousarray(gt, dtype=np.float64).reshape(-1, 3, 4)
+        est = np.ascontiguousarray(est, dtype=np.float64).reshape(-1, 3, 4)
+        if len(gt) != len(est):
+            raise ValueError("gt and est must hold the same number of poses")
+        sb, se, dl, sc = self._rpe_args(segments, deltas, scales)
+        n, nd = len(sb), len(dl)
+        res = (RpeResult * max(n * nd, 1))()
+        self._check(lib().ebo_trajectory_rpe(self._h, len(gt), _vp(gt) if len(gt) else None, _vp(est) if len(est) else None, n,
+                                             _vp(sb) if n else None, _vp(se) if n else None, _vp(sc) if sc is not None and n else None,
+                                             nd, _vp(dl) if nd else None, C.addressof(res)))
+        return self._rpe_out(res, n, dl)
+
+    def trajectory_rpe_device(self, n_poses, d_gt, d_est, segments, deltas, scales=None):
+        """ebo_trajectory_rpe_device: device pointers as int for gt and est; the segments, deltas, scales and the results
+        stay on the host.  -> as trajectory_rpe."""
+        sb, se, dl, sc = self._rpe_args(segments, deltas, scales)
+        n, nd = len(sb), len(dl)
+        res = (RpeResult * max(n * nd, 1))()
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        self._check(lib().ebo_trajectory_rpe_device(self._h, int(n_poses), p(d_gt), p(d_est), n, _vp(sb) if n else None,
+                                                    _vp(se) if n else None, _vp(sc) if sc is not None and n else None, nd,
+                                                    _vp(dl) if nd else None, C.addressof(res)))
+        return self._rpe_out(res, n, dl)
 
     def triangulate(self, poses, pose_pair, f1, f2):
         """ebo_triangulate: poses float64 [n_poses][3][4] camera-to-world, pose_pair int [n][2] -> world points [n][3]."""

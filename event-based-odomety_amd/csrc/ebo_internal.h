@@ -15,6 +15,7 @@
 #include "ebo_bundle.h"
 #include "ebo_relpose.h"
 #include "ebo_align.h"
+#include "ebo_rpe.h"
 
 namespace ebo
 {
@@ -544,5 +545,11 @@ int launch_relpose_refine(int n_pairs, const int* d_offsets, const int* d_n_inli
 // d_model (double [n_points][3]); one result per segment
 int launch_align_sim3(int n_points, const double* d_data, const double* d_model, int n_segments, const int* d_seg_begin,
 					  const int* d_seg_end, int fix_scale, ebo_align_result* d_results, void* stream);
+
+// relative pose error (ebo_rpe.inc, ebo_rpe.cpp): unit g * n_deltas + k is segment g, poses d_seg_begin[g] .. d_seg_end[g] - 1 of
+// d_gt and d_est (double [n_poses][12]), at step d_deltas[k] with scale d_seg_scale[g] (null: 1); one result per unit
+int launch_trajectory_rpe(int n_poses, const double* d_gt, const double* d_est, int n_segments, const int* d_seg_begin,
+						  const int* d_seg_end, const double* d_seg_scale, int n_deltas, const int* d_deltas, ebo_rpe_result* d_results,
+						  void* stream);
 
 }  // namespace ebo

@@ -1285,6 +1285,7 @@ __global__ void __launch_bounds__(64) k_route(const uint32_t* __restrict__ xy, u
 #include "ebo_bundle.inc"
 #include "ebo_relpose.inc"
 #include "ebo_align.inc"
+#include "ebo_rpe.inc"
 #include "ebo_field.inc"
 #include "ebo_fieldtv.inc"
 #include "ebo_optimizer.inc"
@@ -2009,6 +2010,20 @@ int launch_align_sim3(int n_points, const double* d_data, const double* d_model,
 	}
 	hipLaunchKernelGGL(k_align_sim3, dim3(n_segments), dim3(kRpLanes), 0, static_cast<hipStream_t>(stream), n_points, d_data, d_model,
 					   d_seg_begin, d_seg_end, fix_scale, d_results);
+	return check_launch();
+}
+
+// relative pose error (ebo_rpe.inc): one wave per (segment, delta) unit
+int launch_trajectory_rpe(int n_poses, const double* d_gt, const double* d_est, int n_segments, const int* d_seg_begin,
+						  const int* d_seg_end, const double* d_seg_scale, int n_deltas, const int* d_deltas, ebo_rpe_result* d_results,
+						  void* stream)
+{
+	if (n_segments <= 0 || n_deltas <= 0)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_trajectory_rpe, dim3(n_segments * n_deltas), dim3(kRpLanes), 0, static_cast<hipStream_t>(stream), n_poses, d_gt,
+					   d_est, d_seg_begin, d_seg_end, d_seg_scale, n_deltas, d_deltas, d_results);
 	return check_launch();
 }
 

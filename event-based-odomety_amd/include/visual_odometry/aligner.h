@@ -7,6 +7,8 @@
 //
 //   alignPrefixes: what the reference does serially, one alignment of all keyframes so far after every new keyframe,
 //     as ONE call over every prefix of the final trajectory.
+//   relativePoseErrors / relativePoseErrorsPrefixes: the relative pose error beside the ATE, over ebo_trajectory_rpe
+//     (include/ebo.h, rules T1-T7); the reference has none.
 //   common::Sim3: Sophus::Sim3d's stand-in, as far as the path uses it: scale, rotation, translation, inverse(), and
 //     the product with a point and with a pose.
 #pragma once
@@ -182,6 +184,109 @@ inline std::vector<Alignment> alignPrefixes(ebo_ctx* ctx, const std::vector<comm
 		end.push_back(static_cast<int>(k));
 	}
 	return detail::alignSegments(ctx, reference_centres, camera_centres, begin, end, fixScale, "alignPrefixes");
+}
+
+// The relative pose error of one step size (include/ebo.h, "trajectory evaluation: relative pose error", rules T1-T7;
+// the reference has no counterpart): the drift of the estimate over `delta` poses against the ground truth's, the
+// translation in the ground truth's unit and the rotation in radians.  status as ebo_rpe_result's (0 evaluated, 1 no
+// pair, 2 a non-finite input); unless it is 0 both metrics are zero but for their count
+struct RelativeErrors
+{
+	ErrorMetricValue translation;
+	ErrorMetricValue rotation;
+	int delta = 0;
+	int status = 1;
+};
+
+namespace detail
+{
+inline std::vector<double> packedPoses(const std::vector<common::Pose3d>& poses)
+{
+	std::vector<double> out(12 * poses.size());
+	for (size_t i = 0; i < poses.size(); ++i)
+	{
+		poses[i].toArray(&out[12 * i]);
+	}
+	return out;
+}
+
+inline RelativeErrors toRelativeErrors(const ebo_rpe_result& r, int delta)
+{
+	RelativeErrors e;
+	e.translation.rmse = r.trans_rmse;
+	e.translation.mean = r.trans_mean;
+	e.translation.min = r.trans_min;
+	e.translation.max = r.trans_max;
+	e.rotation.rmse = r.rot_rmse;
+	e.rotation.mean = r.rot_mean;
+	e.rotation.min = r.rot_min;
+	e.rotation.max = r.rot_max;
+	e.translation.count = e.rotation.count = static_cast<double>(r.count);
+	e.delta = delta;
+	e.status = r.status;
+	return e;
+}
+
+// entry [g][k]: segment g at deltas[k]
+inline std::vector<std::vector<RelativeErrors>> relativeErrorsOfSegments(ebo_ctx* ctx, const std::vector<common::Pose3d>& reference_poses,
+																		 const std::vector<common::Pose3d>& camera_poses,
+																		 const std::vector<int>& begin, const std::vector<int>& end,
+																		 const std::vector<double>& scales, const std::vector<int>& deltas,
+																		 const char* who)
+{
+	if (reference_poses.size() != camera_poses.size())
+	{
+		throw std::invalid_argument(std::string(who) + ": reference and camera poses differ in length");
+	}
+	if (!scales.empty() && scales.size() != begin.size())
+	{
+		throw std::invalid_argument(std::string(who) + ": one scale per segment, or none");
+	}
+	const std::vector<double> gt = packedPoses(reference_poses), est = packedPoses(camera_poses);
+	std::vector<ebo_rpe_result> results(begin.size() * deltas.size());
+	check(ctx,
+		  ebo_trajectory_rpe(ctx, static_cast<int>(reference_poses.size()), gt.data(), est.data(), static_cast<int>(begin.size()),
+							 begin.data(), end.data(), scales.empty() ? nullptr : scales.data(), static_cast<int>(deltas.size()),
+							 deltas.data(), results.data()),
+		  who);
+	std::vector<std::vector<RelativeErrors>> out(begin.size());
+	for (size_t g = 0; g < begin.size(); ++g)
+	{
+		for (size_t k = 0; k < deltas.size(); ++k)
+		{
+			out[g].push_back(toRelativeErrors(results[g * deltas.size() + k], deltas[k]));
+		}
+	}
+	return out;
+}
+}  // namespace detail
+
+// camera pose i against reference pose i, both camera (or body) to world, over steps of deltas[k] poses: entry k is the
+// relative pose error at deltas[k], with the camera translations multiplied by `scale` (an alignment's, for an estimate
+// with a free scale).  No alignment is needed: a rigid motion of either trajectory changes nothing
+inline std::vector<RelativeErrors> relativePoseErrors(ebo_ctx* ctx, const std::vector<common::Pose3d>& reference_poses,
+													  const std::vector<common::Pose3d>& camera_poses, const std::vector<int>& deltas,
+													  double scale = 1.0)
+{
+	return detail::relativeErrorsOfSegments(ctx, reference_poses, camera_poses, {0}, {static_cast<int>(camera_poses.size())}, {scale}, deltas,
+											"relativePoseErrors")[0];
+}
+
+// every prefix of length first .. K of a K-pose trajectory in ONE call: entry [k - first][d] is the error of the first k
+// poses at deltas[d], what an evaluation after the k-th keyframe gives.  scales: one per prefix (alignPrefixes' scales),
+// or empty for 1
+inline std::vector<std::vector<RelativeErrors>> relativePoseErrorsPrefixes(ebo_ctx* ctx, const std::vector<common::Pose3d>& reference_poses,
+																			const std::vector<common::Pose3d>& camera_poses,
+																			const std::vector<int>& deltas, size_t first,
+																			const std::vector<double>& scales = {})
+{
+	std::vector<int> begin, end;
+	for (size_t k = first; k <= camera_poses.size(); ++k)
+	{
+		begin.push_back(0);
+		end.push_back(static_cast<int>(k));
+	}
+	return detail::relativeErrorsOfSegments(ctx, reference_poses, camera_poses, begin, end, scales, deltas, "relativePoseErrorsPrefixes");
 }
 
 namespace detail

@@ -30,6 +30,9 @@
 //     alignment", S1-S7, this project's own statement: parity with Eigen's JacobiSVD is not claimed).  The reference
 //     indexes gt_[i] by keyframe position even when a keyframe had no ground truth, which reads out of range; here a
 //     keyframe without a synced pose is left out of the pairing.  Without the two calls nothing of it runs;
+//   * useDeviceRelativeErrors(deltas) adds what the reference does not have: after every added keyframe the relative
+//     pose error (ebo_trajectory_rpe, include/ebo.h T1-T7) of the same paired keyframes, poses instead of centres.
+//     Without the call nothing of it runs;
 //   * the log lines are not here.
 #pragma once
 
@@ -98,6 +101,15 @@ class VisualOdometryFrontEnd
 	void useDeviceAlignment() { deviceAlignment_ = true; }
 	// of the last candidate that was aligned; status 1 and the identity before that
 	const Alignment& lastAlignment() const { return lastAlignment_; }
+	// the relative pose error at every one of `deltas` (steps in paired keyframes) after every added keyframe, once
+	// ground-truth samples are set: over the keyframes alignToGroundTruth pairs, in its order.  The estimate's
+	// translations are multiplied by lastAlignment()'s scale when that alignment has status 0, else by 1
+	void useDeviceRelativeErrors(std::vector<int> deltas) { relativeDeltas_ = std::move(deltas); }
+	// of the last added keyframe: one entry per delta; empty before the first evaluation
+	const std::vector<RelativeErrors>& lastRelativeErrors() const { return lastRelativeErrors_; }
+	// the scale they were evaluated with, and whether it is an alignment's (false: no alignment with status 0, scale 1)
+	double lastRelativeErrorsScale() const { return relativeScale_; }
+	bool lastRelativeErrorsAligned() const { return relativeAligned_; }
 	// the reference's getGtPoses(): the synced poses relative to the first, in keyframe order; after an alignment
 	// sim.inverse() * each of them
 	std::vector<common::Pose3d> const& alignedGroundTruth() const { return gtAligned_; }
@@ -152,6 +164,39 @@ class VisualOdometryFrontEnd
 		{
 			alignToGroundTruth();
 		}
+		if (!relativeDeltas_.empty())
+		{
+			evaluateRelativeErrors();
+		}
+	}
+
+	// stored and active keyframes against their synced ground-truth poses, pose by pose, in alignToGroundTruth's order
+	void evaluateRelativeErrors()
+	{
+		if (gt_.empty())
+		{
+			return;
+		}
+		std::vector<common::Pose3d> reference, cameras;
+		const auto pair = [&](const Keyframe& kf) {
+			const auto it = gt_.find(static_cast<size_t>(kf.timestamp.count()));
+			if (it != gt_.end())
+			{
+				reference.push_back(it->second);
+				cameras.push_back(kf.pose);
+			}
+		};
+		for (const auto& kf : storedFrames_)
+		{
+			pair(kf);
+		}
+		for (const auto& kf : activeFrames_)
+		{
+			pair(kf.second);
+		}
+		relativeAligned_ = lastAlignment_.status == 0;
+		relativeScale_ = relativeAligned_ ? lastAlignment_.sim.scale : 1.0;
+		lastRelativeErrors_ = relativePoseErrors(ctx_, reference, cameras, relativeDeltas_, relativeScale_);
 	}
 
 	// visual_odometry.cpp:78-97: stored and active keyframes against their synced ground-truth poses, by their centres
@@ -438,5 +483,9 @@ class VisualOdometryFrontEnd
 	std::vector<common::Pose3d> gtAligned_;
 	common::Pose3d zeroGt_;
 	Alignment lastAlignment_;
+	std::vector<int> relativeDeltas_;
+	std::vector<RelativeErrors> lastRelativeErrors_;
+	double relativeScale_ = 1.0;
+	bool relativeAligned_ = false;
 };
 }  // namespace visual_odometry

@@ -1,6 +1,6 @@
 // track_recording — the reference's feature-tracking experiment on a DAVIS240C recording directory, without OpenCV:
 //
-//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--ate]]
+//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--ate] [--rpe]]
 //
 // DIR holds events.txt, images.txt + the frames (8-bit grey PNG), optionally groundtruth.txt / calib.txt.
 // --rectify: the events of every compensation window are undistorted with the recording's calib.txt as they are
@@ -26,6 +26,12 @@
 // OUT/groundtruth_aligned.txt the synced poses relative to the first, taken into the estimate's frame by the inverse of
 // the last alignment (timestamp and [R | t] row by row).  The last line of ate.txt is printed with its status: a prefix
 // that cannot be aligned (a ground truth along a straight line is status 3) has zeros in its line.
+// --rpe (needs --odometry and a groundtruth.txt with samples): over the same synced keyframes, ONE batched call
+// (visual_odometry::relativePoseErrorsPrefixes, ebo_trajectory_rpe) evaluates the relative pose error of every prefix of
+// 3 .. K keyframes at steps of 1, 2, 5 and 10 keyframes.  OUT/rpe.txt gets one line per (prefix, step): "k delta", the
+// translation's rmse mean min max (the ground truth's unit of length), the rotation's rmse mean min max (radians), the
+// pair count, the status, the scale the estimate's translations were multiplied by and 1 when that scale is the
+// prefix's alignment's, 0 when the prefix could not be aligned and the scale is 1.  The last line is printed.
 // Writes OUT/trajectory.txt and OUT/final_cost.txt and prints one JSON line: frames, events, tracks (archived patches),
 // compensation windows, total ms (construction to the files written), ms per frame interval and Mevents/s.
 // Built by `make -C event-based-odomety_amd/csrc track_recording`.
@@ -42,7 +48,7 @@
 
 static int usage(const char* argv0)
 {
-	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--ate]]\n", argv0);
+	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--ate] [--rpe]]\n", argv0);
 	return 2;
 }
 
@@ -52,7 +58,7 @@ int main(int argc, char** argv)
 	bool trackerExperiment = false;
 	size_t windowBatch = 1;
 	bool rectify = false, rectifyFrames = false;
-	bool odometry = false, bundleAdjust = false, refine = false, refineTwoView = false, ate = false;
+	bool odometry = false, bundleAdjust = false, refine = false, refineTwoView = false, ate = false, rpe = false;
 	for (int i = 1; i < argc; ++i)
 	{
 		const std::string a = argv[i];
@@ -96,6 +102,10 @@ int main(int argc, char** argv)
 		{
 			ate = true;
 		}
+		else if (a == "--rpe")
+		{
+			rpe = true;
+		}
 		else if (a == "--window-batch" && i + 1 < argc)
 		{
 			char* end = nullptr;
@@ -115,9 +125,9 @@ int main(int argc, char** argv)
 	{
 		return usage(argv[0]);
 	}
-	if (ate && !odometry)
+	if ((ate || rpe) && !odometry)
 	{
-		std::fprintf(stderr, "track_recording: --ate evaluates the odometry's trajectory and needs --odometry\n");
+		std::fprintf(stderr, "track_recording: --ate and --rpe evaluate the odometry's trajectory and need --odometry\n");
 		return 2;
 	}
 	try
@@ -129,12 +139,12 @@ int main(int argc, char** argv)
 		p.windowBatch = windowBatch;
 		const auto recording = std::make_shared<tools::Davis240cRecording>(dataset);
 		common::GroundTruth groundTruth;
-		if (ate)
+		if (ate || rpe)
 		{
 			groundTruth = recording->getGroundTruth();
 			if (groundTruth.empty())
 			{
-				throw std::runtime_error("--ate needs " + dataset + "/groundtruth.txt with at least one sample");
+				throw std::runtime_error("--ate and --rpe need " + dataset + "/groundtruth.txt with at least one sample");
 			}
 		}
 		if (rectify)
@@ -239,10 +249,11 @@ int main(int argc, char** argv)
 					line(kf.second);
 				}
 				std::fclose(f);
-				if (ate)
+				if (ate || rpe)
 				{
 					// the reference's gt_ bookkeeping (visual_odometry.cpp:62-71) over the final trajectory
 					std::vector<common::Vector3d> reference, cameras;
+					std::vector<common::Pose3d> cameraPoses;
 					std::vector<std::pair<common::timestamp_t, common::Pose3d>> synced;
 					common::Pose3d zero;
 					const auto sync = [&](const visual_odometry::Keyframe& kf) {
@@ -256,6 +267,7 @@ int main(int argc, char** argv)
 							synced.emplace_back(kf.timestamp, zero.inverse() * pose.value());
 							reference.push_back(synced.back().second.translation());
 							cameras.push_back(kf.pose.translation());
+							cameraPoses.push_back(kf.pose);
 						}
 					};
 					for (const auto& kf : frontEnd->getStoredFrames())
@@ -268,36 +280,73 @@ int main(int argc, char** argv)
 					}
 					if (synced.size() < 3)
 					{
-						throw std::runtime_error("--ate: fewer than 3 keyframes lie within the ground truth's time span");
+						throw std::runtime_error("--ate, --rpe: fewer than 3 keyframes lie within the ground truth's time span");
 					}
 					const auto prefixes = visual_odometry::alignPrefixes(odometryCtx, reference, cameras, 3);
-					FILE* fa = std::fopen((out + "/ate.txt").c_str(), "w");
-					FILE* fg = std::fopen((out + "/groundtruth_aligned.txt").c_str(), "w");
-					if (!fa || !fg)
+					if (rpe)
 					{
-						throw std::runtime_error("cannot write " + out + "/ate.txt or groundtruth_aligned.txt");
-					}
-					for (const auto& a : prefixes)
-					{
-						std::fprintf(fa, "%.0f %.17g %.17g %.17g %.17g\n", a.ate.count, a.ate.rmse, a.ate.mean, a.ate.min, a.ate.max);
-					}
-					const common::Sim3 back = prefixes.back().sim.inverse();
-					for (const auto& g : synced)
-					{
-						double m[12];
-						(back * g.second).toArray(m);
-						std::fprintf(fg, "%lld", static_cast<long long>(g.first.count()));
-						for (const double v : m)
+						std::vector<common::Pose3d> referencePoses;
+						std::vector<double> scales;
+						for (const auto& g : synced)
 						{
-							std::fprintf(fg, " %.17g", v);
+							referencePoses.push_back(g.second);
 						}
-						std::fprintf(fg, "\n");
+						for (const auto& a : prefixes)
+						{
+							scales.push_back(a.status == 0 ? a.sim.scale : 1.0);
+						}
+						const auto errors =
+							visual_odometry::relativePoseErrorsPrefixes(odometryCtx, referencePoses, cameraPoses, {1, 2, 5, 10}, 3, scales);
+						FILE* fr = std::fopen((out + "/rpe.txt").c_str(), "w");
+						if (!fr)
+						{
+							throw std::runtime_error("cannot write " + out + "/rpe.txt");
+						}
+						char last[512] = "";
+						for (size_t i = 0; i < errors.size(); ++i)
+						{
+							for (const auto& e : errors[i])
+							{
+								std::snprintf(last, sizeof(last), "%zu %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.0f %d %.17g %d", i + 3,
+											  e.delta, e.translation.rmse, e.translation.mean, e.translation.min, e.translation.max, e.rotation.rmse,
+											  e.rotation.mean, e.rotation.min, e.rotation.max, e.translation.count, e.status, scales[i],
+											  prefixes[i].status == 0 ? 1 : 0);
+								std::fprintf(fr, "%s\n", last);
+							}
+						}
+						std::fclose(fr);
+						std::printf("rpe: %s\n", last);
 					}
-					std::fclose(fa);
-					std::fclose(fg);
-					const auto& last = prefixes.back();
-					std::printf("ate: %.0f %.17g %.17g %.17g %.17g (status %d)\n", last.ate.count, last.ate.rmse, last.ate.mean, last.ate.min,
-								last.ate.max, last.status);
+					if (ate)
+					{
+						FILE* fa = std::fopen((out + "/ate.txt").c_str(), "w");
+						FILE* fg = std::fopen((out + "/groundtruth_aligned.txt").c_str(), "w");
+						if (!fa || !fg)
+						{
+							throw std::runtime_error("cannot write " + out + "/ate.txt or groundtruth_aligned.txt");
+						}
+						for (const auto& a : prefixes)
+						{
+							std::fprintf(fa, "%.0f %.17g %.17g %.17g %.17g\n", a.ate.count, a.ate.rmse, a.ate.mean, a.ate.min, a.ate.max);
+						}
+						const common::Sim3 back = prefixes.back().sim.inverse();
+						for (const auto& g : synced)
+						{
+							double m[12];
+							(back * g.second).toArray(m);
+							std::fprintf(fg, "%lld", static_cast<long long>(g.first.count()));
+							for (const double v : m)
+							{
+								std::fprintf(fg, " %.17g", v);
+							}
+							std::fprintf(fg, "\n");
+						}
+						std::fclose(fa);
+						std::fclose(fg);
+						const auto& last = prefixes.back();
+						std::printf("ate: %.0f %.17g %.17g %.17g %.17g (status %d)\n", last.ate.count, last.ate.rmse, last.ate.mean, last.ate.min,
+									last.ate.max, last.status);
+					}
 				}
 				landmarks = frontEnd->getMapLandmarks().landmarks.size() + frontEnd->getStoredLandmarks().size();
 			}

@@ -1098,6 +1098,65 @@ int ebo_align_sim3(ebo_ctx* ctx, int n_points, const double* data, const double*
 int ebo_align_sim3_device(ebo_ctx* ctx, int n_points, const double* d_data, const double* d_model, int n_segments,
 						  const int* seg_begin, const int* seg_end, int fix_scale, ebo_align_result* results);
 
+/* ---- trajectory evaluation: relative pose error (RPE), the drift per step beside the ATE ------------------------
+ * The reference judges a trajectory by the absolute trajectory error alone; this is the other half of the usual
+ * pair (Sturm et al., "A Benchmark for the Evaluation of RGB-D SLAM Systems", IROS 2012): the error of the motion
+ * over a fixed number of poses, for MANY (segment, delta) units over one pair of pose arrays in one call.  It needs
+ * no alignment, so it has an answer where the alignment is degenerate.  tests/rpe_ref.py restates every rule in
+ * numpy.  As S1-S7: float64 throughout, one rounding per operation in exactly the association written here, no
+ * contraction, only + - * / sqrt and comparisons, a comparison with a NaN is false; dot is the two-view section's,
+ * tree64 is R6's with pair k (counted from the unit's first) dealt to partial k mod 64.
+ * A *pose* is double [3][4] row-major = [R | t], taking camera (or body) coordinates to world coordinates, as in the
+ * absolute-pose section.  `gt` holds the ground-truth poses Q_i = [G_i | g_i], `est` the estimated poses
+ * P_i = [R_i | p_i].  A unit is (segment [b, e), delta D >= 1, scale s); its pairs are (i, j = i + D) for
+ * i = b .. e - D - 1.  X[:][k] is column k of X.
+ *
+ * T1. Entry.  No pair (e - b <= D): status 1, all eight statistics 0, count = 0.  Any of the 12 doubles of any pose
+ *     of the segment, in either array, not finite, or s not finite: status 2, the statistics 0, count = the number
+ *     of pairs.  Rotation blocks are taken as given: nothing re-orthonormalises them.
+ * T2. Relative translation error, the TUM definition |trans((Q_i^-1 Q_j)^-1 (P_i^-1 P_j))| without the rotation
+ *     that preserves the norm.  dp = p_j - p_i, dg = g_j - g_i, entry by entry;
+ *       a_k = s * dot(R_i[:][k], dp);  b_k = dot(G_i[:][k], dg);  r = a - b;  q = dot(r, r);  e = sqrt(q).
+ * T3. Relative rotation.  A[r][c] = dot(R_i[:][r], R_j[:][c]) (A = R_i^T R_j);  B the same of G_i, G_j;
+ *       E[r][c] = dot(B[:][r], A[:][c]) (E = B^T A).
+ * T4. Sine and cosine of its angle.  v = (0.5 * (E21 - E12), 0.5 * (E02 - E20), 0.5 * (E10 - E01));
+ *       sn = sqrt(dot(v, v));  cs = (((E00 + E11) + E22) - 1) / 2.
+ * T5. The angle from (sn, cs) without a library function.  h = sqrt(sn * sn + cs * cs); theta = 0 unless h > 0.
+ *     Otherwise u = sn / (h + |cs|);  twice: u = u / (1 + sqrt(1 + u * u));  z = u * u;
+ *       p = c12;  p = p * z + c_k for k = 11 .. 0,  c_k = (k odd ? -1 : 1) / double(2 k + 1);
+ *       phi = 8 * (u * p);  theta = phi when cs >= 0, else double(pi) - phi.
+ *     (u is the tangent of an eighth of the angle folded onto [0, pi / 2], at most tan(pi / 16); p is the
+ *     arctangent's series to u^25.)  Exactly 0 at the identity, exactly double(pi) at a half turn; within 1e-15 of
+ *     atan2(sn, cs) in between.
+ * T6. Statistics, of e and of theta separately.  rmse = sqrt(tree64 of q / double(n_pairs)), the rotation's with
+ *     theta * theta for q;  mean = tree64 of e / double(n_pairs);  min and max over the same tree exactly as S7's
+ *     (strict comparisons, DBL_MAX and 0 as starts).  count = n_pairs, status 0.
+ * T7. Independence.  A unit's result depends neither on the other units of the call nor on the run.
+ *
+ * ebo_trajectory_rpe: gt and est are double [n_poses][3][4]; segment g covers poses seg_begin[g] .. seg_end[g] - 1
+ *   of BOTH arrays and is evaluated at every one of the n_deltas steps with the scale seg_scale[g] (NULL: 1 for
+ *   all); results is [n_segments][n_deltas].  Segments may overlap and may be prefixes of one another.  Limits:
+ *   2^24 poses per segment, 65535 segments, 16 deltas.  EBO_ERR_ARG beyond them and for a needed pointer that is
+ *   NULL, a negative count, seg_end < seg_begin, a segment outside [0, n_poses], a delta < 1.  EBO_ERR_STATE while
+ *   a graph is being recorded.  Synchronous.
+ * ebo_trajectory_rpe_device: device pointers for gt and est; segments, scales, deltas and results stay host arrays.
+ * ebo_two_view_timing brackets both: slot [0] the kernel, [4] the whole call, the others 0.
+ * Not built: an absolute rotation error (it needs the hand-eye rotation between the ground truth's body and the
+ * camera, which neither the reference nor the recording format carries); ground-truth interpolation on the device
+ * (it stays syncGroundTruth's, visual_odometry/aligner.h); pairs chosen by time or by path length. */
+typedef struct ebo_rpe_result
+{
+	double trans_rmse, trans_mean, trans_min, trans_max; /* of e (T2), in the ground truth's unit */
+	double rot_rmse, rot_mean, rot_min, rot_max;         /* of theta (T5), radians */
+	int32_t count;
+	int32_t status;
+} ebo_rpe_result;
+int ebo_trajectory_rpe(ebo_ctx* ctx, int n_poses, const double* gt, const double* est, int n_segments, const int* seg_begin,
+					   const int* seg_end, const double* seg_scale_or_null, int n_deltas, const int* deltas, ebo_rpe_result* results);
+int ebo_trajectory_rpe_device(ebo_ctx* ctx, int n_poses, const double* d_gt, const double* d_est, int n_segments,
+							  const int* seg_begin, const int* seg_end, const double* seg_scale_or_null, int n_deltas,
+							  const int* deltas, ebo_rpe_result* results);
+
 /* ---- absolute pose: three-point RANSAC on (bearing vector, landmark) pairs ----------------------------
  * What VisualOdometryFrontEnd::localizeCamera (visual_odometry.cpp:212-286) does through OpenGV's
  * AbsolutePoseSacProblem(KNEIP), stated as this project's own rules (OpenGV's source is not part of the reference
