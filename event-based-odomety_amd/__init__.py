@@ -124,6 +124,74 @@ class RpeResult(C.Structure):
                 ("count", C.c_int32), ("status", C.c_int32)]
 
 
+class TrackErrorResult(C.Structure):
+    """ebo_track_error_result: one (track, tau) unit's error statistics over its inliers, its age and where it was cut."""
+    _fields_ = [("err_mean", C.c_double), ("err_rmse", C.c_double), ("err_max", C.c_double), ("age_us", C.c_int64),
+                ("t_first_us", C.c_int64), ("n_inliers", C.c_int32), ("n_comparable", C.c_int32), ("first", C.c_int32),
+                ("cut", C.c_int32), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
+class TrackErrorSummary(C.Structure):
+    """ebo_track_error_summary_result."""
+    _fields_ = [("mean_error", C.c_double), ("mean_age_s", C.c_double), ("counted", C.c_int32), ("discarded", C.c_int32),
+                ("outlived", C.c_int32), ("pad", C.c_int32)]
+
+
+class LkParams(C.Structure):
+    """ebo_lk_params: ebo_lk_track's parameters as ebo_reference_tracks takes them."""
+    _fields_ = [("win_w", C.c_int32), ("win_h", C.c_int32), ("max_level", C.c_int32), ("max_count", C.c_int32),
+                ("epsilon", C.c_double), ("min_eig_threshold", C.c_double)]
+
+
+TRACK_ERROR_FIELDS = ("err_mean", "err_rmse", "err_max")
+TRACK_ERROR_INTS = ("age_us", "t_first_us", "n_inliers", "n_comparable", "first", "cut", "status")
+
+
+def _pack_tracks(tracks):
+    """[(t_us, xy), ..] -> (offsets int32 [n + 1], t int64, xy float64 [.][2])."""
+    ts = [np.asarray(t, dtype=np.int64).reshape(-1) for t, _ in tracks]
+    xs = [np.asarray(xy, dtype=np.float64).reshape(-1, 2) for _, xy in tracks]
+    if any(len(t) != len(x) for t, x in zip(ts, xs)):
+        raise ValueError("a track's times and positions must have the same length")
+    off = np.zeros(len(tracks) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(t) for t in ts])
+    t = np.ascontiguousarray(np.concatenate(ts) if ts else np.zeros(0, np.int64))
+    xy = np.ascontiguousarray(np.concatenate(xs) if xs else np.zeros((0, 2)))
+    return off, t, xy
+
+
+def track_seeds(tracks, frame_t_us):
+    """ebo_track_seeds: tracks a list of (t_us int64 [n], xy float64 [n][2]); frame_t_us strictly increasing.  ->
+    (seed_frame int32 [n_tracks], -1 where no frame lies within the track's life; seed_xy float32 [n_tracks][2], the
+    track's own position at that frame's time)."""
+    off, t, xy = _pack_tracks(tracks)
+    ft = np.ascontiguousarray(frame_t_us, dtype=np.int64).reshape(-1)
+    n = len(tracks)
+    sf = np.zeros(max(n, 1), dtype=np.int32)
+    sx = np.zeros((max(n, 1), 2), dtype=np.float32)
+    rc = lib().ebo_track_seeds(n, _vp(off), _vp(t) if len(t) else None, _vp(xy) if len(t) else None, len(ft),
+                               _vp(ft) if len(ft) else None, _vp(sf), _vp(sx))
+    if rc:
+        raise EboError(rc, "ebo_track_seeds: offsets, track times or frame times out of order")
+    return sf[:n], sx[:n]
+
+
+def track_error_summary(results):
+    """ebo_track_error_summary over the results of ONE tau (dicts as Context.track_errors returns them, in track
+    order): -> dict(mean_error, mean_age_s, counted, discarded, outlived)."""
+    n = len(results)
+    res = (TrackErrorResult * max(n, 1))()
+    for r, d in zip(res, results):
+        for f in TRACK_ERROR_FIELDS + TRACK_ERROR_INTS:
+            setattr(r, f, d[f])
+    out = TrackErrorSummary()
+    rc = lib().ebo_track_error_summary(n, C.addressof(res), 1, C.addressof(out))
+    if rc:
+        raise EboError(rc, "ebo_track_error_summary")
+    return dict(mean_error=np.float64(out.mean_error), mean_age_s=np.float64(out.mean_age_s), counted=int(out.counted),
+                discarded=int(out.discarded), outlived=int(out.outlived))
+
+
 def default_ba_opts(**over):
     """ebo_default_ba_opts (Ceres' Solver::Options defaults) as a SolverOpts; keyword arguments override fields."""
     o = SolverOpts()
@@ -236,6 +304,14 @@ def lib():
         _rpe = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _lib.ebo_trajectory_rpe.argtypes = _rpe
         _lib.ebo_trajectory_rpe_device.argtypes = _rpe
+        _te = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ebo_track_errors.argtypes = _te
+        _lib.ebo_track_errors_device.argtypes = _te
+        _lib.ebo_track_seeds.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ebo_reference_tracks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        _lib.ebo_track_error_summary.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ebo_default_lk_params.argtypes = [C.c_void_p]
+        _lib.ebo_default_lk_params.restype = None
         _lib.ebo_absolute_pose_scores.argtypes = _sc
         _lib.ebo_absolute_pose_scores_device.argtypes = _sc
         _tr = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1530,6 +1606,78 @@ class Context:
                                                     _vp(se) if n else None, _vp(sc) if sc is not None and n else None, nd,
                                                     _vp(dl) if nd else None, C.addressof(res)))
         return self._rpe_out(res, n, dl)
+
+    # -- track evaluation (KLT reference tracks on the frames, track error and feature age) ------------------
+    def reference_tracks(self, frames, frame_t_us, seed_frame, seed_xy, win=(21, 21), max_level=3, max_count=30, epsilon=0.01,
+                         min_eig_threshold=1e-4):
+        """ebo_reference_tracks: frames uint8 [F][h][w] at the context's size, seeds as track_seeds returns them; the
+        others are lk_track's parameters.  -> (first int32 [n], last int32 [n], xy float64 [n][F][2], 0 outside
+        [first, last]).  The context's last two images are then the last two frames."""
+        fr = np.ascontiguousarray(frames, dtype=np.uint8)
+        assert fr.ndim == 3 and fr.shape[1:] == (self.params.image_h, self.params.image_w), fr.shape
+        ft = np.ascontiguousarray(frame_t_us, dtype=np.int64).reshape(-1)
+        if len(ft) != len(fr):
+            raise ValueError("one time per frame")
+        sf = np.ascontiguousarray(seed_frame, dtype=np.int32).reshape(-1)
+        sx = np.ascontiguousarray(seed_xy, dtype=np.float32).reshape(-1, 2)
+        if len(sf) != len(sx):
+            raise ValueError("one position per seed")
+        n, F = len(sf), len(fr)
+        first = np.zeros(max(n, 1), dtype=np.int32)
+        last = np.zeros(max(n, 1), dtype=np.int32)
+        xy = np.zeros((max(n, 1), max(F, 1), 2), dtype=np.float64)
+        lk = LkParams(int(win[0]), int(win[1]), int(max_level), int(max_count), float(epsilon), float(min_eig_threshold))
+        self._check(lib().ebo_reference_tracks(self._h, F, _vp(fr) if F else None, _vp(ft) if F else None, n, _vp(sf), _vp(sx),
+                                               C.addressof(lk), _vp(first), _vp(last), _vp(xy)))
+        return first[:n], last[:n], xy[:n, :F]
+
+    @staticmethod
+    def _track_error_out(res, n, taus):
+        nt = len(taus)
+        out = []
+        for u in range(n * nt):
+            r = res[u]
+            d = {f: np.float64(getattr(r, f)) for f in TRACK_ERROR_FIELDS}
+            d.update({f: int(getattr(r, f)) for f in TRACK_ERROR_INTS})
+            d.update(track=u // nt, tau=np.float64(taus[u % nt]))
+            out.append(d)
+        return out
+
+    def track_errors(self, est_tracks, gt_tracks, taus, sample_errors=False):
+        """ebo_track_errors: est_tracks and gt_tracks lists of (t_us int64 [n], xy float64 [n][2]), one ground-truth
+        track per estimated track; taus the thresholds in pixels (at most 8).  -> one dict per (track, tau),
+        track-major: err_mean, err_rmse, err_max (over the inliers), age_us, t_first_us, n_inliers, n_comparable, first,
+        cut (-1: never beyond tau), status (0 evaluated, 1 nothing to compare, 2 a non-finite coordinate), track, tau;
+        with sample_errors also float64 [n_est], each estimated sample's error, -1 where it has none."""
+        if len(est_tracks) != len(gt_tracks):
+            raise ValueError("one ground-truth track per estimated track")
+        eo, et, exy = _pack_tracks(est_tracks)
+        go, gt, gxy = _pack_tracks(gt_tracks)
+        ta = np.ascontiguousarray(taus, dtype=np.float64).reshape(-1)
+        n, nt = len(est_tracks), len(ta)
+        res = (TrackErrorResult * max(n * nt, 1))()
+        per = np.zeros(max(len(et), 1), dtype=np.float64) if sample_errors else None
+        self._check(lib().ebo_track_errors(self._h, n, _vp(eo), _vp(et) if len(et) else None, _vp(exy) if len(et) else None,
+                                           _vp(go), _vp(gt) if len(gt) else None, _vp(gxy) if len(gt) else None, nt,
+                                           _vp(ta) if nt else None, C.addressof(res), _vp(per) if sample_errors else None))
+        out = self._track_error_out(res, n, ta)
+        return (out, per[:len(et)]) if sample_errors else out
+
+    def track_errors_device(self, est_off, d_est_t, d_est_xy, gt_off, d_gt_t, d_gt_xy, taus, d_sample_err=0):
+        """ebo_track_errors_device: device pointers as int for the four sample arrays (int64 times, float64 [.][2]
+        positions) and the per-sample errors; the offsets (int32 [n_tracks + 1]), taus and the results stay on the host.
+        -> as track_errors."""
+        eo = np.ascontiguousarray(est_off, dtype=np.int32).reshape(-1)
+        go = np.ascontiguousarray(gt_off, dtype=np.int32).reshape(-1)
+        if len(eo) != len(go) or len(eo) < 1:
+            raise ValueError("est_off and gt_off hold n_tracks + 1 entries each")
+        ta = np.ascontiguousarray(taus, dtype=np.float64).reshape(-1)
+        n, nt = len(eo) - 1, len(ta)
+        res = (TrackErrorResult * max(n * nt, 1))()
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        self._check(lib().ebo_track_errors_device(self._h, n, _vp(eo), p(d_est_t), p(d_est_xy), _vp(go), p(d_gt_t), p(d_gt_xy), nt,
+                                                  _vp(ta) if nt else None, C.addressof(res), p(d_sample_err)))
+        return self._track_error_out(res, n, ta)
 
     def triangulate(self, poses, pose_pair, f1, f2):
         """ebo_triangulate: poses float64 [n_poses][3][4] camera-to-world, pose_pair int [n][2] -> world points [n][3]."""

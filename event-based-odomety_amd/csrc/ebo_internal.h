@@ -16,6 +16,7 @@
 #include "ebo_relpose.h"
 #include "ebo_align.h"
 #include "ebo_rpe.h"
+#include "ebo_trackerr.h"
 
 namespace ebo
 {
@@ -551,5 +552,12 @@ int launch_align_sim3(int n_points, const double* d_data, const double* d_model,
 int launch_trajectory_rpe(int n_poses, const double* d_gt, const double* d_est, int n_segments, const int* d_seg_begin,
 						  const int* d_seg_end, const double* d_seg_scale, int n_deltas, const int* d_deltas, ebo_rpe_result* d_results,
 						  void* stream);
+
+// track evaluation (ebo_trackerr.inc, ebo_trackerr.cpp): unit k * n_taus + j is track k, samples d_est_off[k] .. d_est_off[k + 1] - 1
+// of d_est_t / d_est_xy (n_est of them) and d_gt_off[k] .. d_gt_off[k + 1] - 1 of d_gt_t / d_gt_xy (n_gt), at threshold d_taus[j];
+// one result per unit; d_sample_err is double [n_est] or null
+int launch_track_errors(int n_est, int n_gt, int n_tracks, const int* d_est_off, const int64_t* d_est_t, const double* d_est_xy,
+						const int* d_gt_off, const int64_t* d_gt_t, const double* d_gt_xy, int n_taus, const double* d_taus,
+						ebo_track_error_result* d_results, double* d_sample_err, void* stream);
 
 }  // namespace ebo

@@ -1286,6 +1286,7 @@ __global__ void __launch_bounds__(64) k_route(const uint32_t* __restrict__ xy, u
 #include "ebo_relpose.inc"
 #include "ebo_align.inc"
 #include "ebo_rpe.inc"
+#include "ebo_trackerr.inc"
 #include "ebo_field.inc"
 #include "ebo_fieldtv.inc"
 #include "ebo_optimizer.inc"
@@ -2024,6 +2025,20 @@ int launch_trajectory_rpe(int n_poses, const double* d_gt, const double* d_est, 
 	}
 	hipLaunchKernelGGL(k_trajectory_rpe, dim3(n_segments * n_deltas), dim3(kRpLanes), 0, static_cast<hipStream_t>(stream), n_poses, d_gt,
 					   d_est, d_seg_begin, d_seg_end, d_seg_scale, n_deltas, d_deltas, d_results);
+	return check_launch();
+}
+
+// track evaluation (ebo_trackerr.inc): one wave per (track, threshold) unit
+int launch_track_errors(int n_est, int n_gt, int n_tracks, const int* d_est_off, const int64_t* d_est_t, const double* d_est_xy,
+						const int* d_gt_off, const int64_t* d_gt_t, const double* d_gt_xy, int n_taus, const double* d_taus,
+						ebo_track_error_result* d_results, double* d_sample_err, void* stream)
+{
+	if (n_tracks <= 0 || n_taus <= 0)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_track_errors, dim3(n_tracks * n_taus), dim3(kRpLanes), 0, static_cast<hipStream_t>(stream), n_est, n_gt, d_est_off,
+					   d_est_t, d_est_xy, d_gt_off, d_gt_t, d_gt_xy, n_taus, d_taus, d_results, d_sample_err);
 	return check_launch();
 }
 

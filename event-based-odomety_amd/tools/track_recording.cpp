@@ -1,6 +1,6 @@
 // track_recording — the reference's feature-tracking experiment on a DAVIS240C recording directory, without OpenCV:
 //
-//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--ate] [--rpe]]
+//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--ate] [--rpe]]
 //
 // DIR holds events.txt, images.txt + the frames (8-bit grey PNG), optionally groundtruth.txt / calib.txt.
 // --rectify: the events of every compensation window are undistorted with the recording's calib.txt as they are
@@ -32,6 +32,15 @@
 // translation's rmse mean min max (the ground truth's unit of length), the rotation's rmse mean min max (radians), the
 // pair count, the status, the scale the estimate's translations were multiplied by and 1 when that scale is the
 // prefix's alignment's, 0 when the prefix could not be aligned and the scale is 1.  The last line is printed.
+// --track-error (needs frames; neither --odometry nor a groundtruth.txt): at the end of the run the written
+// OUT/trajectory.txt is judged against KLT reference tracks on the recording's frames (tools::TrackEvaluator,
+// tools/track_evaluator.h; include/ebo.h V1-V9): each track is seeded at its own position on the first frame inside its
+// life, followed frame to frame (ebo_reference_tracks), and compared, interpolated in time, at the threshold of
+// --track-error-threshold (pixels, default 5).  OUT/groundtruth_tracks.txt gets the reference tracks in trajectory.txt's
+// format and OUT/track_errors.txt one line per track: "id n_inliers mean rmse max age_s cut status" (cut counts the
+// track's points in time order, as tools::TrackEvaluator sorts them; -1: never beyond the threshold).  The JSON line
+// gains track_error_mean (pixels), feature_age_mean_s, tracks_counted and tracks_discarded.  With --rectify-frames the
+// frames are rectified as the tracker's were, so both sides live in one geometry.
 // Writes OUT/trajectory.txt and OUT/final_cost.txt and prints one JSON line: frames, events, tracks (archived patches),
 // compensation windows, total ms (construction to the files written), ms per frame interval and Mevents/s.
 // Built by `make -C event-based-odomety_amd/csrc track_recording`.
@@ -44,11 +53,12 @@
 #include "../include/dataset_reader/davis240c_recording.h"
 #include "../include/tools/recording_evaluator.h"
 #include "../include/tools/replayer.h"
+#include "../include/tools/track_evaluator.h"
 #include "../include/visual_odometry/visual_odometry.h"
 
 static int usage(const char* argv0)
 {
-	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--ate] [--rpe]]\n", argv0);
+	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--ate] [--rpe]]\n", argv0);
 	return 2;
 }
 
@@ -58,6 +68,8 @@ int main(int argc, char** argv)
 	bool trackerExperiment = false;
 	size_t windowBatch = 1;
 	bool rectify = false, rectifyFrames = false;
+	bool trackError = false;
+	double trackErrorThreshold = 5.0;
 	bool odometry = false, bundleAdjust = false, refine = false, refineTwoView = false, ate = false, rpe = false;
 	for (int i = 1; i < argc; ++i)
 	{
@@ -105,6 +117,19 @@ int main(int argc, char** argv)
 		else if (a == "--rpe")
 		{
 			rpe = true;
+		}
+		else if (a == "--track-error")
+		{
+			trackError = true;
+		}
+		else if (a == "--track-error-threshold" && i + 1 < argc)
+		{
+			char* end = nullptr;
+			trackErrorThreshold = std::strtod(argv[++i], &end);
+			if (!end || *end || !(trackErrorThreshold >= 0.0))
+			{
+				return usage(argv[0]);
+			}
 		}
 		else if (a == "--window-batch" && i + 1 < argc)
 		{
@@ -159,6 +184,7 @@ int main(int argc, char** argv)
 			p.rectifyFrames = true;
 		}
 		size_t events = 0, frames = 0, tracks = 0, windows = 0, keyframes = 0, landmarks = 0;
+		ebo_track_error_summary_result trackSummary{};
 		ebo_ctx* odometryCtx = nullptr;
 		if (odometry)
 		{
@@ -222,6 +248,34 @@ int main(int argc, char** argv)
 			events = evaluator.events();
 			windows = evaluator.windows();
 			tracks = evaluator.detector().getArchivedPatches().size();
+			if (trackError)
+			{
+				// the file, not the patches: what is judged is what was written, to its printed digits
+				tools::TrackEvaluator te(recording, tools::TrackEvaluator::readTracks(out + "/trajectory.txt"));
+				if (rectifyFrames)
+				{
+					te.rectifyFrames(recording->getCalibration(), odometryCamera);
+				}
+				const auto& reference = te.referenceTracks();
+				if (ebo_write_tracks_txt((out + "/groundtruth_tracks.txt").c_str(), reference.data(), reference.size()) != EBO_OK)
+				{
+					throw std::runtime_error("cannot write " + out + "/groundtruth_tracks.txt");
+				}
+				const auto& results = te.evaluate({trackErrorThreshold});
+				FILE* f = std::fopen((out + "/track_errors.txt").c_str(), "w");
+				if (!f)
+				{
+					throw std::runtime_error("cannot write " + out + "/track_errors.txt");
+				}
+				for (size_t k = 0; k < results.size(); ++k)
+				{
+					const ebo_track_error_result& r = results[k];
+					std::fprintf(f, "%lld %d %.17g %.17g %.17g %.17g %d %d\n", static_cast<long long>(te.ids()[k]), r.n_inliers, r.err_mean,
+								 r.err_rmse, r.err_max, static_cast<double>(r.age_us) * 1e-6, r.cut, r.status);
+				}
+				std::fclose(f);
+				trackSummary = te.summary(trackErrorThreshold);
+			}
 			if (odometry)
 			{
 				FILE* f = std::fopen((out + "/keyframe_poses.txt").c_str(), "w");
@@ -358,10 +412,16 @@ int main(int argc, char** argv)
 		const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 		std::printf("{\"frames\": %zu, \"events\": %zu, \"tracks\": %zu, \"windows\": %zu, \"total_ms\": %.3f, "
 					"\"ms_per_frame_interval\": %.4f, \"mevents_per_s\": %.4f, \"tracker_experiment\": %s, "
-					"\"window_batch\": %zu, \"rectify\": %s, \"odometry\": %s, \"keyframes\": %zu, \"landmarks\": %zu}\n",
+					"\"window_batch\": %zu, \"rectify\": %s, \"odometry\": %s, \"keyframes\": %zu, \"landmarks\": %zu",
 					frames, events, tracks, windows, ms, frames > 1 ? ms / static_cast<double>(frames - 1) : 0.0,
 					ms > 0 ? static_cast<double>(events) / (ms * 1e3) : 0.0, trackerExperiment ? "true" : "false",
 					windowBatch, rectify ? "true" : "false", odometry ? "true" : "false", keyframes, landmarks);
+		if (trackError)
+		{
+			std::printf(", \"track_error_mean\": %.17g, \"feature_age_mean_s\": %.17g, \"tracks_counted\": %d, \"tracks_discarded\": %d",
+						trackSummary.mean_error, trackSummary.mean_age_s, trackSummary.counted, trackSummary.discarded);
+		}
+		std::printf("}\n");
 	}
 	catch (const std::exception& e)
 	{

@@ -1157,6 +1157,112 @@ int ebo_trajectory_rpe_device(ebo_ctx* ctx, int n_poses, const double* d_gt, con
 							  const int* seg_begin, const int* seg_end, const double* seg_scale_or_null, int n_deltas,
 							  const int* deltas, ebo_rpe_result* results);
 
+/* ---- track evaluation: KLT reference tracks on the frames, track error and feature age ------------------------
+ * The two figures the reference's report judges the feature tracker by, mean track error in pixels and feature age in
+ * seconds, by the protocol published for event-based trackers on real recordings (Gehrig et al., "EKLT: Asynchronous
+ * Photometric Feature Tracking using Events and Frames"): a KLT track on the recording's frames, seeded at the event
+ * track's position on the first frame inside its life, is the ground truth; the event track is compared against it,
+ * interpolated in time, and its age ends when the error first exceeds a threshold tau.  The reference has no such
+ * code.  tests/trackerr_ref.py restates every rule in numpy.  As S and T: float64 throughout, one rounding per
+ * operation in exactly the association written here, no contraction, only + - * / sqrt and comparisons, a comparison
+ * with a NaN is false; tree64 is R6's.
+ * A *track* is its samples (t_i, x_i, y_i), i = 0 .. n - 1, t in integer microseconds (below 2^53).  The estimated
+ * track's times do not decrease; the ground-truth track's, gt_t, increase strictly; first and last are its first and
+ * last sample.  A unit is (track, tau).
+ *
+ * V1. Entry.  In this order: no estimated sample, or fewer than 2 ground-truth samples: status 1.  Any coordinate of
+ *     any estimated or ground-truth sample of the track not finite, inside the span of V2 or not: status 2.  No
+ *     estimated sample with gt_t[first] <= t <= gt_t[last]: status 1.  In all three every field of the result is 0
+ *     (first and cut mean something under status 0 only).
+ * V2. Comparable samples: the estimated samples with gt_t[first] <= t_i <= gt_t[last], a contiguous run [i0, i1)
+ *     because times do not decrease.  Earlier samples are skipped, later ones are not judged.
+ * V3. Interpolation of a track (t, p) at time T, t[0] <= T <= t[last]:  j = the largest index with t[j] <= T.  When
+ *     t[j] == T:  g = p[j] exactly.  Otherwise  w = double(T - t[j]) / double(t[j+1] - t[j])  (the int64 differences
+ *     are exact);  g = p[j] + w * (p[j+1] - p[j])  per component: subtract, multiply, add.
+ * V4. Error of a comparable sample (t, x, y):  (gx, gy) = the ground-truth track at t by V3;  dx = x - gx;
+ *     dy = y - gy;  q = dx * dx + dy * dy;  e = sqrt(q).
+ * V5. Cut.  c = the first comparable sample in index order with e > tau (strictly); the inliers are the comparable
+ *     samples before c, all of them when there is no c.  cut = c's index within the track, or -1.
+ * V6. Age.  age_us = t(last inlier) - t(first inlier) as int64; the first inlier is sample i0.  With no inlier (sample
+ *     i0 is beyond tau already): status 0, n_inliers = 0, cut = i0, age and statistics 0.  t_first_us = t(i0);
+ *     first = i0;  n_comparable = i1 - i0.
+ * V7. Statistics over the inliers, inlier k (counted from i0) dealt to partial k mod 64:
+ *     err_mean = tree64 of e / double(n_inliers);  err_rmse = sqrt(tree64 of q / double(n_inliers));  err_max over
+ *     the same tree exactly as S7's max (strict comparisons, 0 as start).
+ * V8. Per-sample output, where asked: sample_err_out[i] = e (V4) for comparable samples and -1.0 for all others; all
+ *     -1.0 for a track whose status is not 0.  It does not depend on tau.
+ * V9. Independence.  A unit's result depends neither on the other units of the call nor on the run.
+ *
+ * ebo_track_seeds (host only, no context): where a KLT track starts for each estimated track.  Track k owns samples
+ *   est_off[k] .. est_off[k+1] - 1 of est_t_us (int64) and est_xy (double [.][2]); frame_t_us [n_frames] increases
+ *   strictly.  f = the first frame with frame_t_us[f] >= t_0.  seed_frame[k] = -1 and seed_xy[k] = (0, 0) when there is
+ *   none, when frame_t_us[f] > t_(n-1), or when the track is empty.  Otherwise seed_frame[k] = f and seed_xy[k] = the
+ *   track ITSELF at frame_t_us[f] by V3 (of samples with equal times the last one counts), rounded to float, LK's
+ *   type.  EBO_ERR_ARG for a needed pointer that is NULL, a negative count, offsets that decrease or do not start at
+ *   0, estimated times that decrease within a track, frame times that do not increase strictly.
+ * ebo_reference_tracks: the KLT tracks of n seeds through `frames`, uint8 [n_frames][image_h][image_w] on the host at
+ *   the context's size, taken at frame_t_us (not read beyond the NULL check: the frames' order is the arrays').  BY
+ *   DEFINITION the hand-written loop: ebo_lk_add_image(frame 0); for f = 0 .. n_frames - 2: ebo_lk_add_image(frame
+ *   f + 1), then, if any track is alive at f, ONE ebo_lk_track of all of them, in seed order, from their positions at
+ *   f, with the parameters of ebo_lk_track in lk_or_null (NULL: ebo_default_lk_params' values, the reference's
+ *   FlowEstimator ones: 21 x 21, 3, 30, 0.01, 1e-4).  A track becomes alive at its seed frame, at seed_xy.  After a launch it stays alive
+ *   iff status == 1 and 0 <= x < image_w and 0 <= y < image_h at the new position; otherwise last[k] = f.  first[k] =
+ *   seed_frame[k]; last[k] = the last frame at which the track has a position; xy is double [n][n_frames][2], the
+ *   float results widened, 0 outside [first, last].  seed_frame < 0: first = last = -1.  No LK kernel of its own.  It
+ *   leaves the context's "last two images" as that loop does: the last two frames (one frame: that frame as the newer
+ *   image).  EBO_ERR_ARG for a needed pointer that is NULL, negative counts, a seed_frame >= n_frames, and whatever
+ *   ebo_lk_track refuses.  EBO_ERR_STATE while a graph is being recorded.  Synchronous.
+ * ebo_track_errors: track k owns estimated samples est_off[k] .. est_off[k+1] - 1 and ground-truth samples
+ *   gt_off[k] .. gt_off[k+1] - 1; every track is evaluated at each of the n_taus thresholds (pixels); results is
+ *   [n_tracks][n_taus]; sample_err_out_or_null is double [est_off[n_tracks]] (V8).  One launch, one wave per unit.
+ *   Limits: 65535 tracks, 8 thresholds, 2^24 samples per track on either side.  EBO_ERR_ARG beyond them and, checked
+ *   on the host before the launch, for a needed pointer that is NULL, negative counts, offsets that decrease or do not
+ *   start at 0, ground-truth times not strictly increasing within a track, estimated times decreasing within a track,
+ *   a tau that is NaN or negative (+infinity is allowed: it never cuts).  EBO_ERR_STATE while a graph is being
+ *   recorded.  Synchronous.
+ * ebo_track_errors_device: device pointers for the four sample arrays and sample_err_out; offsets, taus and results
+ *   stay host arrays.  It cannot look at the times: tracks whose times are out of order get unspecified numbers, never
+ *   an access outside the arrays.
+ * ebo_two_view_timing brackets both: slot [0] the kernel, [4] the whole call, the others 0.
+ * ebo_track_error_summary (host only): over results[k * stride] for k = 0 .. n_tracks - 1 (one tau of a results
+ *   array: results + j with stride n_taus), in track order with sequential double sums.  Counted tracks have status 0
+ *   and n_inliers >= 1; m = their number; discarded = n_tracks - m;  mean_error = (sum of err_mean) / double(m), the
+ *   report's Table 1;  mean_age_s = ((sum of double(age_us)) / double(m)) * 1e-6, Table 2;  outlived = the counted
+ *   tracks with cut == -1, whose age is censored by the end of the track or of the ground truth.  m = 0: every field 0, discarded too.
+ * Not built: ground truth from a simulated recording's projected landmarks (neither the reference nor the dataset
+ *   carries depth); re-seeding a reference track after it is lost. */
+typedef struct ebo_track_error_result
+{
+	double err_mean, err_rmse, err_max; /* of e (V4) over the inliers, pixels */
+	int64_t age_us, t_first_us;
+	int32_t n_inliers, n_comparable, first, cut, status, pad;
+} ebo_track_error_result;
+typedef struct ebo_track_error_summary_result
+{
+	double mean_error; /* pixels */
+	double mean_age_s;
+	int32_t counted, discarded, outlived, pad;
+} ebo_track_error_summary_result;
+typedef struct ebo_lk_params
+{
+	int32_t win_w, win_h, max_level, max_count;
+	double epsilon, min_eig_threshold;
+} ebo_lk_params;
+void ebo_default_lk_params(ebo_lk_params* p);
+int ebo_track_seeds(int n_tracks, const int* est_off, const int64_t* est_t_us, const double* est_xy, int n_frames,
+					const int64_t* frame_t_us, int* seed_frame, float* seed_xy);
+int ebo_reference_tracks(ebo_ctx* ctx, int n_frames, const uint8_t* frames, const int64_t* frame_t_us, int n,
+						 const int* seed_frame, const float* seed_xy, const ebo_lk_params* lk_or_null, int* first, int* last,
+						 double* xy);
+int ebo_track_errors(ebo_ctx* ctx, int n_tracks, const int* est_off, const int64_t* est_t_us, const double* est_xy,
+					 const int* gt_off, const int64_t* gt_t_us, const double* gt_xy, int n_taus, const double* taus,
+					 ebo_track_error_result* results, double* sample_err_out_or_null);
+int ebo_track_errors_device(ebo_ctx* ctx, int n_tracks, const int* est_off, const int64_t* d_est_t_us, const double* d_est_xy,
+							const int* gt_off, const int64_t* d_gt_t_us, const double* d_gt_xy, int n_taus, const double* taus,
+							ebo_track_error_result* results, double* d_sample_err_out_or_null);
+int ebo_track_error_summary(int n_tracks, const ebo_track_error_result* results, int stride,
+							ebo_track_error_summary_result* out);
+
 /* ---- absolute pose: three-point RANSAC on (bearing vector, landmark) pairs ----------------------------
  * What VisualOdometryFrontEnd::localizeCamera (visual_odometry.cpp:212-286) does through OpenGV's
  * AbsolutePoseSacProblem(KNEIP), stated as this project's own rules (OpenGV's source is not part of the reference
