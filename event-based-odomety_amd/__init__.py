@@ -117,6 +117,18 @@ class AlignResult(C.Structure):
                 ("mean", C.c_double), ("min", C.c_double), ("max", C.c_double), ("count", C.c_int32), ("status", C.c_int32)]
 
 
+class LandmarkParams(C.Structure):
+    """ebo_landmark_params."""
+    _fields_ = [("threshold", C.c_double), ("min_parallax", C.c_double), ("min_inliers", C.c_int32), ("max_hypotheses", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
+class LandmarkResult(C.Structure):
+    """ebo_landmark_result: one landmark's point, parallax, largest finite score and L6 status."""
+    _fields_ = [("point", C.c_double * 3), ("parallax", C.c_double), ("score_max", C.c_double), ("status", C.c_int32),
+                ("n_obs", C.c_int32), ("n_inliers", C.c_int32), ("winner", C.c_int32), ("hypotheses", C.c_int32), ("reserved", C.c_int32)]
+
+
 class RpeResult(C.Structure):
     """ebo_rpe_result: one (segment, delta) unit's relative pose error, translation then rotation."""
     _fields_ = [("trans_rmse", C.c_double), ("trans_mean", C.c_double), ("trans_min", C.c_double), ("trans_max", C.c_double),
@@ -304,6 +316,13 @@ def lib():
         _rpe = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _lib.ebo_trajectory_rpe.argtypes = _rpe
         _lib.ebo_trajectory_rpe_device.argtypes = _rpe
+        _lmt = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        _lib.ebo_default_landmark_params.argtypes = [C.c_void_p]
+        _lib.ebo_default_landmark_params.restype = None
+        _lib.ebo_triangulate_tracks.argtypes = _lmt
+        _lib.ebo_triangulate_tracks_device.argtypes = _lmt
+        _lib.ebo_landmark_scores.argtypes = _lmt + [C.c_void_p]
+        _lib.ebo_landmark_scores_device.argtypes = _lmt + [C.c_void_p]
         _te = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.ebo_track_errors.argtypes = _te
         _lib.ebo_track_errors_device.argtypes = _te
@@ -1606,6 +1625,106 @@ class Context:
                                                     _vp(se) if n else None, _vp(sc) if sc is not None and n else None, nd,
                                                     _vp(dl) if nd else None, C.addressof(res)))
         return self._rpe_out(res, n, dl)
+
+    # -- landmark maintenance (N-view triangulation of whole observation lists, the audit of landmarks) --------
+    LANDMARK_DOUBLES = ("parallax", "score_max")
+    LANDMARK_INTS = ("status", "n_obs", "n_inliers", "winner", "hypotheses")
+
+    @staticmethod
+    def landmark_params(**kw):
+        """ebo_default_landmark_params with the given fields replaced -> LandmarkParams."""
+        p = LandmarkParams()
+        lib().ebo_default_landmark_params(C.byref(p))
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise ValueError("no landmark parameter " + k)
+            setattr(p, k, v)
+        return p
+
+    LANDMARK_DTYPE = np.dtype([("point", np.float64, 3), ("parallax", np.float64), ("score_max", np.float64), ("status", np.int32),
+                               ("n_obs", np.int32), ("n_inliers", np.int32), ("winner", np.int32), ("hypotheses", np.int32),
+                               ("reserved", np.int32)])
+
+    @classmethod
+    def _landmark_out(cls, res, n):
+        rec = np.frombuffer(res, dtype=cls.LANDMARK_DTYPE, count=n)
+        return {f: rec[f].copy() for f in ("point",) + cls.LANDMARK_DOUBLES + cls.LANDMARK_INTS}
+
+    def _landmarks(self, solve, poses, obs_offsets, obs_pose, obs_f, points, params, want_scores, want_flags):
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3, 4)
+        off = np.ascontiguousarray(obs_offsets, dtype=np.int32).reshape(-1)
+        if len(off) < 1:
+            raise ValueError("obs_offsets holds n_landmarks + 1 entries")
+        n = len(off) - 1
+        idx = np.ascontiguousarray(obs_pose, dtype=np.int32).reshape(-1)
+        f = np.ascontiguousarray(obs_f, dtype=np.float64).reshape(-1, 3)
+        total = max(int(off[-1]), 0)
+        if len(idx) < total or len(f) < total:
+            raise ValueError("obs_pose and obs_f hold obs_offsets[-1] observations")
+        prm = params if params is not None else self.landmark_params()
+        res = (LandmarkResult * max(n, 1))()
+        scores = np.zeros(total) if want_scores else None
+        flags = np.zeros(total, dtype=np.uint8) if want_flags else None
+        args = [self._h, len(poses), _vp(poses) if len(poses) else None, n, _vp(off), _vp(idx) if total else None,
+                _vp(f) if total else None]
+        if not solve:
+            pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+            if len(pts) != n:
+                raise ValueError("one point per landmark")
+            args.append(_vp(pts) if n else None)
+        args += [C.byref(prm), C.addressof(res), _vp(scores) if want_scores and total else None,
+                 _vp(flags) if want_flags and total else None]
+        self._check((lib().ebo_triangulate_tracks if solve else lib().ebo_landmark_scores)(*args))
+        out = self._landmark_out(res, n)
+        if want_scores:
+            out["scores"] = scores
+        if want_flags:
+            out["flags"] = flags
+        return out
+
+    def triangulate_tracks(self, poses, obs_offsets, obs_pose, obs_f, params=None, scores=True, flags=True):
+        """ebo_triangulate_tracks: poses float64 [n_poses][3][4], camera to world; landmark l owns observations
+        obs_offsets[l] .. obs_offsets[l + 1] - 1 of obs_pose (int32 pose indices) and obs_f (float64 [.][3] bearing
+        vectors).  Consensus over two-observation hypotheses, least squares over the winner's inliers (L1-L6 of
+        include/ebo.h).  -> dict of arrays with one row per landmark: point [n][3], parallax, score_max, status, n_obs,
+        n_inliers, winner, hypotheses; and per observation `scores` and `flags` (unless switched off)."""
+        return self._landmarks(True, poses, obs_offsets, obs_pose, obs_f, None, params, scores, flags)
+
+    def landmark_scores(self, poses, obs_offsets, obs_pose, obs_f, points, params=None, scores=True, flags=True):
+        """ebo_landmark_scores: the audit (L7) of the given points float64 [n_landmarks][3] against their observations
+        under the given poses.  -> as triangulate_tracks; status 0 keeps a landmark."""
+        return self._landmarks(False, poses, obs_offsets, obs_pose, obs_f, points, params, scores, flags)
+
+    def _landmarks_device(self, solve, n_poses, d_poses, obs_offsets, d_obs_pose, d_obs_f, d_points, params, d_results, d_scores, d_flags):
+        off = np.ascontiguousarray(obs_offsets, dtype=np.int32).reshape(-1)
+        if len(off) < 1:
+            raise ValueError("obs_offsets holds n_landmarks + 1 entries")
+        prm = params if params is not None else self.landmark_params()
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        args = [self._h, int(n_poses), p(d_poses), len(off) - 1, _vp(off), p(d_obs_pose), p(d_obs_f)]
+        if not solve:
+            args.append(p(d_points))
+        args += [C.byref(prm), p(d_results), p(d_scores), p(d_flags)]
+        self._check((lib().ebo_triangulate_tracks_device if solve else lib().ebo_landmark_scores_device)(*args))
+
+    def triangulate_tracks_device(self, n_poses, d_poses, obs_offsets, d_obs_pose, d_obs_f, d_results, params=None, d_scores=None,
+                                  d_flags=None):
+        """ebo_triangulate_tracks_device: device pointers as int; obs_offsets and params stay on the host; d_results
+        receives n_landmarks ebo_landmark_result records (64 bytes each).  Asynchronous on the context's stream."""
+        self._landmarks_device(True, n_poses, d_poses, obs_offsets, d_obs_pose, d_obs_f, None, params, d_results, d_scores, d_flags)
+
+    def landmark_scores_device(self, n_poses, d_poses, obs_offsets, d_obs_pose, d_obs_f, d_points, d_results, params=None,
+                               d_scores=None, d_flags=None):
+        """ebo_landmark_scores_device: as triangulate_tracks_device with the points on the device."""
+        self._landmarks_device(False, n_poses, d_poses, obs_offsets, d_obs_pose, d_obs_f, d_points, params, d_results, d_scores, d_flags)
+
+    @classmethod
+    def landmark_results(cls, raw):
+        """The bytes of n ebo_landmark_result records (a uint8 array copied back from the device) -> the dict of
+        triangulate_tracks without scores and flags."""
+        raw = np.ascontiguousarray(raw, dtype=np.uint8).reshape(-1)
+        n = raw.size // cls.LANDMARK_DTYPE.itemsize
+        return cls._landmark_out(raw[:n * cls.LANDMARK_DTYPE.itemsize].tobytes(), n)
 
     # -- track evaluation (KLT reference tracks on the frames, track error and feature age) ------------------
     def reference_tracks(self, frames, frame_t_us, seed_frame, seed_xy, win=(21, 21), max_level=3, max_count=30, epsilon=0.01,

@@ -17,6 +17,7 @@
 #include "ebo_align.h"
 #include "ebo_rpe.h"
 #include "ebo_trackerr.h"
+#include "ebo_landmark.h"
 
 namespace ebo
 {
@@ -552,6 +553,12 @@ int launch_align_sim3(int n_points, const double* d_data, const double* d_model,
 int launch_trajectory_rpe(int n_poses, const double* d_gt, const double* d_est, int n_segments, const int* d_seg_begin,
 						  const int* d_seg_end, const double* d_seg_scale, int n_deltas, const int* d_deltas, ebo_rpe_result* d_results,
 						  void* stream);
+
+// landmark maintenance (ebo_landmark.inc, ebo_landmark.cpp): solve != 0 triangulates (L1-L6), otherwise audits d_points (L7);
+// `lanes` per landmark is 64, or 16 when no landmark of the call holds more than kLmGroupMaxObs observations
+int launch_landmarks(int solve, int lanes, int n_poses, const double* d_poses, int n_landmarks, const int* d_offsets,
+					 const int* d_obs_pose, const double* d_obs_f, const double* d_points, const ebo_landmark_params* params,
+					 ebo_landmark_result* d_results, double* d_scores, uint8_t* d_flags, void* stream);
 
 // track evaluation (ebo_trackerr.inc, ebo_trackerr.cpp): unit k * n_taus + j is track k, samples d_est_off[k] .. d_est_off[k + 1] - 1
 // of d_est_t / d_est_xy (n_est of them) and d_gt_off[k] .. d_gt_off[k + 1] - 1 of d_gt_t / d_gt_xy (n_gt), at threshold d_taus[j];

@@ -1287,6 +1287,7 @@ __global__ void __launch_bounds__(64) k_route(const uint32_t* __restrict__ xy, u
 #include "ebo_align.inc"
 #include "ebo_rpe.inc"
 #include "ebo_trackerr.inc"
+#include "ebo_landmark.inc"
 #include "ebo_field.inc"
 #include "ebo_fieldtv.inc"
 #include "ebo_optimizer.inc"
@@ -2026,6 +2027,40 @@ int launch_trajectory_rpe(int n_poses, const double* d_gt, const double* d_est, 
 	hipLaunchKernelGGL(k_trajectory_rpe, dim3(n_segments * n_deltas), dim3(kRpLanes), 0, static_cast<hipStream_t>(stream), n_poses, d_gt,
 					   d_est, d_seg_begin, d_seg_end, d_seg_scale, n_deltas, d_deltas, d_results);
 	return check_launch();
+}
+
+// landmark maintenance (ebo_landmark.inc): a group of `lanes` lanes per landmark, 64 / lanes landmarks per wave
+template <bool SOLVE, int W>
+int launch_landmarks_as(int n_poses, const double* d_poses, int n_landmarks, const int* d_offsets, const int* d_obs_pose,
+						const double* d_obs_f, const double* d_points, const LmParamsArg& prm, ebo_landmark_result* d_results,
+						double* d_scores, uint8_t* d_flags, void* stream)
+{
+	constexpr int kGroups = 64 / W;
+	hipLaunchKernelGGL((k_landmarks<SOLVE, W>), dim3((n_landmarks + kGroups - 1) / kGroups), dim3(64), 0, static_cast<hipStream_t>(stream),
+					   n_poses, d_poses, n_landmarks, d_offsets, d_obs_pose, d_obs_f, d_points, prm, d_results, d_scores, d_flags);
+	return check_launch();
+}
+
+int launch_landmarks(int solve, int lanes, int n_poses, const double* d_poses, int n_landmarks, const int* d_offsets,
+					 const int* d_obs_pose, const double* d_obs_f, const double* d_points, const ebo_landmark_params* params,
+					 ebo_landmark_result* d_results, double* d_scores, uint8_t* d_flags, void* stream)
+{
+	if (n_landmarks <= 0)
+	{
+		return 0;
+	}
+	const LmParamsArg prm = {params->threshold, params->min_parallax, params->min_inliers, params->max_hypotheses, params->seed};
+	if (solve)
+	{
+		return lanes == 16 ? launch_landmarks_as<true, 16>(n_poses, d_poses, n_landmarks, d_offsets, d_obs_pose, d_obs_f, d_points, prm,
+														   d_results, d_scores, d_flags, stream)
+						   : launch_landmarks_as<true, 64>(n_poses, d_poses, n_landmarks, d_offsets, d_obs_pose, d_obs_f, d_points, prm,
+														   d_results, d_scores, d_flags, stream);
+	}
+	return lanes == 16 ? launch_landmarks_as<false, 16>(n_poses, d_poses, n_landmarks, d_offsets, d_obs_pose, d_obs_f, d_points, prm,
+														d_results, d_scores, d_flags, stream)
+					   : launch_landmarks_as<false, 64>(n_poses, d_poses, n_landmarks, d_offsets, d_obs_pose, d_obs_f, d_points, prm,
+														d_results, d_scores, d_flags, stream);
 }
 
 // track evaluation (ebo_trackerr.inc): one wave per (track, threshold) unit

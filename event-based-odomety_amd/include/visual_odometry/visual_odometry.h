@@ -33,6 +33,9 @@
 //   * useDeviceRelativeErrors(deltas) adds what the reference does not have: after every added keyframe the relative
 //     pose error (ebo_trajectory_rpe, include/ebo.h T1-T7) of the same paired keyframes, poses instead of centres.
 //     Without the call nothing of it runs;
+//   * useDeviceMapMaintenance(params) adds what the reference leaves as TODOs (:169, :407): after the optimizer hook of
+//     every added keyframe the map is audited and repaired (map_maintenance.h): landmarks can be replaced and erased
+//     between keyframes, observations never.  Without the call nothing of it runs;
 //   * the log lines are not here.
 #pragma once
 
@@ -42,6 +45,7 @@
 
 #include "aligner.h"
 #include "bundle_adjustment.h"
+#include "map_maintenance.h"
 #include "two_view.h"
 
 namespace visual_odometry
@@ -110,6 +114,14 @@ class VisualOdometryFrontEnd
 	// the scale they were evaluated with, and whether it is an alignment's (false: no alignment with status 0, scale 1)
 	double lastRelativeErrorsScale() const { return relativeScale_; }
 	bool lastRelativeErrorsAligned() const { return relativeAligned_; }
+	// maintainMap (map_maintenance.h) after the optimizer hook of every added keyframe and before the alignment
+	void useDeviceMapMaintenance(const MapMaintenanceParams& params)
+	{
+		mapMaintenance_ = params;
+		deviceMapMaintenance_ = true;
+	}
+	// of the last added keyframe; zeros before the first
+	const MapMaintenanceSummary& lastMapMaintenance() const { return lastMapMaintenance_; }
 	// the reference's getGtPoses(): the synced poses relative to the first, in keyframe order; after an alignment
 	// sim.inverse() * each of them
 	std::vector<common::Pose3d> const& alignedGroundTruth() const { return gtAligned_; }
@@ -159,6 +171,10 @@ class VisualOdometryFrontEnd
 		if (optimizer_)
 		{
 			optimizer_(activeFrames_, mapLandmarks_);
+		}
+		if (deviceMapMaintenance_)
+		{
+			lastMapMaintenance_ = maintainMap(ctx_, calibration_, mapMaintenance_, activeFrames_, mapLandmarks_);
 		}
 		if (deviceAlignment_)
 		{
@@ -487,5 +503,8 @@ class VisualOdometryFrontEnd
 	std::vector<RelativeErrors> lastRelativeErrors_;
 	double relativeScale_ = 1.0;
 	bool relativeAligned_ = false;
+	bool deviceMapMaintenance_ = false;
+	MapMaintenanceParams mapMaintenance_;
+	MapMaintenanceSummary lastMapMaintenance_;
 };
 }  // namespace visual_odometry

@@ -1,6 +1,6 @@
 // track_recording — the reference's feature-tracking experiment on a DAVIS240C recording directory, without OpenCV:
 //
-//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--ate] [--rpe]]
+//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--maintain-map] [--ate] [--rpe]]
 //
 // DIR holds events.txt, images.txt + the frames (8-bit grey PNG), optionally groundtruth.txt / calib.txt.
 // --rectify: the events of every compensation window are undistorted with the recording's calib.txt as they are
@@ -19,6 +19,9 @@
 // useDeviceLocalizeRefinement).
 // --refine-two-view (needs --odometry): the refinement after the two-view RANSAC of initCameras through
 // ebo_relative_pose_refine (twoView().useDeviceRefinement()).
+// --maintain-map (needs --odometry): after every added keyframe the map is audited and repaired
+// (useDeviceMapMaintenance, visual_odometry/map_maintenance.h; include/ebo.h L1-L7) and one line per keyframe is printed:
+// "map: <timestamp> candidates audited kept retriangulated added culled landmarks".
 // --ate (needs --odometry and a groundtruth.txt with samples): at the end of the run every keyframe is synced against the
 // ground truth (visual_odometry::syncGroundTruth; a keyframe outside the samples' time span takes no part), and ONE
 // batched call (visual_odometry::alignPrefixes, ebo_align_sim3) aligns every prefix of 3 .. K keyframes of the final
@@ -58,7 +61,7 @@
 
 static int usage(const char* argv0)
 {
-	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--ate] [--rpe]]\n", argv0);
+	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--maintain-map] [--ate] [--rpe]]\n", argv0);
 	return 2;
 }
 
@@ -70,7 +73,7 @@ int main(int argc, char** argv)
 	bool rectify = false, rectifyFrames = false;
 	bool trackError = false;
 	double trackErrorThreshold = 5.0;
-	bool odometry = false, bundleAdjust = false, refine = false, refineTwoView = false, ate = false, rpe = false;
+	bool odometry = false, bundleAdjust = false, refine = false, refineTwoView = false, maintainMap = false, ate = false, rpe = false;
 	for (int i = 1; i < argc; ++i)
 	{
 		const std::string a = argv[i];
@@ -110,6 +113,10 @@ int main(int argc, char** argv)
 		{
 			refineTwoView = true;
 		}
+		else if (a == "--maintain-map")
+		{
+			maintainMap = true;
+		}
 		else if (a == "--ate")
 		{
 			ate = true;
@@ -146,7 +153,7 @@ int main(int argc, char** argv)
 			return usage(argv[0]);
 		}
 	}
-	if (dataset.empty() || out.empty() || ((bundleAdjust || refine || refineTwoView) && !odometry))
+	if (dataset.empty() || out.empty() || ((bundleAdjust || refine || refineTwoView || maintainMap) && !odometry))
 	{
 		return usage(argv[0]);
 	}
@@ -203,6 +210,12 @@ int main(int argc, char** argv)
 				hook = [&](const tracker::Patches& patches, const common::timestamp_t& t) {
 					visual_odometry::Keyframe keyframe(patches, t);
 					frontEnd->newKeyframeCandidate(keyframe);
+					if (maintainMap && frontEnd->getActiveFrames().count(static_cast<size_t>(t.count())) != 0)
+					{
+						const visual_odometry::MapMaintenanceSummary& m = frontEnd->lastMapMaintenance();
+						std::printf("map: %lld %zu %zu %zu %zu %zu %zu %zu\n", static_cast<long long>(t.count()), m.candidates, m.audited, m.kept,
+									m.retriangulated, m.added, m.culled, frontEnd->getMapLandmarks().landmarks.size());
+					}
 				};
 			}
 			tools::Evaluator evaluator(p, hook);
@@ -239,6 +252,10 @@ int main(int argc, char** argv)
 				if (refineTwoView)
 				{
 					frontEnd->twoView().useDeviceRefinement();
+				}
+				if (maintainMap)
+				{
+					frontEnd->useDeviceMapMaintenance(visual_odometry::MapMaintenanceParams());
 				}
 			}
 			tools::Replayer replayer(recording);

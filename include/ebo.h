@@ -1461,6 +1461,108 @@ int ebo_bundle_adjust_device(ebo_ctx* ctx, int n_problems, const int* frame_offs
 							 double huber, int fix_points, const ebo_solver_opts* opts, ebo_summary* summaries,
 							 double* d_trace_or_null);
 
+/* ---- landmark maintenance: N-view triangulation and the audit of landmarks -------------------------------
+ * The reference triangulates a landmark once, from the first two keyframes that observe it
+ * (VisualOdometryFrontEnd::addNewLandmarks, visual_odometry.cpp:353), and never removes one (its TODOs at :169 and
+ * :407).  These entries take a landmark's WHOLE observation list, for every landmark of a call at once.
+ * tests/landmark_ref.py restates every rule in numpy.  The conventions are those of "absolute pose": float64, one
+ * rounding per operation in exactly the association written here, no contraction, only + - * / sqrt and comparisons;
+ * a comparison with a NaN is false.  dot, cross, cof, det, jacobi(M, sweeps), mix / hash and the score A1 are the ones
+ * stated there.
+ * A pose is camera-to-world [R | t], double [3][4].  Observation o of a landmark is (pose index k_o, bearing vector
+ * f_o in that camera); landmark l owns observations obs_offsets[l] .. obs_offsets[l+1]-1 of obs_pose and obs_f, m
+ * their number; o below is the index WITHIN the landmark.
+ *
+ * L1. World rays.  d_o[i] = dot(R[i][:], f_o);  c_o = t of the pose;  c_ref = the centre of the landmark's
+ *     observation 0 (used or not);  e_o = c_o - c_ref.  Bearing vectors are taken as they come, not renormalised.
+ * L2. Least-squares point over a set U of observations.  Per observation: dd = dot(d, d);  A_ii = dd - d_i * d_i;
+ *     A_ij = -(d_i * d_j) for i != j;  a_i = dot(A[i][:], e).  Each of the nine sums (M00 M01 M02 M11 M12 M22 of the
+ *     symmetric M = sum of A, and b = sum of a) is taken as SIXTEEN partials: partial j = +0, then plus the term of every
+ *     o in U with o = j (mod 16) in ascending o; then for s = 8, 4, 2, 1: partial[i] = partial[i] + partial[i + s] for
+ *     i < s; the sum is partial[0].  C = cof(M);  D = det(M).  NO POINT unless D > 0.
+ *       x_i = dot((C[0][i], C[1][i], C[2][i]), b) / D;   X = c_ref + x.
+ * L3. Parallax of a set U.  (lambda, V) = jacobi(M, 8);  lo = lambda_0, replaced by lambda_1 and then by lambda_2 where
+ *     that is strictly smaller;  parallax = (2 * lo) / |U|.  For two unit rays at the angle theta this is
+ *     1 - cos(theta); for more it is twice the mean squared sine of their angles to the principal direction.
+ * L4. Hypotheses.  n_pairs = m (m - 1) / 2.  With n_pairs <= max_hypotheses there are n_pairs of them, hypothesis h
+ *     the h-th pair (a, b), a < b, in lexicographic order.  Otherwise there are max_hypotheses, (a, b) = the two
+ *     distinct indices of rule 3's Fisher-Yates shuffle with TWO draws, hash(seed, 0, h, d): the `pair` slot is the
+ *     constant 0, so a landmark's answer depends on its own observations and the seed, not on its place in the call.
+ *     Gate:  g = dot(d_a, d_b);  n2 = dot(d_a, d_a) * dot(d_b, d_b);  valid only when n2 > 0 and
+ *     1 - g / sqrt(n2) >= min_parallax.  X_h = L2 over {a, b}; invalid when there is no point.
+ *     count[h] = the number of the landmark's observations (all m, a and b among them) with A1(pose_o, f_o, X_h) <
+ *     threshold.  The winner is the FIRST valid h with the largest count, and only when that count is >= 2.
+ * L5. Final point.  U = the winner's inliers;  X = L2 over U;  parallax = L3 over U.  Then one re-selection without
+ *     another solve (as selectWithinDistance after the reference's refinements, visual_odometry.cpp:270):
+ *     score_o = A1(pose_o, f_o, X), inlier_o = score_o < threshold, n_inliers their number, score_max the largest
+ *     finite score over all m observations (0 when none is finite).  With threshold in (0, 1) an inlier lies in front
+ *     of its camera along its ray: there is no separate cheirality test.
+ * L6. Status, the first that applies:
+ *       2  an entry of one of the landmark's poses or bearing vectors is not finite (for the audit also an entry of
+ *          its point), or a pose index is out of range in a _device call: a scan before anything else
+ *       1  m < 2
+ *       3  no valid hypothesis with count >= 2
+ *       4  L5's solve has no point, or parallax >= min_parallax is false (parallax is computed either way)
+ *       5  n_inliers < min_inliers
+ *       0  otherwise.
+ *     With a status other than 0 the point is zeros.  parallax, score_max and n_inliers hold what had been computed
+ *     when the status was decided and zeros before that: all zero for 2, 1 and 3; parallax alone for 4; all three for 5.
+ *     winner is -1 unless L4 found one; hypotheses is the number L4 formed (0 for 2 and 1).  Per-observation scores
+ *     and flags are those of L5's re-selection where it ran (status 0 and 5) and zeros elsewhere.
+ * L7. Audit.  X is given.  L6's scan; status 1 when m < 1; then L5's re-selection under X; then M of L2 over those
+ *     inliers for L3's parallax (b and the solve are skipped; parallax = 0 with no inlier).  Status 4 when
+ *     parallax >= min_parallax is false, else 5 when n_inliers < min_inliers, else 0.  winner = -1, hypotheses = 0;
+ *     result.point repeats X with status 0; the points array itself is never written.  parallax, score_max, n_inliers
+ *     and the per-observation scores and flags are the selection's for every status but 2 and 1, where they are zeros.
+ *
+ * ebo_triangulate_tracks: L1-L6 for every landmark.  ebo_landmark_scores: L7 with points double [n_landmarks][3].
+ *   scores is double [obs_offsets[n_landmarks]], inlier_flags uint8 of the same length; either may be NULL.
+ *   Limits: 512 observations per landmark, 2^20 landmarks per call, max_hypotheses 1 .. 4096, min_inliers >= 2.
+ *   EBO_ERR_ARG beyond them, for a threshold outside (0, 1), a negative or NaN min_parallax, offsets that decrease or
+ *   do not start at 0, a pose index out of range, a needed pointer NULL.  EBO_ERR_STATE while a graph is being
+ *   recorded.  A landmark's result depends neither on the other landmarks of the call nor on the run.  Synchronous.
+ * The _device forms take device pointers for poses, obs_pose, obs_f, points, results, scores and flags (obs_offsets
+ *   and params stay on the host) and are asynchronous on the context's stream; they cannot look at the pose indices:
+ *   a landmark with one out of range gets status 2.
+ * ebo_two_view_timing brackets the host forms: slot [0] the kernel, [4] the whole call, the others 0. */
+typedef struct ebo_landmark_params
+{
+	double threshold;     /* A1 score below which an observation is an inlier; in (0, 1) */
+	double min_parallax;  /* L3 / L4's gate; >= 0 */
+	int min_inliers;      /* >= 2 */
+	int max_hypotheses;   /* 1 .. 4096 */
+	uint64_t seed;        /* L4's sampling */
+} ebo_landmark_params;
+typedef struct ebo_landmark_result
+{
+	double point[3];
+	double parallax;
+	double score_max;
+	int status;      /* L6 */
+	int n_obs;       /* m */
+	int n_inliers;
+	int winner;      /* L4's h, or -1 */
+	int hypotheses;  /* the number L4 formed */
+	int reserved;    /* 0 */
+} ebo_landmark_result;
+/* threshold (double)(float)(1 - cos(atan2(2, 200))), localizeCamera's at its default reprojection error;
+ * min_parallax 1 - cos(1 degree), a policy default in the range ORB-SLAM and COLMAP use, not a measured number;
+ * min_inliers 2; max_hypotheses 300 (every landmark of up to 25 observations is exhaustive); seed 0. */
+void ebo_default_landmark_params(ebo_landmark_params* params);
+int ebo_triangulate_tracks(ebo_ctx* ctx, int n_poses, const double* poses, int n_landmarks, const int* obs_offsets,
+						   const int* obs_pose, const double* obs_f, const ebo_landmark_params* params,
+						   ebo_landmark_result* results, double* scores_or_null, uint8_t* inlier_flags_or_null);
+int ebo_triangulate_tracks_device(ebo_ctx* ctx, int n_poses, const double* d_poses, int n_landmarks, const int* obs_offsets,
+								  const int* d_obs_pose, const double* d_obs_f, const ebo_landmark_params* params,
+								  ebo_landmark_result* d_results, double* d_scores_or_null, uint8_t* d_inlier_flags_or_null);
+int ebo_landmark_scores(ebo_ctx* ctx, int n_poses, const double* poses, int n_landmarks, const int* obs_offsets,
+						const int* obs_pose, const double* obs_f, const double* points, const ebo_landmark_params* params,
+						ebo_landmark_result* results, double* scores_or_null, uint8_t* inlier_flags_or_null);
+int ebo_landmark_scores_device(ebo_ctx* ctx, int n_poses, const double* d_poses, int n_landmarks, const int* obs_offsets,
+							   const int* d_obs_pose, const double* d_obs_f, const double* d_points,
+							   const ebo_landmark_params* params, ebo_landmark_result* d_results, double* d_scores_or_null,
+							   uint8_t* d_inlier_flags_or_null);
+
 /* Device-side timing of everything enqueued between begin and end on the
  * context's stream (hipEvent based). */
 int ebo_timer_begin(ebo_ctx* ctx);
