@@ -28,37 +28,26 @@
 //     weights (value_tap): the exact product is rounded ONCE onto the 2^(k-52) grid.  Where the
 //     weights can be tiny (sigma < 1) it is  fma(wx, wy, bias): bias = 1.5 * 2^k has a zero low
 //     dword, so removing it is a 32-bit subtract on the high dword (fix_tap);
-//   * exp on [-1, 1] without range reduction (degree-12 Taylor on x/4, two squarings)
-//     when sigma >= 1 (the reference's sigma is 1).
+//   * exp on [-1, 1] without range reduction (Taylor on x/4, two squarings; exp(a) and exp(-a) share
+//     their even and odd parts: exp_taps.h) when sigma >= 1 (the reference's sigma is 1).
 
-// exp(x) for |x| <= 1, relative error ~4e-16.
-__device__ __forceinline__ double exp_small(double x)
-{
-	const double t = x * 0.25;
-	double p = 1.0 / 479001600.0;             // 1/12!
-	p = fma(p, t, 1.0 / 39916800.0);          // 1/11!
-	p = fma(p, t, 1.0 / 3628800.0);
-	p = fma(p, t, 1.0 / 362880.0);
-	p = fma(p, t, 1.0 / 40320.0);
-	p = fma(p, t, 1.0 / 5040.0);
-	p = fma(p, t, 1.0 / 720.0);
-	p = fma(p, t, 1.0 / 120.0);
-	p = fma(p, t, 1.0 / 24.0);
-	p = fma(p, t, 1.0 / 6.0);
-	p = fma(p, t, 0.5);
-	p = fma(p, t, 1.0);
-	p = fma(p, t, 1.0);
-	p = p * p;
-	return p * p;
-}
-
+// SMALL (sigma >= 1): hs f^2 lies in [-0.5, 0] and |a| <= 1 (|f| < 1), the ranges of exp_taps.h's polynomials; exp(a)
+// and exp(-a) come as a pair from one cosh / sinh evaluation.
 template <bool SMALL>
 __device__ __forceinline__ void axis_taps3(double f, double pre, const EvalConsts& c, double (&w)[7])
 {
 	const double a = f * c.inv_sigsq;
-	const double e0 = pre * (SMALL ? exp_small(c.hs * (f * f)) : exp(c.hs * (f * f)));
-	const double p = SMALL ? exp_small(a) : exp(a);
-	const double q = SMALL ? exp_small(-a) : exp(-a);
+	const double e0 = pre * (SMALL ? exp_gauss(c.hs * (f * f)) : exp(c.hs * (f * f)));
+	double p, q;
+	if (SMALL)
+	{
+		exp_pair(a, p, q);
+	}
+	else
+	{
+		p = exp(a);
+		q = exp(-a);
+	}
 	const double p2 = p * p, q2 = q * q;
 	const double e1 = c.ck1 * e0, e2 = c.ck2 * e0, e3 = c.ck3 * e0;
 	w[3] = e0;
@@ -108,7 +97,15 @@ struct EvalReuse
 	double s0, s1, s2;   // sum I, sum I^2, number of non-zero pixels
 };
 
-template <bool SMALL>
+// D1S: which pass forms the image-free Jacobian sums D1k (S[3], S[4]).  They need the weights only, so either pass
+// can.  k_eval3 forms them in the scatter (D1S = true; only where wantJac is set): that takes the four sums and their
+// two accumulators, 12 registers live across the gather's rows, out of the pass that needs registers for its table of
+// derivative weights (measured, DESIGN.md 4.1 item 16: the move alone costs 1 %, the table without the move 1.5 %,
+// both together nothing, and they leave the registers the cheaper exponentials need).  k_solve_independent keeps them
+// in the gather (D1S = false): an EvalReuse hit runs no scatter.  Same operations on the same operands in the same order
+// either way (the scatter's weights carry exact power-of-two prefactors in the subnormal form, taken off each sum
+// by one exact multiply BEFORE the two products, which would underflow scaled), so S[3] and S[4] have the same bits.
+template <bool SMALL, bool D1S>
 __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, const Unit& u, double m0,
 											double m1, bool wantJac, int tile, int tiles,
 											int capDoubles, const EvalConsts& c, double* lds,
@@ -165,7 +162,8 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 	};
 
 	// (uniform: every thread reads the same record, written before the barriers that separate two evaluations)
-	const bool reuse = ru && wantJac && ru->valid == 1.0 && __double_as_longlong(ru->m0) == __double_as_longlong(m0) &&
+	// !D1S: a hit runs no scatter, so only an evaluation whose gather forms D1 may take it
+	const bool reuse = !D1S && ru && wantJac && ru->valid == 1.0 && __double_as_longlong(ru->m0) == __double_as_longlong(m0) &&
 					   __double_as_longlong(ru->m1) == __double_as_longlong(m1);
 	int xmin = 0x7fffffff, xmax = -0x7fffffff, ymin = 0x7fffffff, ymax = -0x7fffffff;
 	if (!reuse)
@@ -243,6 +241,10 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 #else
 	constexpr bool subTaps = SMALL;
 #endif
+	// D1S: what takes the scatter's prefactors off a sum of weights again, norm 2^-511 -> norm and 2^-(511 + k) -> 1
+	// (powers of two: the quotient is exact)
+	const double unX = subTaps ? 0x1p511 : 1.0;
+	const double unY = subTaps ? 1.0 / preY : 1.0;
 
 	for (int sy0 = ty0; sy0 < ty1; sy0 += maxRows)
 	{
@@ -262,6 +264,7 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 		// ---- scatter the value taps ----
 		if (!reuse)
 		{
+		double h3 = 0.0, h4 = 0.0;  // D1S: this sub-band's D1 sums
 		for_each_event([&](uint64_t rec) {
 			int pxc, pyc;
 			double fx, fy, tau;
@@ -278,10 +281,61 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 			double wx[7], wy[7];
 			axis_taps3<SMALL>(fx, subTaps ? preX : c.norm, c, wx);
 			axis_taps3<SMALL>(fy, subTaps ? preY : 1.0, c, wy);
+			const bool interior = rowLo >= 0 && rowLo + 6 < srows && colLo >= 0 && colLo + 6 < bw;
+			if (D1S && wantJac)
+			{
+				// the sums of the weights and of the derivative weights over the taps this sub-band holds: the statements
+				// of the gather's two paths (below, !D1S), on weights that may carry the prefactors
+				const double g = tau * c.inv_sigsq;
+				const double gfx = g * fx, gfy = g * fy;
+				double sumWy = 0.0, sumAy = 0.0, sumW = 0.0, sumA = 0.0;
+				if (interior)
+				{
+#pragma unroll
+					for (int i = 0; i < 7; ++i)
+					{
+						sumW += wx[i];
+						sumA = fma(wx[i], fma(g, static_cast<double>(i - 3), -gfx), sumA);
+					}
+#pragma unroll
+					for (int j = 0; j < 7; ++j)
+					{
+						const double ay = wy[j] * fma(g, static_cast<double>(j - 3), -gfy);
+						sumWy += wy[j];
+						sumAy += ay;
+					}
+				}
+				else
+				{
+#pragma unroll
+					for (int i = 0; i < 7; ++i)
+					{
+						const int col = colLo + i;
+						const double w = (col >= 0 && col < bw) ? wx[i] : 0.0;
+						const double a = w * fma(g, static_cast<double>(i - 3), -gfx);
+						sumW += w;
+						sumA += a;
+					}
+#pragma unroll
+					for (int j = 0; j < 7; ++j)
+					{
+						const int row = rowLo + j;
+						if (row < 0 || row >= srows)
+						{
+							continue;
+						}
+						const double ay = wy[j] * fma(g, static_cast<double>(j - 3), -gfy);
+						sumWy += wy[j];
+						sumAy += ay;
+					}
+				}
+				h3 = fma(sumA * unX, sumWy * unY, h3);
+				h4 = fma(sumW * unX, sumAy * unY, h4);
+			}
 			// (the form is a compile-time constant of the tap loops; only the A/B build holds both)
 			auto taps = [&](auto form) {
 				constexpr bool SUB = decltype(form)::value;
-				if (rowLo >= 0 && rowLo + 6 < srows && colLo >= 0 && colLo + 6 < bw)
+				if (interior)
 				{
 					unsigned long long* p = imgq + __mul24(rowLo, cols) + colLo;  // (both far below 2^24: not the quarter-rate v_mul_lo_u32)
 #pragma unroll
@@ -330,6 +384,16 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 			taps(std::integral_constant<bool, subTaps>{});
 #endif
 		});
+		if (D1S && wantJac)
+		{
+			h3 = wave_sum(h3);
+			h4 = wave_sum(h4);
+			if (lane == kWaveResultLane)
+			{
+				slot[3] += h3;
+				slot[4] += h4;
+			}
+		}
 		__syncthreads();
 		EDGE_TICK(18);
 
@@ -367,7 +431,8 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 		EDGE_TICK(19);
 
 		// ---- gather the derivative sums ----
-		double g3 = 0.0, g4 = 0.0, g5 = 0.0, g6 = 0.0;
+		[[maybe_unused]] double g3 = 0.0, g4 = 0.0;
+		double g5 = 0.0, g6 = 0.0;
 		for_each_event([&](uint64_t rec) {
 			int pxc, pyc;
 			double fx, fy, tau;
@@ -386,22 +451,29 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 			axis_taps3<SMALL>(fy, 1.0, c, wy);
 			const double g = tau * c.inv_sigsq;
 			const double gfx = g * fx, gfy = g * fy;
-			double d2a = 0.0, d2b = 0.0, sumWy = 0.0, sumAy = 0.0, sumW = 0.0, sumA = 0.0;
+			double d2a = 0.0, d2b = 0.0;
+			[[maybe_unused]] double sumWy = 0.0, sumAy = 0.0, sumW = 0.0, sumA = 0.0;  // !D1S: the D1 sums are formed here
 			if (rowLo >= 0 && rowLo + 6 < srows && colLo >= 0 && colLo + 6 < bw)
 			{
+				// the seven x-derivative weights, as the clipped path below has them: 14 registers, which the kernel has
+				// since the D1 sums and their four accumulators left this pass (D1S); two fma per tap
+				double ax[7];
 #pragma unroll
 				for (int i = 0; i < 7; ++i)
 				{
-					sumW += wx[i];
-					sumA = fma(wx[i], fma(g, static_cast<double>(i - 3), -gfx), sumA);
+					const double ci = fma(g, static_cast<double>(i - 3), -gfx);
+					ax[i] = wx[i] * ci;
+					if constexpr (!D1S)
+					{
+						sumW += wx[i];
+						sumA = fma(wx[i], ci, sumA);
+					}
 				}
 				const double* rowp = img + __mul24(rowLo, cols) + colLo;
 #pragma unroll
 				for (int j = 0; j < 7; ++j)
 				{
-					// rb = sum_i wx_i I_i, rc = sum_i (i - 3) wx_i I_i; the x-derivative row sum is g rc - g fx rb
-					// (no table of the seven derivative weights: 14 registers, which is what keeps the kernel
-					// at 128 = four waves per SIMD)
+					// rb = sum_i wx_i I_i, ra = sum_i ax_i I_i
 					double v[7];
 #pragma unroll
 					for (int i = 0; i < 7; ++i)
@@ -409,21 +481,19 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 						v[i] = lds_ld(rowp + i);  // the row's seven reads back to back, then the arithmetic (measured: within
 												  // 0.5 % of reads interleaved with the arithmetic -- the pass is throughput-bound)
 					}
-					double rb = wx[3] * v[3], rc = 0.0;
+					double rb = wx[0] * v[0], ra = ax[0] * v[0];
 #pragma unroll
-					for (int i = 0; i < 7; ++i)
+					for (int i = 1; i < 7; ++i)
 					{
-						if (i != 3)
-						{
-							const double t = wx[i] * v[i];
-							rb += t;
-							rc = fma(static_cast<double>(i - 3), t, rc);
-						}
+						rb = fma(wx[i], v[i], rb);
+						ra = fma(ax[i], v[i], ra);
 					}
-					const double ra = fma(g, rc, -(gfx * rb));
 					const double ay = wy[j] * fma(g, static_cast<double>(j - 3), -gfy);
-					sumWy += wy[j];
-					sumAy += ay;
+					if constexpr (!D1S)
+					{
+						sumWy += wy[j];
+						sumAy += ay;
+					}
 					d2a = fma(wy[j], ra, d2a);
 					d2b = fma(ay, rb, d2b);
 					rowp += cols;
@@ -441,8 +511,11 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 					wx[i] = ok ? wx[i] : 0.0;
 					ax[i] = wx[i] * fma(g, static_cast<double>(i - 3), -gfx);
 					ci[i] = min(max(col, 0), bw - 1);
-					sumW += wx[i];
-					sumA += ax[i];
+					if constexpr (!D1S)
+					{
+						sumW += wx[i];
+						sumA += ax[i];
+					}
 				}
 #pragma unroll
 				for (int j = 0; j < 7; ++j)
@@ -453,8 +526,11 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 						continue;
 					}
 					const double ay = wy[j] * fma(g, static_cast<double>(j - 3), -gfy);
-					sumWy += wy[j];
-					sumAy += ay;
+					if constexpr (!D1S)
+					{
+						sumWy += wy[j];
+						sumAy += ay;
+					}
 					const double* rowp = img + row * cols;
 					double ra = 0.0, rb = 0.0;
 #pragma unroll
@@ -468,19 +544,28 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 					d2b = fma(ay, rb, d2b);
 				}
 			}
-			g3 = fma(sumA, sumWy, g3);
-			g4 = fma(sumW, sumAy, g4);
+			if constexpr (!D1S)
+			{
+				g3 = fma(sumA, sumWy, g3);
+				g4 = fma(sumW, sumAy, g4);
+			}
 			g5 += d2a;
 			g6 += d2b;
 		});
-		g3 = wave_sum(g3);
-		g4 = wave_sum(g4);
+		if constexpr (!D1S)
+		{
+			g3 = wave_sum(g3);
+			g4 = wave_sum(g4);
+		}
 		g5 = wave_sum(g5);
 		g6 = wave_sum(g6);
 		if (lane == kWaveResultLane)
 		{
-			slot[3] += g3;
-			slot[4] += g4;
+			if constexpr (!D1S)
+			{
+				slot[3] += g3;
+				slot[4] += g4;
+			}
 			slot[5] += g5;
 			slot[6] += g6;
 		}
@@ -529,8 +614,8 @@ template <bool SMALL>
 // LDS, which idles while a workgroup is between its tap passes, so a fifth 192-lane workgroup per CU is worth
 // 4-5 % -- but only without spills: the first attempt (round 1) spilled inside the tap loops and was 8x slower.
 // What fits the kernel into 128 registers: the seven sums live in per-wave LDS slots instead of registers
-// across the passes, the box and everything derived from it are scalars (readfirstlane), and the gather
-// forms the x-derivative row sum from two accumulators instead of a table of seven derivative weights.
+// across the passes, the box and everything derived from it are scalars (readfirstlane), and the D1 sums are
+// formed in the scatter pass, which leaves the gather room for its table of seven x-derivative weights (D1S).
 // The sigma < 1 instantiation (library exp, the one-step floor of fix_tap) is
 // given three waves per SIMD: at four it spills a register.  It is not the reference's sigma.
 __global__ void __launch_bounds__(512, SMALL ? 4 : 3) k_eval3(const uint64_t* __restrict__ events,
@@ -592,7 +677,7 @@ __global__ void __launch_bounds__(512, SMALL ? 4 : 3) k_eval3(const uint64_t* __
 	double m1 = flows[2 * u.flow_idx + 1];
 	fd_offset(set, fdStep, m0, m1);
 	double S[7];
-	eval_unit3<SMALL>(events + u.ev_off, u, m0, m1, wantJac != 0, tile, tiles, capDoubles, c, lds, S);
+	eval_unit3<SMALL, true>(events + u.ev_off, u, m0, m1, wantJac != 0, tile, tiles, capDoubles, c, lds, S);
 	if (threadIdx.x == 0)
 	{
 		if (fused)

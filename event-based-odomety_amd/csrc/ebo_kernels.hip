@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "ebo_internal.h"
+#include "exp_taps.h"
 
 namespace ebo
 {
@@ -584,7 +585,7 @@ __device__ __forceinline__ void eval_unit(const uint64_t* __restrict__ ev, const
 										   double& j0, double& j1, EvalReuse* ru)
 {
 	double S[7];
-	eval_unit3<SMALL>(ev, u, m0, m1, wantJac, 0, 1, capDoubles, c, lds, S, ru);
+	eval_unit3<SMALL, false>(ev, u, m0, m1, wantJac, 0, 1, capDoubles, c, lds, S, ru);  // (the gather forms D1: ebo_eval3.inc)
 	j0 = 0.0;
 	j1 = 0.0;
 	variance_from_sums(S, wantJac, m0, m1, c.max_res, r, j0, j1);
@@ -861,7 +862,7 @@ struct LmUnit
 	}
 };
 
-// SMALL: exp_small (sigma >= 1) instead of the library exp (ebo_eval3.inc)
+// SMALL: exp_taps.h's polynomials (sigma >= 1) instead of the library exp (ebo_eval3.inc)
 template <bool SMALL>
 __global__ void __launch_bounds__(512) k_solve_independent(const uint64_t* __restrict__ events,
 									const Unit* __restrict__ units, int capDoubles,

@@ -9,7 +9,7 @@
 // The powers of two ride in the prefactor that an axis' weights are multiplied by anyway; scaling a normal number by a
 // power of two is exact as long as the result is normal, so every weight keeps its mantissa.  That is the condition
 // the subnormal form rests on: the smallest scaled weights, norm e^-8 2^-511 and e^-8 2^-(511 + k) (the sigma >= 1 path:
-// outer taps at most e^-4.5 of the centre, the exp_small factors within e^+-1), have to stay far above 2^-1022.
+// outer taps at most e^-4.5 of the centre, the factors of exp_taps.h within e^+-1), have to stay far above 2^-1022.
 // With |log2 norm| and |k| below kFixGuardExp = 400 they are above 2^-923; every sigma ebo_create admits gives
 // norm in [1.6e-7, 2.6] and k in [0, 3 + 32].  A context outside the rule evaluates with the biased form.
 #pragma once
