@@ -243,7 +243,10 @@ int ebo_contrast_image(ebo_ctx* ctx, int window, int patch, const double* flow,
 					   int channels, double* image);
 
 /* Solve for the flows of every loaded window starting from 0 (R2 :316-414).
- * flows_out host [Wn][P][2]; summary [Wn] (may be NULL). */
+ * flows_out host [Wn][P][2]; summary [Wn] (may be NULL).  EBO_SOLVE_INDEPENDENT folds a window's per-patch solves
+ * into its summary: max of iterations and termination, sums of the evaluation counts.  initial_cost and final_cost
+ * are reported (summed over the patches) only by its lock-step host path (EBO_GRAD_CENTRAL); the device-resident
+ * path, which ebo_solve_device's d_stats describes per patch, leaves both 0. */
 int ebo_solve(ebo_ctx* ctx, const ebo_solver_opts* o, double* flows_out, ebo_summary* summary);
 /* EBO_SOLVE_INDEPENDENT only: the whole solve in one launch, result left on the
  * device in d_flows_out [Wn][P][2]; asynchronous. d_stats (may be NULL) [Wn][P][4]
