@@ -1044,7 +1044,9 @@ class Context:
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4)
         flow_dirs = np.ascontiguousarray(flow_dirs, dtype=np.float64).reshape(-1)
         n = len(rects)
-        shapes = [(int(np.rint(r[3])), int(np.rint(r[2]))) for r in rects]
+        # a size the entry refuses (NaN, outside 0..32767) takes no room here: the call reports it
+        dim = lambda v: int(np.rint(v)) if np.isfinite(v) and 0 <= np.rint(v) <= 32767 else 0
+        shapes = [(dim(r[3]), dim(r[2])) for r in rects]
         sizes = [h * w for h, w in shapes]
         noff = np.zeros(max(n, 1), dtype=np.uint64)
         noff[1:n] = np.cumsum(sizes[:-1])

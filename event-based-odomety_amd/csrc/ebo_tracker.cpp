@@ -344,6 +344,14 @@ int ebo_optimizer_set_grad(ebo_ctx* c, const double* grad_x, const double* grad_
 	return rc;
 }
 
+// What the two nearest-neighbour map kernels can index: the cv::Rect2d -> cv::Rect conversion (round half to even) of a
+// finite corner, and a width and height that round into 0..32767.  Also false for NaN.
+static bool map_rect_ok(const double* r)
+{
+	const double w = std::nearbyint(r[2]), h = std::nearbyint(r[3]);
+	return std::isfinite(r[0]) && std::isfinite(r[1]) && w >= 0 && h >= 0 && w <= 32767 && h <= 32767;
+}
+
 // FeatureDetector::updateNumOfEvents' estimate (feature_detector.cpp:689-707) for n patches, one launch.
 int ebo_estimate_num_events(ebo_ctx* c, int n, const double* rects, const double* poses, const double* flow_dirs,
 							uint64_t* out)
@@ -367,6 +375,13 @@ int ebo_estimate_num_events(ebo_ctx* c, int n, const double* rects, const double
 	if (n == 0)
 	{
 		return EBO_OK;
+	}
+	for (int i = 0; i < n; ++i)
+	{
+		if (!map_rect_ok(rects + 4 * static_cast<size_t>(i)))
+		{
+			return c->fail(EBO_ERR_RANGE, "patch rect out of range");
+		}
 	}
 	(void)hipSetDevice(c->prm.device);
 	const size_t nn = static_cast<size_t>(n);
@@ -439,9 +454,9 @@ int ebo_patch_warp_image(ebo_ctx* c, int n, const double* rects, const double* p
 		const double* r = rects + 4 * i;
 		const bool border = r[0] < 0 || r[1] < 0 || r[0] + r[2] >= c->prm.image_w || r[1] + r[3] >= c->prm.image_h;
 		const double w = std::nearbyint(r[2]), h = std::nearbyint(r[3]);
-		if (!(w >= 0 && h >= 0 && w <= 32767 && h <= 32767))  // also NaN
+		if (!map_rect_ok(r))
 		{
-			return c->fail(EBO_ERR_RANGE, "patch rect size out of range");
+			return c->fail(EBO_ERR_RANGE, "patch rect out of range");
 		}
 		skip[i] = border ? 1 : 0;
 		updated[i] = border ? 0 : 1;
