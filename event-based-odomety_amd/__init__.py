@@ -129,6 +129,40 @@ class LandmarkResult(C.Structure):
                 ("n_obs", C.c_int32), ("n_inliers", C.c_int32), ("winner", C.c_int32), ("hypotheses", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RotationParams(C.Structure):
+    """ebo_rotation_params: sigma_blur of the rotational contrast maximisation (rule V5)."""
+    _fields_ = [("sigma_blur", C.c_double), ("reserved", C.c_double)]
+
+    def __init__(self, sigma_blur=1.0):
+        super().__init__(float(sigma_blur), 0.0)
+
+
+class RotSolverOpts(C.Structure):
+    """ebo_rot_solver_opts (rules N1-N5)."""
+    _fields_ = [("first_rate", C.c_double), ("c1", C.c_double), ("step_tol", C.c_double), ("max_backtracks", C.c_int32),
+                ("max_iterations", C.c_int32)]
+
+
+class RotSummary(C.Structure):
+    """ebo_rot_summary: status (ROT_*), accepted steps, evaluations, r at omega0 and at the result."""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("evaluations", C.c_int32), ("reserved", C.c_int32),
+                ("r_initial", C.c_double), ("r_final", C.c_double)]
+
+
+ROT_RUNNING, ROT_CONVERGED_STEP, ROT_CONVERGED_GRADIENT, ROT_MAX_ITERATIONS, ROT_NO_PROGRESS, ROT_NONFINITE = -1, 0, 1, 2, 3, 4
+
+
+def rot_solver_opts(**kw):
+    """ebo_default_rot_solver_opts (0.5 rad/s, c1 1e-4, step_tol 1e-4, 20 backtracks, 100 iterations), with overrides."""
+    o = RotSolverOpts()
+    lib().ebo_default_rot_solver_opts(C.byref(o))
+    for key, val in kw.items():
+        if not hasattr(o, key):
+            raise AttributeError(key)
+        setattr(o, key, val)
+    return o
+
+
 class RpeResult(C.Structure):
     """ebo_rpe_result: one (segment, delta) unit's relative pose error, translation then rotation."""
     _fields_ = [("trans_rmse", C.c_double), ("trans_mean", C.c_double), ("trans_min", C.c_double), ("trans_max", C.c_double),
@@ -323,6 +357,20 @@ def lib():
         _lib.ebo_triangulate_tracks_device.argtypes = _lmt
         _lib.ebo_landmark_scores.argtypes = _lmt + [C.c_void_p]
         _lib.ebo_landmark_scores_device.argtypes = _lmt + [C.c_void_p]
+        _lib.ebo_default_rotation_params.argtypes = [C.c_void_p]
+        _lib.ebo_default_rotation_params.restype = None
+        _lib.ebo_default_rot_solver_opts.argtypes = [C.c_void_p]
+        _lib.ebo_default_rot_solver_opts.restype = None
+        _lib.ebo_eval_rotation.argtypes = [C.c_void_p] * 6
+        _lib.ebo_eval_rotation_device.argtypes = [C.c_void_p] * 6
+        _lib.ebo_rotation_image.argtypes = [C.c_void_p] * 5
+        _lib.ebo_solve_rotation.argtypes = [C.c_void_p] * 7
+        _lib.ebo_rot_solver_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ebo_rot_solver_request.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ebo_rot_solver_supply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ebo_rot_solver_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ebo_rot_solver_destroy.argtypes = [C.c_void_p]
+        _lib.ebo_rot_solver_destroy.restype = None
         _te = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.ebo_track_errors.argtypes = _te
         _lib.ebo_track_errors_device.argtypes = _te
@@ -422,6 +470,56 @@ class HostSolver:
     def close(self):
         if self._h:
             lib().ebo_lm_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class RotationSolver:
+    """ebo_rot_solver_*: rules N1-N5 for n windows at once as a resumable state machine (request -> evaluate -> supply).
+    Host only: no device is touched."""
+
+    def __init__(self, n, opts=None, omega0=None):
+        self.n = int(n)
+        self._opts = opts if opts is not None else rot_solver_opts()
+        o0 = None if omega0 is None else np.ascontiguousarray(omega0, dtype=np.float64).reshape(self.n, 3)
+        h = C.c_void_p()
+        rc = lib().ebo_rot_solver_create(self.n, C.byref(self._opts), _dp(o0) if o0 is not None else None, C.byref(h))
+        if rc:
+            raise EboError(rc, "ebo_rot_solver_create")
+        self._h = h
+
+    def request(self):
+        """-> (windows still waiting, omegas [n][3], live bool [n])"""
+        om = np.zeros((self.n, 3))
+        live = np.zeros(self.n, dtype=np.uint8)
+        rc = lib().ebo_rot_solver_request(self._h, _dp(om), _vp(live))
+        if rc < 0:
+            raise EboError(rc, "ebo_rot_solver_request")
+        return rc, om, live.astype(bool)
+
+    def supply(self, r, g):
+        r = np.ascontiguousarray(r, dtype=np.float64).reshape(self.n)
+        g = np.ascontiguousarray(g, dtype=np.float64).reshape(self.n, 3)
+        rc = lib().ebo_rot_solver_supply(self._h, _dp(r), _dp(g))
+        if rc:
+            raise EboError(rc, "ebo_rot_solver_supply")
+
+    def result(self):
+        om = np.zeros((self.n, 3))
+        s = (RotSummary * self.n)()
+        rc = lib().ebo_rot_solver_result(self._h, _dp(om), s)
+        if rc:
+            raise EboError(rc, "ebo_rot_solver_result")
+        return om, list(s)
+
+    def close(self):
+        if self._h:
+            lib().ebo_rot_solver_destroy(self._h)
             self._h = None
 
     def __enter__(self):
@@ -1727,6 +1825,45 @@ class Context:
         raw = np.ascontiguousarray(raw, dtype=np.uint8).reshape(-1)
         n = raw.size // cls.LANDMARK_DTYPE.itemsize
         return cls._landmark_out(raw[:n * cls.LANDMARK_DTYPE.itemsize].tobytes(), n)
+
+    # -- angular velocity from events (rotational contrast maximisation, rules V1-V9 / N1-N5) ----------------
+    def _rot_args(self, cam, params):
+        return camera(cam), params if params is not None else RotationParams()
+
+    def eval_rotation(self, cam, omegas, params=None, want_grad=True):
+        """ebo_eval_rotation: omegas float64 [Wn][3] in rad/s -> (r [Wn], g [Wn][3] or None)."""
+        k, prm = self._rot_args(cam, params)
+        om = np.ascontiguousarray(omegas, dtype=np.float64).reshape(self.n_windows, 3)
+        r = np.zeros(self.n_windows)
+        g = np.zeros((self.n_windows, 3)) if want_grad else None
+        self._check(lib().ebo_eval_rotation(self._h, C.addressof(k), C.addressof(prm), _dp(om), _dp(r), _dp(g) if want_grad else None))
+        return r, g
+
+    def eval_rotation_device(self, cam, d_omegas, d_r, d_g=0, params=None):
+        """ebo_eval_rotation_device: device pointers as int; asynchronous on the context's stream."""
+        k, prm = self._rot_args(cam, params)
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        self._check(lib().ebo_eval_rotation_device(self._h, C.addressof(k), C.addressof(prm), p(d_omegas), p(d_r), p(d_g)))
+
+    def rotation_image(self, cam, omegas, votes=True, image=True):
+        """ebo_rotation_image -> (H int64 [Wn][h][w] or None, F float64 [Wn][h][w] or None)."""
+        k = camera(cam)
+        om = np.ascontiguousarray(omegas, dtype=np.float64).reshape(self.n_windows, 3)
+        shape = (self.n_windows, self.params.image_h, self.params.image_w)
+        Hq = np.zeros(shape, dtype=np.int64) if votes else None
+        F = np.zeros(shape) if image else None
+        self._check(lib().ebo_rotation_image(self._h, C.addressof(k), _dp(om), _vp(Hq) if votes else None, _dp(F) if image else None))
+        return Hq, F
+
+    def solve_rotation(self, cam, params=None, opts=None, omega0=None):
+        """ebo_solve_rotation from omega0 ([Wn][3], None: zeros) -> (omega [Wn][3], [RotSummary] * Wn)."""
+        k, prm = self._rot_args(cam, params)
+        o0 = None if omega0 is None else np.ascontiguousarray(omega0, dtype=np.float64).reshape(self.n_windows, 3)
+        out = np.zeros((self.n_windows, 3))
+        summ = (RotSummary * self.n_windows)()
+        self._check(lib().ebo_solve_rotation(self._h, C.addressof(k), C.addressof(prm), C.byref(opts) if opts is not None else None,
+                                             _dp(o0) if o0 is not None else None, _dp(out), summ))
+        return out, list(summ)
 
     # -- track evaluation (KLT reference tracks on the frames, track error and feature age) ------------------
     def reference_tracks(self, frames, frame_t_us, seed_frame, seed_xy, win=(21, 21), max_level=3, max_count=30, epsilon=0.01,

@@ -171,6 +171,9 @@ struct ebo_ctx
 	bool rect_set = false;
 	ebo_camera rect_cam = {}, rect_out = {};  // the (camera, rectified camera) pair of the call that set it
 
+	Dev<void> d_rot;  // ebo_rotation.cpp: a chunk's three images and folds (RotScratch)
+	Dev<double> d_rot_io;  // its host entries' omegas [Wn][3], r [Wn], g [Wn][3]
+
 	std::vector<Unit> units;       // [Wn][P+1], stray unit last in each window
 	std::vector<int64_t> unit_tref;
 	std::vector<int64_t> unit_tmin, unit_tmax;  // ebo_set_patches: earliest / latest event time per unit (ebo_count_image_shard)

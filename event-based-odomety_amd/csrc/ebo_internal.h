@@ -18,6 +18,7 @@
 #include "ebo_rpe.h"
 #include "ebo_trackerr.h"
 #include "ebo_landmark.h"
+#include "ebo_rotation.h"
 
 namespace ebo
 {
@@ -559,6 +560,31 @@ int launch_trajectory_rpe(int n_poses, const double* d_gt, const double* d_est, 
 int launch_landmarks(int solve, int lanes, int n_poses, const double* d_poses, int n_landmarks, const int* d_offsets,
 					 const int* d_obs_pose, const double* d_obs_f, const double* d_points, const ebo_landmark_params* params,
 					 ebo_landmark_result* d_results, double* d_scores, uint8_t* d_flags, void* stream);
+
+// rotational contrast maximisation (ebo_rotation.inc, ebo_rotation.cpp).  A launch covers one chunk of windows: chunk
+// slot s holds window win[s], passed BY VALUE as LiveWindows is; the images and folds are indexed by slot, omegas and
+// results by window (RotWindows, RotConsts: ebo_rotation.h).
+// the chunk's scratch: three images [slots][h][w] of 8 bytes a pixel and the folds
+struct RotScratch
+{
+	void* imgX;       // H, then the horizontal pass of B - mu
+	double* imgY;     // the horizontal pass of F, then C
+	double* imgZ;     // B
+	double* partB;    // [slots][blocks]
+	double* partV;    // [slots][blocks]
+	double* mu;       // [slots]
+	double* partG;    // [slots][P][3]
+};
+inline int rot_blocks(int w, int h)
+{
+	return (w * h + kRotBlock - 1) / kRotBlock;
+}
+// H of the chunk's windows into s.imgX (zeroed here); with d_F also F = H * 2^-30 into it ([slots][h][w])
+int launch_rot_votes(const uint64_t* d_events, const Unit* d_units, const RotWindows& L, const RotConsts& k, const double* d_omegas,
+					 const RotScratch& s, double* d_F, void* stream);
+// r (and g unless d_g is null) of the chunk's windows into d_r[win] / d_g[win][3]
+int launch_rot_eval(const uint64_t* d_events, const Unit* d_units, const RotWindows& L, const RotConsts& k, const double* d_omegas,
+					const RotScratch& s, double* d_r, double* d_g, void* stream);
 
 // track evaluation (ebo_trackerr.inc, ebo_trackerr.cpp): unit k * n_taus + j is track k, samples d_est_off[k] .. d_est_off[k + 1] - 1
 // of d_est_t / d_est_xy (n_est of them) and d_gt_off[k] .. d_gt_off[k + 1] - 1 of d_gt_t / d_gt_xy (n_gt), at threshold d_taus[j];

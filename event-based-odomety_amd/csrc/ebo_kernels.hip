@@ -1289,6 +1289,7 @@ __global__ void __launch_bounds__(64) k_route(const uint32_t* __restrict__ xy, u
 #include "ebo_rpe.inc"
 #include "ebo_trackerr.inc"
 #include "ebo_landmark.inc"
+#include "ebo_rotation.inc"
 #include "ebo_field.inc"
 #include "ebo_fieldtv.inc"
 #include "ebo_optimizer.inc"
@@ -2062,6 +2063,65 @@ int launch_landmarks(int solve, int lanes, int n_poses, const double* d_poses, i
 														d_results, d_scores, d_flags, stream)
 					   : launch_landmarks_as<false, 64>(n_poses, d_poses, n_landmarks, d_offsets, d_obs_pose, d_obs_f, d_points, prm,
 														d_results, d_scores, d_flags, stream);
+}
+
+// rotational contrast maximisation (ebo_rotation.inc): one chunk of windows per call
+int launch_rot_votes(const uint64_t* d_events, const Unit* d_units, const RotWindows& L, const RotConsts& k, const double* d_omegas,
+					 const RotScratch& s, double* d_F, void* stream)
+{
+	if (L.n <= 0)
+	{
+		return 0;
+	}
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	const size_t np = static_cast<size_t>(k.w) * k.h;
+	if (hipMemsetAsync(s.imgX, 0, static_cast<size_t>(L.n) * np * sizeof(unsigned long long), st) != hipSuccess)
+	{
+		return -2;
+	}
+	hipLaunchKernelGGL(k_rot_vote, dim3(k.P, L.n), dim3(kRotBlock), 0, st, d_events, d_units, L, k, d_omegas,
+					   static_cast<unsigned long long*>(s.imgX));
+	if (d_F)
+	{
+		hipLaunchKernelGGL(k_rot_scale, dim3(rot_blocks(k.w, k.h), L.n), dim3(kRotBlock), 0, st, k, static_cast<const long long*>(s.imgX), d_F);
+	}
+	return check_launch();
+}
+
+int launch_rot_eval(const uint64_t* d_events, const Unit* d_units, const RotWindows& L, const RotConsts& k, const double* d_omegas,
+					const RotScratch& s, double* d_r, double* d_g, void* stream)
+{
+	if (L.n <= 0)
+	{
+		return 0;
+	}
+	if (launch_rot_votes(d_events, d_units, L, k, d_omegas, s, nullptr, stream))
+	{
+		return -2;
+	}
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	const int nb = rot_blocks(k.w, k.h);
+	const dim3 px(nb, L.n), blk(kRotBlock);
+	hipLaunchKernelGGL((k_rot_hpass<false, true>), px, blk, 0, st, k, static_cast<const void*>(s.imgX), static_cast<const double*>(nullptr),
+					   s.imgY, static_cast<double*>(nullptr));
+	hipLaunchKernelGGL((k_rot_vpass<true>), px, blk, 0, st, k, static_cast<const double*>(s.imgY), s.imgZ, s.partB);
+	hipLaunchKernelGGL(k_rot_mean, dim3(L.n), dim3(64), 0, st, k, nb, static_cast<const double*>(s.partB), s.mu);
+	if (d_g)
+	{
+		hipLaunchKernelGGL((k_rot_hpass<true, true>), px, blk, 0, st, k, static_cast<const void*>(s.imgZ), static_cast<const double*>(s.mu),
+						   static_cast<double*>(s.imgX), s.partV);
+		hipLaunchKernelGGL((k_rot_vpass<false>), px, blk, 0, st, k, static_cast<const double*>(s.imgX), s.imgY, static_cast<double*>(nullptr));
+		hipLaunchKernelGGL(k_rot_gather, dim3(k.P, L.n), blk, 0, st, d_events, d_units, L, k, d_omegas, static_cast<const double*>(s.imgY),
+						   s.partG);
+	}
+	else
+	{
+		hipLaunchKernelGGL((k_rot_hpass<true, false>), px, blk, 0, st, k, static_cast<const void*>(s.imgZ), static_cast<const double*>(s.mu),
+						   static_cast<double*>(nullptr), s.partV);
+	}
+	hipLaunchKernelGGL(k_rot_finish, dim3(L.n), dim3(64), 0, st, L, k, nb, static_cast<const double*>(s.partV),
+					   static_cast<const double*>(s.partG), d_r, d_g);
+	return check_launch();
 }
 
 // track evaluation (ebo_trackerr.inc): one wave per (track, threshold) unit

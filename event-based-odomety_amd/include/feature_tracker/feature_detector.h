@@ -755,6 +755,9 @@ class FeatureDetector
 		reset();
 	}
 	ebo_ctx* handle() { return ctx_; }
+	// the second context of compensateWindows (null before its first call): after a call it holds the windows of the
+	// call's last chunk, which is the whole call unless max_events split it or a window was refused
+	ebo_ctx* batchHandle() { return batchCtx_; }
 
 	// Rectify events at load (include/ebo.h: ebo_set_rectification): every window this detector compensates or
 	// integrates afterwards -- compensateEventsContrast, integrateEvents, compensateWindows -- is bucketed through the

@@ -14,10 +14,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "../feature_tracker/angular_velocity.h"
 #include "../feature_tracker/feature_detector.h"
 
 namespace tools
@@ -52,6 +54,13 @@ struct EvaluatorParams
 	// the one fitted to the sensor (common::fitRectifiedCamera), which keeps every corner in view.
 	bool rectifyFrames = false;
 	common::CameraModelParams<double> rectifiedCamera;
+	// true: the camera's angular velocity is estimated on every compensation window (tracker::AngularVelocityEstimator,
+	// feature_tracker/angular_velocity.h) from the events the compensation has just loaded -- no second upload; with
+	// windowBatch > 1 one batched solve per flushed queue.  The camera is the rectified one when events are rectified,
+	// else cameraModelParams when it has no distortion; otherwise the pump refuses at construction (rectifyEvents).
+	bool estimateAngularVelocity = false;
+	ebo_rotation_params rotationParams = tracker::defaultRotationParams();
+	ebo_rot_solver_opts rotationSolver = tracker::defaultRotationSolver();
 };
 
 class EventPump
@@ -89,6 +98,12 @@ class EventPump
 		{
 			tracker_.setRectification(params_.cameraModelParams);
 		}
+		if (params_.estimateAngularVelocity)
+		{
+			rotation_.reset(new tracker::AngularVelocityEstimator(
+				tracker::AngularVelocityEstimator::cameraFor(tracker_.handle(), params_.cameraModelParams), params_.rotationParams,
+				params_.rotationSolver));
+		}
 	}
 
 	void onWindow(WindowCallback cb) { onWindow_ = std::move(cb); }
@@ -116,6 +131,11 @@ class EventPump
 			const size_t n = tracker_.getEvents().size();
 			tracker_.compensateEventsContrast(tracker_.getEvents());
 			tracker_.integrateEvents(tracker_.getEvents());
+			if (rotation_)
+			{
+				// the window integrateEvents has just loaded is resident in the detector's context
+				appendEstimates(rotation_->estimate(tracker_.handle()));
+			}
 			if (onWindow_)
 			{
 				onWindow_(tracker_, n);
@@ -157,7 +177,28 @@ class EventPump
 			}
 			++windows_;
 		});
+		if (rotation_)
+		{
+			// One batched compensation normally leaves exactly these windows resident in the batch context.  A queue that
+			// the compensation had to split (windowBatch above FeatureDetector::kMaxBatchWindows, max_events) or that lost
+			// a window is estimated chunk by chunk from a second load; a window the loader refuses alone gets an entry with
+			// status EBO_ROT_RUNNING and no estimate, so a run the compensation tolerated is not ended here.
+			ebo_ctx* batch = tracker_.batchHandle();
+			int resident = 0;
+			const int nw = static_cast<int>(offsets.size() - 1);
+			if (batch && ebo_num_windows(batch, &resident) == EBO_OK && resident == nw)
+			{
+				appendEstimates(rotation_->estimate(batch));
+			}
+			else
+			{
+				appendEstimates(rotation_->estimateWindows(
+					batch, events, offsets, std::min(params_.windowBatch, tracker::FeatureDetector::kMaxBatchWindows)));
+			}
+		}
 	}
+	// EvaluatorParams::estimateAngularVelocity: one estimate per compensated window, in order
+	const std::vector<tracker::AngularVelocityEstimate>& angularVelocities() const { return angularVelocities_; }
 	size_t queuedWindows() const { return queueOffsets_.size() - 1; }
 
 	size_t windows() const { return windows_; }
@@ -210,6 +251,11 @@ class EventPump
 	}
 
    private:
+	void appendEstimates(const std::vector<tracker::AngularVelocityEstimate>& est)
+	{
+		angularVelocities_.insert(angularVelocities_.end(), est.begin(), est.end());
+	}
+
 	// the batched form of the compensation branch: the held events join the queue, the detector's list is
 	// cleared and lastCompensation moves to the window's last timestamp as compensateEventsContrast would move it
 	void queueWindow(const common::EventSample& sample)
@@ -234,6 +280,8 @@ class EventPump
 	size_t windows_ = 0;
 	std::vector<ebo_event> queueEvents_;
 	std::vector<size_t> queueOffsets_ = std::vector<size_t>(1, 0);
+	std::unique_ptr<tracker::AngularVelocityEstimator> rotation_;
+	std::vector<tracker::AngularVelocityEstimate> angularVelocities_;
 };
 
 // tools::Replayer (tools/replayer/src/replayer.cpp:42-131) for the two streams that decide WHEN the

@@ -82,6 +82,10 @@ class Evaluator
 		tracker_->preExit();
 		saveFeaturesTrajectory(tracker_->getArchivedPatches());
 		saveFinalCosts(tracker_->getOptimizedFinalCosts());
+		if (params_.estimateAngularVelocity)
+		{
+			saveAngularVelocities(pump_->angularVelocities());
+		}
 	}
 
 	// evaluator.cpp:32-45
@@ -212,6 +216,25 @@ class Evaluator
 					 << v.timeStampMicrosecond << std::endl;
 		}
 	}
+
+	// Not in the reference: <outputDir>/angular_velocity.txt, one line per compensation window,
+	// "t_ref_seconds wx wy wz r_at_zero r iterations status" (rad/s; status EBO_ROT_*)
+	void saveAngularVelocities(const std::vector<tracker::AngularVelocityEstimate>& estimates) const
+	{
+		const std::string file = params_.outputDir + "/angular_velocity.txt";
+		FILE* f = std::fopen(file.c_str(), "w");
+		if (!f)
+		{
+			throw std::runtime_error("tools::Evaluator: cannot write " + file);
+		}
+		for (const auto& e : estimates)
+		{
+			std::fprintf(f, "%.6f %.17g %.17g %.17g %.17g %.17g %d %d\n", static_cast<double>(e.tRefUs) * 1e-6, e.omega[0], e.omega[1],
+						 e.omega[2], e.summary.r_initial, e.summary.r_final, e.summary.iterations, e.summary.status);
+		}
+		std::fclose(f);
+	}
+	const std::vector<tracker::AngularVelocityEstimate>& angularVelocities() const { return pump_->angularVelocities(); }
 
 	// evaluator.cpp:165-171: the patches of a VO run, keyed by their current timestamp
 	void setPatches(const tracker::Patches& patches)

@@ -215,7 +215,7 @@ def _undistorted_grid(px, py, focal, cx, cy, k1, k2, p1, p2, iterations=60):
 
 
 def make_recording(path, seed=0, size=(240, 180), duration_s=0.8, fps=24.0, velocity=(40.0, -25.0), threshold=0.25,
-                   step_us=1000, focal=200.0, distortion=None):
+                   step_us=1000, focal=200.0, distortion=None, angular_velocity=None):
     """Writes a DAVIS240C recording directory at `path`: events.txt, images.txt + images/frame_<i>.png,
     groundtruth.txt and calib.txt.
 
@@ -231,7 +231,13 @@ def make_recording(path, seed=0, size=(240, 180), duration_s=0.8, fps=24.0, velo
     model of include/ebo.h with fx = fy = focal and the sensor centre).  A point of the ideal pinhole image appears at
     `project` of its position: sensor pixel (x, y) shows the scene at its undistorted position, found by iterating the
     model's fixed point to convergence.  calib.txt then carries the coefficients (k3 = 0).  The default (None) writes
-    exactly what this function wrote before the keyword existed."""
+    exactly what this function wrote before the keyword existed.
+
+    angular_velocity=(wx, wy, wz) in rad/s, camera frame: the scene rotates about the camera centre instead of
+    translating (`velocity` is ignored).  A static point moves by dX/dt = -omega x X in the camera frame, so the pixel
+    whose ray is X at time t shows the texture where project(R(omega t) X) falls, R the exact (Rodrigues) rotation.
+    groundtruth.txt then carries the rotation: zero translation and the quaternion (x y z w) of exp([omega]x t), camera
+    to world.  The default (None) writes exactly what this function wrote before the keyword existed."""
     w, h = size
     rng = np.random.default_rng(20240601 + seed)
     vx, vy = velocity
@@ -240,9 +246,32 @@ def make_recording(path, seed=0, size=(240, 180), duration_s=0.8, fps=24.0, velo
     if distortion is not None:
         gx, gy = _undistorted_grid(gx, gy, focal, w / 2.0, h / 2.0, *[float(v) for v in distortion])
         margin += int(np.ceil(max(-gx.min(), gx.max() - (w - 1), -gy.min(), gy.max() - (h - 1), 0.0)))
+    if angular_velocity is not None:
+        om = np.array([float(v) for v in angular_velocity])
+        rays = np.stack([(gx - w / 2.0) / focal, (gy - h / 2.0) / focal, np.ones_like(gx)], axis=-1)
+
+        def source(t_us):
+            """Where in the pinhole image of t = 0 every pixel of time t looks."""
+            rv = om * (t_us * 1e-6)
+            th = float(np.linalg.norm(rv))
+            R = np.eye(3)
+            if th > 0.0:
+                kx, ky, kz = rv / th
+                K = np.array([[0.0, -kz, ky], [kz, 0.0, -kx], [-ky, kx, 0.0]])
+                R = np.eye(3) + np.sin(th) * K + (1.0 - np.cos(th)) * (K @ K)
+            X = rays @ R.T
+            return focal * X[..., 0] / X[..., 2] + w / 2.0, focal * X[..., 1] / X[..., 2] + h / 2.0
+
+        margin = 4
+        for t_us in np.linspace(0.0, duration_s * 1e6, 17):
+            sx, sy = source(t_us)
+            margin = max(margin, 4 + int(np.ceil(max(-sx.min(), sx.max() - (w - 1), -sy.min(), sy.max() - (h - 1), 0.0))))
     tex = _smooth_texture(rng, h + 2 * margin, w + 2 * margin)
 
     def render(t_us):
+        if angular_velocity is not None:
+            sx, sy = source(t_us)
+            return _bilinear(tex, sx + margin, sy + margin)
         t = t_us * 1e-6
         return _bilinear(tex, gx + margin - vx * t, gy + margin - vy * t)
 
@@ -287,6 +316,12 @@ def make_recording(path, seed=0, size=(240, 180), duration_s=0.8, fps=24.0, velo
     with open(os.path.join(path, "groundtruth.txt"), "w") as f:
         for k in range(0, n_steps + 1, 10):
             ts = k * step_us
+            if angular_velocity is not None:
+                rv = om * (ts * 1e-6)
+                th = float(np.linalg.norm(rv))
+                q = np.append(rv / th * np.sin(th / 2.0), np.cos(th / 2.0)) if th > 0.0 else np.array([0.0, 0.0, 0.0, 1.0])
+                f.write("%d.%06d000 0.0 0.0 0.0 %.9f %.9f %.9f %.9f\n" % ((ts // 1000000, ts % 1000000) + tuple(q)))
+                continue
             f.write("%d.%06d000 %.9f %.9f 0.0 0.0 0.0 0.0 1.0\n" % (ts // 1000000, ts % 1000000,
                                                                    -vx * ts * 1e-6 / focal, -vy * ts * 1e-6 / focal))
     with open(os.path.join(path, "calib.txt"), "w") as f:
@@ -294,4 +329,6 @@ def make_recording(path, seed=0, size=(240, 180), duration_s=0.8, fps=24.0, velo
             f.write("%g %g %g %g 0 0 0 0 0\n" % (focal, focal, w / 2.0, h / 2.0))
         else:  # calib.txt's order: fx fy cx cy k1 k2 p1 p2 k3
             f.write("%g %g %g %g %s 0\n" % (focal, focal, w / 2.0, h / 2.0, " ".join(repr(float(v)) for v in distortion)))
+    if angular_velocity is not None:
+        return dict(events=len(ev), frames=i, velocity=(vx, vy), angular_velocity=tuple(float(v) for v in om))
     return dict(events=len(ev), frames=i, velocity=(vx, vy))

@@ -1,6 +1,6 @@
 // track_recording — the reference's feature-tracking experiment on a DAVIS240C recording directory, without OpenCV:
 //
-//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--maintain-map] [--ate] [--rpe]]
+//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--angular-velocity] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--maintain-map] [--ate] [--rpe]]
 //
 // DIR holds events.txt, images.txt + the frames (8-bit grey PNG), optionally groundtruth.txt / calib.txt.
 // --rectify: the events of every compensation window are undistorted with the recording's calib.txt as they are
@@ -11,6 +11,11 @@
 // end is given it instead of the lens calibration: the tracks are already undistorted.  The
 // recording is played through tools::Replayer into tools::Evaluator::replay (tools/recording_evaluator.h; the files
 // equal those of per-event callbacks).
+// --angular-velocity: the camera's angular velocity is estimated on every compensation window by rotational contrast
+// maximisation (tools::EvaluatorParams::estimateAngularVelocity, feature_tracker/angular_velocity.h), from the events the
+// compensation loaded, batched under --window-batch.  OUT/angular_velocity.txt gets one line per window:
+// "t_ref_seconds wx wy wz r_at_zero r iterations status" (rad/s, camera frame).  The camera is the rectified one with
+// --rectify / --rectify-frames, else calib.txt's when it has no distortion; otherwise the run is refused: use --rectify.
 // --odometry: visual_odometry::VisualOdometryFrontEnd (visual_odometry/visual_odometry.h) runs as the keyframe hook on a
 // context of its own and OUT/keyframe_poses.txt gets one line per keyframe, stored ones first: the timestamp and the
 // camera-to-world pose [R | t] row by row (the first keyframe is the world frame, the first baseline the unit of length).
@@ -61,7 +66,7 @@
 
 static int usage(const char* argv0)
 {
-	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--maintain-map] [--ate] [--rpe]]\n", argv0);
+	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--angular-velocity] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--maintain-map] [--ate] [--rpe]]\n", argv0);
 	return 2;
 }
 
@@ -71,6 +76,7 @@ int main(int argc, char** argv)
 	bool trackerExperiment = false;
 	size_t windowBatch = 1;
 	bool rectify = false, rectifyFrames = false;
+	bool angularVelocity = false;
 	bool trackError = false;
 	double trackErrorThreshold = 5.0;
 	bool odometry = false, bundleAdjust = false, refine = false, refineTwoView = false, maintainMap = false, ate = false, rpe = false;
@@ -96,6 +102,10 @@ int main(int argc, char** argv)
 		else if (a == "--rectify-frames")
 		{
 			rectifyFrames = true;
+		}
+		else if (a == "--angular-velocity")
+		{
+			angularVelocity = true;
 		}
 		else if (a == "--odometry")
 		{
@@ -189,6 +199,11 @@ int main(int argc, char** argv)
 			p.cameraModelParams = recording->getCalibration();
 			p.rectifyEvents = true;
 			p.rectifyFrames = true;
+		}
+		if (angularVelocity)
+		{
+			p.cameraModelParams = recording->getCalibration();
+			p.estimateAngularVelocity = true;
 		}
 		size_t events = 0, frames = 0, tracks = 0, windows = 0, keyframes = 0, landmarks = 0;
 		ebo_track_error_summary_result trackSummary{};

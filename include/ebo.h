@@ -1577,6 +1577,129 @@ int ebo_landmark_scores_device(ebo_ctx* ctx, int n_poses, const double* d_poses,
 							   const ebo_landmark_params* params, ebo_landmark_result* d_results, double* d_scores_or_null,
 							   uint8_t* d_inlier_flags_or_null);
 
+/* ---- angular velocity from events: rotational contrast maximisation ------------------------------
+ * A global warp of every resident window by the camera's rotation, the variance of the image of warped events as the
+ * objective, its exact gradient, and a three-variable solver: one angular velocity per window.  The rules are this
+ * project's own (the reference has no counterpart); tests/rotation_ref.py restates them in numpy.  All arithmetic is
+ * float64; in V2 and V3 every operation is rounded on its own, in the association written, with no contraction
+ * (__dadd_rn and the others, as the camera model), because they decide integer bits.
+ *
+ * Inputs: the windows resident in the context, loaded by any ebo_set_window* loader (rectified coordinates when a
+ * rectification is set; events of a window's stray unit take no part); a pinhole camera `cam` under rule C1 (k1 k2 p1
+ * p2 all zero, else EBO_ERR_ARG; fx or fy not finite or zero: EBO_ERR_RANGE); one omega = (wx, wy, wz) in rad/s per
+ * window, the camera's angular velocity in the camera frame: a static point moves by dX/dt = -omega x X.
+ *
+ * V1. Per event: integer pixel (x, y), dt = t_ref(window) - t_event in microseconds, t_ref(window) as ebo_window_info
+ *     reports it.   a = (x - cx) / fx;  b = (y - cy) / fy;  tau = dt * 1e-6;  th = (tau * wx, tau * wy, tau * wz).
+ * V2. First-order rotation to the reference time, X - th x X on (a, b, 1):
+ *       X = (a - thy) + thz * b;   Y = (b - thz * a) + thx;   Z = (1 - thx * b) + thy * a
+ *     If not (Z > 0) the event is skipped.   u = fx * (X / Z) + cx;   v = fy * (Y / Z) + cy.
+ *     If not (u > -1 and u < w and v > -1 and v < h) the event is skipped.  Both tests are made in double before any
+ *     conversion to an integer: a NaN, an infinity or omega = 1e9 skips the event and reads or writes nothing.  omega is
+ *     not validated; a NaN in it gives the empty image and the zeros the rules give.
+ * V3. Bilinear vote in exact fixed point.  x0 = floor(u); y0 = floor(v); al = u - x0; be = v - y0; ial = 1 - al;
+ *     ibe = 1 - be.  The weights ial * ibe, al * ibe, ial * be, al * be go to (x0, y0), (x0+1, y0), (x0, y0+1),
+ *     (x0+1, y0+1).  Each becomes the int64 q = rint(weight * 2^30), ties to even, added to the int64 vote image H[y][x]
+ *     at the taps inside the image.  Integer adds commute: H depends neither on the order of the events nor on the
+ *     kernel's design, and cannot overflow below 2^31 events per window.
+ * V4. F = H * 2^-30.
+ * V5. Blur.  sigma_blur (default 1.0) is 0 or positive and finite, else EBO_ERR_ARG.  For sigma_blur > 0 the seven
+ *     weights g_d = exp(-d^2 / (2 sigma^2)), d = -3 .. 3, are divided by their sum taken in that order, on the host (the
+ *     kernels receive seven doubles and call no exp).  B = the horizontal pass followed by the vertical pass; an output
+ *     is the sum, from 0, in tap order d = -3 .. 3 of g_d * value; taps outside the image are skipped, nothing is
+ *     renormalised.  With sigma_blur = 0, B = F (the weights 0 0 0 1 0 0 0 give exactly that).
+ * V6. Np = w * h;  mu = sum(B) / Np;  r = sum((B - mu)^2) / Np: the variance, to be maximised.
+ * V7. C = the same two passes applied to B - mu.  The blur with dropped taps is a symmetric operator and
+ *     sum(B - mu) = 0, so V8 is the exact gradient of V6 between pixel crossings.
+ * V8. For every event that voted, c00 c10 c01 c11 = C at its four taps, 0 at a tap outside the image.
+ *       Du = ibe * (c10 - c00) + be * (c11 - c01);   Dv = ial * (c01 - c00) + al * (c11 - c10)
+ *       dX/dth = (0, -1, b);  dY/dth = (1, 0, -a);  dZ/dth = (-b, a, 0)
+ *       du/dth_i = fx * (dX_i * Z - X * dZ_i) / Z^2;   dv/dth_i = fy * (dY_i * Z - Y * dZ_i) / Z^2
+ *       g_i = (2 / Np) * sum over the events of tau * (Du * du/dth_i + Dv * dv/dth_i)
+ *     At al = 0 or be = 0 this is the right-hand derivative, which is what floor gives.
+ * V9. H is bit-equal to the restatement.  r and g are deterministic: the same bits for a window alone, inside any
+ *     batch, at any position of it, and from run to run -- every sum follows a fixed order that does not depend on the
+ *     launch: 256 consecutive pixels (resp. a patch's events, lane t taking events t, t + 256, ..) fold by the wave's
+ *     shuffle tree 32, 16, .. 1 and then wave 0 + 1 + 2 + 3; of a window's folds, lane l of one wave adds folds l, l + 64, ..
+ *     in ascending order and the same shuffle tree adds the lanes.  Against
+ *     the restatement |dr| <= 1e-9 * sum(B^2) / Np and |dg_i| <= 1e-9 * A_i with
+ *     A_i = (2 / Np) * sum |tau| * (|Du * du/dth_i| + |Dv * dv/dth_i|): a float64 sum of n <= 2e5 terms errs by at most
+ *     n * 2^-53 = 2e-11 of these scales.
+ *
+ * The solver minimises f = -r with gf = -g; dot(a, b) = (a0 * b0 + a1 * b1) + a2 * b2.
+ * N1. Evaluate at omega0.  f or gf not finite: NONFINITE.  gmax = max |gf_i|; gmax == 0: CONVERGED_GRADIENT.
+ *     alpha = first_rate / gmax (the largest component of the first trial step is first_rate).
+ * N2. d = -gf; slope = -dot(gf, gf); omega_t = omega + alpha * d.  Evaluate (f_t, gf_t) at omega_t.
+ * N3. Accepted when f_t and gf_t are finite and f_t <= f + (c1 * alpha) * slope.  Otherwise alpha = alpha / 2,
+ *     backtracks += 1; at max_backtracks: NO_PROGRESS, keeping omega; else N2.
+ * N4. Accepted: s = omega_t - omega; y = gf_t - gf; (omega, f, gf) = (omega_t, f_t, gf_t); iterations += 1;
+ *     backtracks = 0.  max |s_i| < step_tol: CONVERGED_STEP.  iterations == max_iterations: MAX_ITERATIONS.  Otherwise
+ *     sy = dot(s, y); alpha = dot(s, s) / sy when sy > 0 (Barzilai-Borwein), else 2 * alpha; N2.
+ * N5. The summary: status, iterations, evaluations, r at omega0 and r at the result.
+ *
+ * ebo_eval_rotation: r [Wn] and, unless g is NULL, g [Wn][3] at omegas [Wn][3] for all resident windows; with g NULL
+ *   the value-only path skips V7 and V8 and returns the same r bits.  Host pointers, synchronous.  The _device form
+ *   takes device pointers and is asynchronous on the context's stream.
+ * ebo_rotation_image: H as int64 [Wn][h][w] and F as double [Wn][h][w] (either may be NULL): F is the image of
+ *   rotationally compensated events a user looks at.
+ * ebo_rot_solver_*: N1-N5 for n windows at once as a host object, no device and no context involved.
+ *   _request(omegas [n][3], live [n] or NULL): the points wanted; returns the number of windows still waiting (0: all
+ *   finished), < 0 = EBO_ERR_*.  _supply(r [n], g [n][3]): entries of finished windows are ignored; EBO_ERR_STATE once
+ *   all have finished.  _result(omegas [n][3] or NULL, summary [n] or NULL).
+ * ebo_solve_rotation: lock-step rounds over the resident windows from omega0 ([Wn][3], NULL: zeros); every round
+ *   evaluates the windows still waiting, and only those, in one batched pass, then the host solver steps.  A window's
+ *   result has the same bits alone and in any batch (V9).
+ * Evaluation scratch is three images of 8 bytes a pixel per window; windows are evaluated in chunks of at most 64 under
+ *   a budget of 256 MiB (environment EBO_ROTATION_SCRATCH_MB).
+ * Errors: EBO_ERR_STATE with no windows loaded, with units loaded by ebo_set_patches, or while a graph is being
+ *   recorded; EBO_ERR_ARG / EBO_ERR_RANGE as in the rules; EBO_ERR_ARG for a needed pointer that is NULL or solver
+ *   options outside first_rate > 0, 0 < c1 < 1, max_backtracks >= 1, step_tol >= 0, max_iterations >= 1. */
+#define EBO_ROT_RUNNING -1
+#define EBO_ROT_CONVERGED_STEP 0
+#define EBO_ROT_CONVERGED_GRADIENT 1
+#define EBO_ROT_MAX_ITERATIONS 2
+#define EBO_ROT_NO_PROGRESS 3
+#define EBO_ROT_NONFINITE 4
+typedef struct ebo_rotation_params
+{
+	double sigma_blur;  /* V5; 0 or positive and finite */
+	double reserved;    /* 0 */
+} ebo_rotation_params;
+typedef struct ebo_rot_solver_opts
+{
+	double first_rate;   /* rad/s, N1 */
+	double c1;           /* N3 */
+	double step_tol;     /* rad/s, N4 */
+	int max_backtracks;  /* N3 */
+	int max_iterations;  /* N4 */
+} ebo_rot_solver_opts;
+typedef struct ebo_rot_summary
+{
+	int status;       /* EBO_ROT_* */
+	int iterations;   /* accepted steps */
+	int evaluations;  /* evaluations supplied */
+	int reserved;     /* 0 */
+	double r_initial; /* r at omega0 */
+	double r_final;   /* r at the result */
+} ebo_rot_summary;
+/* sigma_blur 1.0 */
+void ebo_default_rotation_params(ebo_rotation_params* params);
+/* first_rate 0.5, c1 1e-4, step_tol 1e-4, max_backtracks 20, max_iterations 100 */
+void ebo_default_rot_solver_opts(ebo_rot_solver_opts* opts);
+int ebo_eval_rotation(ebo_ctx* ctx, const ebo_camera* cam, const ebo_rotation_params* params, const double* omegas, double* r,
+					  double* g_or_null);
+int ebo_eval_rotation_device(ebo_ctx* ctx, const ebo_camera* cam, const ebo_rotation_params* params, const double* d_omegas,
+							 double* d_r, double* d_g_or_null);
+int ebo_rotation_image(ebo_ctx* ctx, const ebo_camera* cam, const double* omegas, int64_t* votes_or_null, double* image_or_null);
+typedef struct ebo_rot_solver ebo_rot_solver;
+int ebo_rot_solver_create(int n, const ebo_rot_solver_opts* opts, const double* omega0_or_null, ebo_rot_solver** out);
+int ebo_rot_solver_request(ebo_rot_solver* s, double* omegas, uint8_t* live_or_null);
+int ebo_rot_solver_supply(ebo_rot_solver* s, const double* r, const double* g);
+int ebo_rot_solver_result(const ebo_rot_solver* s, double* omegas_or_null, ebo_rot_summary* summary_or_null);
+void ebo_rot_solver_destroy(ebo_rot_solver* s);
+int ebo_solve_rotation(ebo_ctx* ctx, const ebo_camera* cam, const ebo_rotation_params* params, const ebo_rot_solver_opts* opts,
+					   const double* omega0_or_null, double* omega_out, ebo_rot_summary* summary_or_null);
+
 /* Device-side timing of everything enqueued between begin and end on the
  * context's stream (hipEvent based). */
 int ebo_timer_begin(ebo_ctx* ctx);
