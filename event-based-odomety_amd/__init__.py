@@ -137,6 +137,23 @@ class RotationParams(C.Structure):
         super().__init__(float(sigma_blur), 0.0)
 
 
+class DepthParams(C.Structure):
+    """ebo_depth_params: the planes (rule M1), the threshold's box radius and excess (M6), the median radius (M7)."""
+    _fields_ = [("nz", C.c_int32), ("box_radius", C.c_int32), ("median_radius", C.c_int32), ("reserved", C.c_int32),
+                ("z_near", C.c_double), ("z_far", C.c_double), ("min_excess", C.c_double)]
+
+
+def default_depth_params(**kw):
+    """ebo_default_depth_params (nz 64, z_near 0.5, z_far 8, box_radius 2, min_excess 3, median_radius 2), with overrides."""
+    o = DepthParams()
+    lib().ebo_default_depth_params(C.byref(o))
+    for key, val in kw.items():
+        if not hasattr(o, key):
+            raise AttributeError(key)
+        setattr(o, key, val)
+    return o
+
+
 class RotSolverOpts(C.Structure):
     """ebo_rot_solver_opts (rules N1-N5)."""
     _fields_ = [("first_rate", C.c_double), ("c1", C.c_double), ("step_tol", C.c_double), ("max_backtracks", C.c_int32),
@@ -357,6 +374,13 @@ def lib():
         _lib.ebo_triangulate_tracks_device.argtypes = _lmt
         _lib.ebo_landmark_scores.argtypes = _lmt + [C.c_void_p]
         _lib.ebo_landmark_scores_device.argtypes = _lmt + [C.c_void_p]
+        _lib.ebo_default_depth_params.argtypes = [C.c_void_p]
+        _lib.ebo_default_depth_params.restype = None
+        _lib.ebo_dsi_begin.argtypes = [C.c_void_p] * 4
+        _lib.ebo_dsi_add_windows.argtypes = [C.c_void_p] * 3
+        _lib.ebo_dsi_volume.argtypes = [C.c_void_p] * 2
+        _lib.ebo_dsi_depth.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+        _lib.ebo_dsi_end.argtypes = [C.c_void_p]
         _lib.ebo_default_rotation_params.argtypes = [C.c_void_p]
         _lib.ebo_default_rotation_params.restype = None
         _lib.ebo_default_rot_solver_opts.argtypes = [C.c_void_p]
@@ -1864,6 +1888,44 @@ class Context:
         self._check(lib().ebo_solve_rotation(self._h, C.addressof(k), C.addressof(prm), C.byref(opts) if opts is not None else None,
                                              _dp(o0) if o0 is not None else None, _dp(out), summ))
         return out, list(summ)
+
+    # -- depth from events (space-sweep voting, rules M1-M9) --------------------------------------------------
+    def dsi_begin(self, cam, ref_pose, params=None):
+        """ebo_dsi_begin: opens and clears the volume of a reference view; ref_pose 12 doubles (R row-major, t)."""
+        k = camera(cam)
+        ref = np.ascontiguousarray(ref_pose, dtype=np.float64).reshape(12)
+        prm = params if params is not None else default_depth_params()
+        self._check(lib().ebo_dsi_begin(self._h, C.addressof(k), _dp(ref), C.addressof(prm)))
+        self._dsi_prm = prm  # a refused begin leaves the open volume, and its shape, as they were
+
+    def dsi_add_windows(self, poses, use=None):
+        """ebo_dsi_add_windows: votes the resident windows; poses [Wn][12], use [Wn] (None: all)."""
+        po = np.ascontiguousarray(poses, dtype=np.float64).reshape(self.n_windows, 12)
+        u = None if use is None else np.ascontiguousarray(use, dtype=np.uint8).reshape(self.n_windows)
+        self._check(lib().ebo_dsi_add_windows(self._h, _dp(po), _vp(u) if u is not None else None))
+
+    def dsi_volume(self):
+        """ebo_dsi_volume -> H uint32 [nz][h][w]"""
+        prm = getattr(self, "_dsi_prm", None)  # None: no begin yet, the call is refused before it writes
+        Hq = np.zeros((prm.nz if prm else 1, self.params.image_h, self.params.image_w), dtype=np.uint32)
+        self._check(lib().ebo_dsi_volume(self._h, _vp(Hq)))
+        return Hq
+
+    def dsi_depth(self, max_points=None):
+        """ebo_dsi_depth -> (index int32 [h][w], conf uint32 [h][w], depth [h][w], points [min(n, max_points)][3], n);
+        max_points None: every kept pixel."""
+        h, w = self.params.image_h, self.params.image_w
+        cap = h * w if max_points is None else int(max_points)
+        index = np.zeros((h, w), dtype=np.int32)
+        conf = np.zeros((h, w), dtype=np.uint32)
+        depth = np.zeros((h, w))
+        points = np.zeros((max(cap, 1), 3))
+        n = C.c_int(0)
+        self._check(lib().ebo_dsi_depth(self._h, _vp(index), _vp(conf), _dp(depth), _dp(points), cap, C.byref(n)))
+        return index, conf, depth, points[:min(n.value, cap)], n.value
+
+    def dsi_end(self):
+        self._check(lib().ebo_dsi_end(self._h))
 
     # -- track evaluation (KLT reference tracks on the frames, track error and feature age) ------------------
     def reference_tracks(self, frames, frame_t_us, seed_frame, seed_xy, win=(21, 21), max_level=3, max_count=30, epsilon=0.01,

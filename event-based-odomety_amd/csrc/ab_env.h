@@ -9,6 +9,10 @@
 // the switches the equivalence tests flip -- goes through ab_env() / ab_size(), which look at the environment only
 // in the -DEBO_AB build (`make ab` -> libebo_hip_ab.so: what tools/ab/*, the tools' A/B scripts and the tests' `ebo_ab`
 // fixture load).  In the shipped build they are constant: one path per call, no knob string in the binary.
+// Among them, the space-sweep vote's (ebo_depth.cpp):
+//   EBO_DSI_TILE = 0     every tap of k_dsi_vote a global atomic instead of the LDS tile per (patch, plane); read by
+//                        ebo_dsi_begin
+//   EBO_DSI_PLANES = n   planes per workgroup of k_dsi_vote instead of the count the launch size gives
 #pragma once
 
 #include <cstdlib>

@@ -174,6 +174,18 @@ struct ebo_ctx
 	Dev<void> d_rot;  // ebo_rotation.cpp: a chunk's three images and folds (RotScratch)
 	Dev<double> d_rot_io;  // its host entries' omegas [Wn][3], r [Wn], g [Wn][3]
 
+	// ebo_depth.cpp: the space-sweep volume between ebo_dsi_begin and ebo_dsi_end
+	Dev<uint32_t> d_dsi;  // H [nz][h][w]
+	Dev<double> d_dsi_z;  // M1's table [nz]
+	Dev<DsiPose> d_dsi_pose;  // M2's relative poses of the resident windows [Wn]
+	Dev<void> d_dsi_x;  // the extraction's maps and point list (DsiScratch)
+	bool dsi_live = false;
+	DsiConsts dsi_k = {};
+	ebo_depth_params dsi_prm = {};
+	double dsi_ref[12] = {};
+	std::vector<double> dsi_z;
+	uint64_t dsi_events = 0;  // events the volume has accepted (M4's cap)
+
 	std::vector<Unit> units;       // [Wn][P+1], stray unit last in each window
 	std::vector<int64_t> unit_tref;
 	std::vector<int64_t> unit_tmin, unit_tmax;  // ebo_set_patches: earliest / latest event time per unit (ebo_count_image_shard)

@@ -19,6 +19,7 @@
 #include "ebo_trackerr.h"
 #include "ebo_landmark.h"
 #include "ebo_rotation.h"
+#include "ebo_depth.h"
 
 namespace ebo
 {
@@ -585,6 +586,30 @@ int launch_rot_votes(const uint64_t* d_events, const Unit* d_units, const RotWin
 // r (and g unless d_g is null) of the chunk's windows into d_r[win] / d_g[win][3]
 int launch_rot_eval(const uint64_t* d_events, const Unit* d_units, const RotWindows& L, const RotConsts& k, const double* d_omegas,
 					const RotScratch& s, double* d_r, double* d_g, void* stream);
+
+// depth from events by space sweep (ebo_depth.inc, ebo_depth.cpp; DsiWindows, DsiConsts, DsiPose: ebo_depth.h).
+// the votes of one chunk of windows (slot s is window win[s], BY VALUE as RotWindows is) into the volume d_H [nz][h][w];
+// d_poses is indexed by window, d_z is M1's table
+int launch_dsi_vote(const uint64_t* d_events, const Unit* d_units, int P, const DsiWindows& L, const DsiConsts& k, const DsiPose* d_poses,
+					const double* d_z, uint32_t* d_H, void* stream);
+// the extraction's scratch, all of it per pixel except blockCount [dsi_blocks + 1]
+struct DsiScratch
+{
+	uint32_t* conf;
+	int* kbest;
+	int* index;
+	double* depth;
+	int* blockCount;
+	unsigned char* keep;
+	double* points;  // [max_points][3], null when no point is wanted
+};
+inline int dsi_blocks(int w, int h)
+{
+	return (w * h + kDsiBlock - 1) / kDsiBlock;
+}
+// M5-M8 of the volume d_H; blockCount[dsi_blocks] receives the number of kept pixels
+int launch_dsi_extract(const DsiConsts& k, int r, long long off, int m, const double* d_z, const uint32_t* d_H, const DsiScratch& s,
+					   int max_points, void* stream);
 
 // track evaluation (ebo_trackerr.inc, ebo_trackerr.cpp): unit k * n_taus + j is track k, samples d_est_off[k] .. d_est_off[k + 1] - 1
 // of d_est_t / d_est_xy (n_est of them) and d_gt_off[k] .. d_gt_off[k + 1] - 1 of d_gt_t / d_gt_xy (n_gt), at threshold d_taus[j];

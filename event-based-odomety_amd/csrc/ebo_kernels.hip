@@ -1290,6 +1290,7 @@ __global__ void __launch_bounds__(64) k_route(const uint32_t* __restrict__ xy, u
 #include "ebo_trackerr.inc"
 #include "ebo_landmark.inc"
 #include "ebo_rotation.inc"
+#include "ebo_depth.inc"
 #include "ebo_field.inc"
 #include "ebo_fieldtv.inc"
 #include "ebo_optimizer.inc"
@@ -2121,6 +2122,39 @@ int launch_rot_eval(const uint64_t* d_events, const Unit* d_units, const RotWind
 	}
 	hipLaunchKernelGGL(k_rot_finish, dim3(L.n), dim3(64), 0, st, L, k, nb, static_cast<const double*>(s.partV),
 					   static_cast<const double*>(s.partG), d_r, d_g);
+	return check_launch();
+}
+
+// depth from events by space sweep (ebo_depth.inc): the votes of one chunk of windows
+int launch_dsi_vote(const uint64_t* d_events, const Unit* d_units, int P, const DsiWindows& L, const DsiConsts& k, const DsiPose* d_poses,
+					const double* d_z, uint32_t* d_H, void* stream)
+{
+	if (L.n <= 0 || k.planes < 1)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_dsi_vote, dim3(P, L.n, (k.nz + k.planes - 1) / k.planes), dim3(kDsiBlock), 0, static_cast<hipStream_t>(stream),
+					   d_events, d_units, L, k, d_poses, d_z, d_H);
+	return check_launch();
+}
+
+int launch_dsi_extract(const DsiConsts& k, int r, long long off, int m, const double* d_z, const uint32_t* d_H, const DsiScratch& s,
+					   int max_points, void* stream)
+{
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	const int nb = dsi_blocks(k.w, k.h);
+	const dim3 px(nb), blk(kDsiBlock);
+	hipLaunchKernelGGL(k_dsi_argmax, px, blk, 0, st, k, d_H, s.conf, s.kbest);
+	hipLaunchKernelGGL(k_dsi_keep, px, blk, 0, st, k, r, off, static_cast<const unsigned int*>(s.conf), s.keep);
+	hipLaunchKernelGGL(k_dsi_median, px, blk, 0, st, k, m, static_cast<const int*>(s.kbest), static_cast<const unsigned char*>(s.keep), d_z,
+					   s.index, s.depth);
+	hipLaunchKernelGGL(k_dsi_count, px, blk, 0, st, k, static_cast<const int*>(s.index), s.blockCount);
+	hipLaunchKernelGGL(k_dsi_scan, dim3(1), blk, 0, st, nb, s.blockCount);
+	if (s.points && max_points > 0)
+	{
+		hipLaunchKernelGGL(k_dsi_points, px, blk, 0, st, k, static_cast<const int*>(s.index), d_z, static_cast<const int*>(s.blockCount),
+						   max_points, s.points);
+	}
 	return check_launch();
 }
 

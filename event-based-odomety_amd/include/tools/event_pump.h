@@ -21,6 +21,7 @@
 
 #include "../feature_tracker/angular_velocity.h"
 #include "../feature_tracker/feature_detector.h"
+#include "../visual_odometry/depth_mapper.h"
 
 namespace tools
 {
@@ -61,6 +62,15 @@ struct EvaluatorParams
 	bool estimateAngularVelocity = false;
 	ebo_rotation_params rotationParams = tracker::defaultRotationParams();
 	ebo_rot_solver_opts rotationSolver = tracker::defaultRotationSolver();
+	// true: every compensation window votes into ONE space-sweep depth volume (visual_odometry::DepthMapper,
+	// visual_odometry/depth_mapper.h) from the events the compensation has just loaded -- no second upload; with
+	// windowBatch > 1 on the batch context, one call per flushed queue.  depthPoses is the pose source (timed poses, camera
+	// to world, ascending), depthReferenceTime the time of the reference view, inside their span; a window whose reference
+	// time lies outside it is left out.  The camera is chosen as for estimateAngularVelocity.
+	bool depthMap = false;
+	ebo_depth_params depthParams = visual_odometry::defaultDepthParams();
+	common::GroundTruth depthPoses;
+	common::timestamp_t depthReferenceTime{0};
 };
 
 class EventPump
@@ -104,6 +114,12 @@ class EventPump
 				tracker::AngularVelocityEstimator::cameraFor(tracker_.handle(), params_.cameraModelParams), params_.rotationParams,
 				params_.rotationSolver));
 		}
+		if (params_.depthMap)
+		{
+			depth_.reset(new visual_odometry::DepthMapper(
+				visual_odometry::DepthMapper::cameraFor(tracker_.handle(), params_.cameraModelParams), params_.depthPoses, params_.depthParams));
+			depth_->begin(params_.depthReferenceTime);
+		}
 	}
 
 	void onWindow(WindowCallback cb) { onWindow_ = std::move(cb); }
@@ -135,6 +151,10 @@ class EventPump
 			{
 				// the window integrateEvents has just loaded is resident in the detector's context
 				appendEstimates(rotation_->estimate(tracker_.handle()));
+			}
+			if (depth_)
+			{
+				depth_->addResidentWindows(tracker_.handle());
 			}
 			if (onWindow_)
 			{
@@ -196,9 +216,39 @@ class EventPump
 					batch, events, offsets, std::min(params_.windowBatch, tracker::FeatureDetector::kMaxBatchWindows)));
 			}
 		}
+		if (depth_)
+		{
+			// as above: the batch context holds exactly the queue's windows, or they are loaded again chunk by chunk
+			ebo_ctx* batch = tracker_.batchHandle();
+			int resident = 0;
+			if (batch && ebo_num_windows(batch, &resident) == EBO_OK && resident == static_cast<int>(offsets.size() - 1))
+			{
+				depth_->addResidentWindows(batch);
+			}
+			else
+			{
+				depth_->addWindows(batch, events, offsets, std::min(params_.windowBatch, tracker::FeatureDetector::kMaxBatchWindows));
+			}
+		}
 	}
 	// EvaluatorParams::estimateAngularVelocity: one estimate per compensated window, in order
 	const std::vector<tracker::AngularVelocityEstimate>& angularVelocities() const { return angularVelocities_; }
+	// EvaluatorParams::depthMap: the depth map of everything voted so far (queued windows are flushed first); the volume
+	// is closed, and the windows the mapper saw stay readable through depthWindows()
+	visual_odometry::DepthMap finishDepthMap()
+	{
+		if (!depth_)
+		{
+			throw std::runtime_error("tools::EventPump: EvaluatorParams::depthMap is not set");
+		}
+		flush();
+		return depth_->finish();
+	}
+	const std::vector<visual_odometry::DepthWindow>& depthWindows() const
+	{
+		static const std::vector<visual_odometry::DepthWindow> none;
+		return depth_ ? depth_->windows() : none;
+	}
 	size_t queuedWindows() const { return queueOffsets_.size() - 1; }
 
 	size_t windows() const { return windows_; }
@@ -282,6 +332,7 @@ class EventPump
 	std::vector<size_t> queueOffsets_ = std::vector<size_t>(1, 0);
 	std::unique_ptr<tracker::AngularVelocityEstimator> rotation_;
 	std::vector<tracker::AngularVelocityEstimate> angularVelocities_;
+	std::unique_ptr<visual_odometry::DepthMapper> depth_;
 };
 
 // tools::Replayer (tools/replayer/src/replayer.cpp:42-131) for the two streams that decide WHEN the

@@ -86,6 +86,11 @@ class Evaluator
 		{
 			saveAngularVelocities(pump_->angularVelocities());
 		}
+		if (params_.depthMap)
+		{
+			depthMap_ = pump_->finishDepthMap();
+			saveDepthMap(depthMap_, pump_->depthWindows());
+		}
 	}
 
 	// evaluator.cpp:32-45
@@ -236,6 +241,66 @@ class Evaluator
 	}
 	const std::vector<tracker::AngularVelocityEstimate>& angularVelocities() const { return pump_->angularVelocities(); }
 
+	// Not in the reference: <outputDir>/depth.txt, "x y depth confidence" per kept pixel in row-major order (confidence in
+	// votes, 1/1024 of an event each); <outputDir>/points.txt, "X Y Z" of the same pixels in the world frame; and
+	// <outputDir>/depth_windows.txt, the reference view first ("reference" and its pose) and then one line per window the
+	// mapper saw: "t_ref_us events used" and the pose it was voted with (R row-major, then t; zeros when not used)
+	void saveDepthMap(const visual_odometry::DepthMap& map, const std::vector<visual_odometry::DepthWindow>& windows) const
+	{
+		FILE* fd = std::fopen((params_.outputDir + "/depth.txt").c_str(), "w");
+		FILE* fp = std::fopen((params_.outputDir + "/points.txt").c_str(), "w");
+		FILE* fw = std::fopen((params_.outputDir + "/depth_windows.txt").c_str(), "w");
+		if (!fd || !fp || !fw)
+		{
+			for (FILE* f : {fd, fp, fw})
+			{
+				if (f)
+				{
+					std::fclose(f);
+				}
+			}
+			throw std::runtime_error("tools::Evaluator: cannot write depth.txt, points.txt or depth_windows.txt in " + params_.outputDir);
+		}
+		size_t k = 0;
+		for (int y = 0; y < map.height; ++y)
+		{
+			for (int x = 0; x < map.width; ++x)
+			{
+				const size_t p = static_cast<size_t>(y) * map.width + x;
+				if (map.index[p] >= 0)
+				{
+					std::fprintf(fd, "%d %d %.17g %u\n", x, y, map.depth[p], map.confidence[p]);
+					const common::Vector3d& q = map.points[k++];
+					std::fprintf(fp, "%.17g %.17g %.17g\n", q[0], q[1], q[2]);
+				}
+			}
+		}
+		double m[12];
+		visual_odometry::DepthMapper::toAbi(map.reference, m);
+		std::fprintf(fw, "reference");
+		for (const double v : m)
+		{
+			std::fprintf(fw, " %.17g", v);
+		}
+		std::fprintf(fw, "\n");
+		for (const auto& w : windows)
+		{
+			visual_odometry::DepthMapper::toAbi(w.pose, m);
+			std::fprintf(fw, "%lld %llu %d", static_cast<long long>(w.tRefUs), static_cast<unsigned long long>(w.events), w.used ? 1 : 0);
+			for (const double v : m)
+			{
+				std::fprintf(fw, " %.17g", w.used ? v : 0.0);
+			}
+			std::fprintf(fw, "\n");
+		}
+		std::fclose(fd);
+		std::fclose(fp);
+		std::fclose(fw);
+	}
+	// after finish(): the map that was written
+	const visual_odometry::DepthMap& depthMap() const { return depthMap_; }
+	const std::vector<visual_odometry::DepthWindow>& depthWindows() const { return pump_->depthWindows(); }
+
 	// evaluator.cpp:165-171: the patches of a VO run, keyed by their current timestamp
 	void setPatches(const tracker::Patches& patches)
 	{
@@ -283,6 +348,7 @@ class Evaluator
 	size_t imageNum_ = 0;
 	size_t events_ = 0;
 	bool finished_ = false;
+	visual_odometry::DepthMap depthMap_;
 };
 
 }  // namespace tools

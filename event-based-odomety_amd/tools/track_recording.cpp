@@ -1,6 +1,6 @@
 // track_recording — the reference's feature-tracking experiment on a DAVIS240C recording directory, without OpenCV:
 //
-//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--angular-velocity] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--maintain-map] [--ate] [--rpe]]
+//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--angular-velocity] [--depth-map] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--maintain-map] [--ate] [--rpe]]
 //
 // DIR holds events.txt, images.txt + the frames (8-bit grey PNG), optionally groundtruth.txt / calib.txt.
 // --rectify: the events of every compensation window are undistorted with the recording's calib.txt as they are
@@ -16,6 +16,13 @@
 // compensation loaded, batched under --window-batch.  OUT/angular_velocity.txt gets one line per window:
 // "t_ref_seconds wx wy wz r_at_zero r iterations status" (rad/s, camera frame).  The camera is the rectified one with
 // --rectify / --rectify-frames, else calib.txt's when it has no distortion; otherwise the run is refused: use --rectify.
+// --depth-map (needs a groundtruth.txt with samples): every compensation window votes into one space-sweep depth volume
+// (tools::EvaluatorParams::depthMap, visual_odometry/depth_mapper.h; include/ebo.h M1-M9) with the ground truth's pose at
+// its reference time, from the events the compensation loaded, on the batch context under --window-batch.  The
+// reference view is the ground truth's pose at the middle of its time span.  OUT/depth.txt gets "x y depth confidence"
+// per kept pixel, OUT/points.txt the same pixels' points in the ground truth's frame and OUT/depth_windows.txt the
+// reference pose and every window's reference time, event count, whether it was voted, and pose.  The camera is chosen
+// as for --angular-velocity: with a distorted calib.txt the run is refused without --rectify.
 // --odometry: visual_odometry::VisualOdometryFrontEnd (visual_odometry/visual_odometry.h) runs as the keyframe hook on a
 // context of its own and OUT/keyframe_poses.txt gets one line per keyframe, stored ones first: the timestamp and the
 // camera-to-world pose [R | t] row by row (the first keyframe is the world frame, the first baseline the unit of length).
@@ -66,7 +73,7 @@
 
 static int usage(const char* argv0)
 {
-	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--angular-velocity] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--maintain-map] [--ate] [--rpe]]\n", argv0);
+	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--angular-velocity] [--depth-map] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--maintain-map] [--ate] [--rpe]]\n", argv0);
 	return 2;
 }
 
@@ -77,6 +84,7 @@ int main(int argc, char** argv)
 	size_t windowBatch = 1;
 	bool rectify = false, rectifyFrames = false;
 	bool angularVelocity = false;
+	bool depthMap = false;
 	bool trackError = false;
 	double trackErrorThreshold = 5.0;
 	bool odometry = false, bundleAdjust = false, refine = false, refineTwoView = false, maintainMap = false, ate = false, rpe = false;
@@ -106,6 +114,10 @@ int main(int argc, char** argv)
 		else if (a == "--angular-velocity")
 		{
 			angularVelocity = true;
+		}
+		else if (a == "--depth-map")
+		{
+			depthMap = true;
 		}
 		else if (a == "--odometry")
 		{
@@ -181,12 +193,12 @@ int main(int argc, char** argv)
 		p.windowBatch = windowBatch;
 		const auto recording = std::make_shared<tools::Davis240cRecording>(dataset);
 		common::GroundTruth groundTruth;
-		if (ate || rpe)
+		if (ate || rpe || depthMap)
 		{
 			groundTruth = recording->getGroundTruth();
 			if (groundTruth.empty())
 			{
-				throw std::runtime_error("--ate and --rpe need " + dataset + "/groundtruth.txt with at least one sample");
+				throw std::runtime_error("--ate, --rpe and --depth-map need " + dataset + "/groundtruth.txt with at least one sample");
 			}
 		}
 		if (rectify)
@@ -205,7 +217,15 @@ int main(int argc, char** argv)
 			p.cameraModelParams = recording->getCalibration();
 			p.estimateAngularVelocity = true;
 		}
-		size_t events = 0, frames = 0, tracks = 0, windows = 0, keyframes = 0, landmarks = 0;
+		if (depthMap)
+		{
+			p.cameraModelParams = recording->getCalibration();
+			p.depthMap = true;
+			p.depthPoses = groundTruth;
+			p.depthReferenceTime =
+				common::timestamp_t((groundTruth.front().timestamp.count() + groundTruth.back().timestamp.count()) / 2);
+		}
+		size_t events = 0, frames = 0, tracks = 0, windows = 0, keyframes = 0, landmarks = 0, depthPixels = 0, depthWindows = 0;
 		ebo_track_error_summary_result trackSummary{};
 		ebo_ctx* odometryCtx = nullptr;
 		if (odometry)
@@ -280,6 +300,14 @@ int main(int argc, char** argv)
 			events = evaluator.events();
 			windows = evaluator.windows();
 			tracks = evaluator.detector().getArchivedPatches().size();
+			if (depthMap)
+			{
+				depthPixels = evaluator.depthMap().points.size();
+				for (const auto& w : evaluator.depthWindows())
+				{
+					depthWindows += w.used ? 1 : 0;
+				}
+			}
 			if (trackError)
 			{
 				// the file, not the patches: what is judged is what was written, to its printed digits
@@ -448,6 +476,10 @@ int main(int argc, char** argv)
 					frames, events, tracks, windows, ms, frames > 1 ? ms / static_cast<double>(frames - 1) : 0.0,
 					ms > 0 ? static_cast<double>(events) / (ms * 1e3) : 0.0, trackerExperiment ? "true" : "false",
 					windowBatch, rectify ? "true" : "false", odometry ? "true" : "false", keyframes, landmarks);
+		if (depthMap)
+		{
+			std::printf(", \"depth_pixels\": %zu, \"depth_windows\": %zu", depthPixels, depthWindows);
+		}
 		if (trackError)
 		{
 			std::printf(", \"track_error_mean\": %.17g, \"feature_age_mean_s\": %.17g, \"tracks_counted\": %d, \"tracks_discarded\": %d",

@@ -1700,6 +1700,82 @@ void ebo_rot_solver_destroy(ebo_rot_solver* s);
 int ebo_solve_rotation(ebo_ctx* ctx, const ebo_camera* cam, const ebo_rotation_params* params, const ebo_rot_solver_opts* opts,
 					   const double* omega0_or_null, double* omega_out, ebo_rot_summary* summary_or_null);
 
+/* ---- depth from events: space-sweep voting --------------------------------------------------------
+ * A semi-dense depth map of a reference view from the events themselves, with known poses (event-based multi-view
+ * stereo by space sweep): every event is back-projected as a ray through a stack of depth planes of the reference view,
+ * the votes are counted per voxel, and the pixels where rays meet are kept with their depth.  The rules are this
+ * project's own; tests/depth_ref.py restates them in numpy.  All arithmetic is float64; in M2 and M3 every operation is
+ * rounded on its own, in the association written, with no contraction, because they decide integer bits.
+ *
+ * Inputs: the windows resident in the context, loaded by any ebo_set_window* loader (rectified coordinates when a
+ * rectification is set).  The event set is ebo_rotation_image's: events of a window's stray unit take no part, units
+ * count whether active or not; polarity and event time are ignored.  A pinhole camera under rule C1 (k1 k2 p1 p2 all
+ * zero, else EBO_ERR_ARG; fx or fy not finite or zero: EBO_ERR_RANGE).  A reference pose and one pose per window, each
+ * 12 doubles (R row-major, t), camera to world, as in A1, B1 and L1.  Poses are not validated.
+ *
+ * M1. Planes.  2 <= Nz <= 256, 0 < z_near < z_far, both finite, else EBO_ERR_ARG.  rho_0 = 1 / z_near;
+ *     drho = (1 / z_far - rho_0) / (Nz - 1);  rho_k = rho_0 + k * drho;  z_k = 1 / rho_k: uniform in inverse depth, plane
+ *     0 the nearest.  The table is made on the host; the kernels receive it.
+ * M2. Relative pose, on the host per window, Rref / tref the reference pose and Rw / tw the window's:
+ *       Rr[i][j] = (Rref[0][i] * Rw[0][j] + Rref[1][i] * Rw[1][j]) + Rref[2][i] * Rw[2][j];   e = tw - tref;
+ *       tr_i = (Rref[0][i] * e0 + Rref[1][i] * e1) + Rref[2][i] * e2
+ *     Per event at integer pixel (x, y):  a = (x - cx) / fx;  b = (y - cy) / fy;
+ *       d_i = (Rr[i][0] * a + Rr[i][1] * b) + Rr[i][2]
+ * M3. Per event and plane k:  lam = (z_k - tr2) / d2.  If not (lam > 0) there is no vote on this plane.
+ *       X = tr0 + lam * d0;   Y = tr1 + lam * d1;   u = fx * (X / z_k) + cx;   v = fy * (Y / z_k) + cy
+ *     If not (u > -1 and u < w and v > -1 and v < h) there is no vote.  Both tests are made in double before any
+ *     conversion: a NaN or an infinity anywhere, a pose included, reads and writes nothing.
+ * M4. Vote.  The bilinear weights of V3 (x0 = floor(u), y0 = floor(v), al, be, ial, ibe and the four products) each
+ *     become q = rint(weight * 2^10), ties to even, added to the uint32 volume H[k][y][x] at the taps inside the image.
+ *     A volume accepts at most 2^21 events in all, counted as the events of the in-sensor units of the windows a call
+ *     votes, whether or not they reach a plane; a call that would pass that returns EBO_ERR_RANGE with the volume
+ *     unchanged.  With this cap no voxel can overflow.  Integer adds commute: H depends on the set of (event, pose)
+ *     pairs only, not on order, batching, the number of calls or the kernel's design.
+ * M5. Confidence.  c(x, y) = max_k H[k][y][x]; kbest = the smallest k attaining it.  A pixel with c = 0 is never kept.
+ * M6. Adaptive threshold, in integers.  Box radius r in 0 .. 7 (default 2); min_excess in votes, finite and >= 0
+ *     (default 3.0), else EBO_ERR_ARG.  off = rint(min_excess * 2^10) as int64 (a min_excess above 2^22 is taken as
+ *     2^22: c never exceeds 2^31, so either keeps nothing).  S = the sum of c over the box's pixels inside the image,
+ *     cnt their number.  A pixel is kept iff c * cnt > S + off * cnt, in int64.
+ * M7. Median.  Radius m in 0 .. 7 (default 2), else EBO_ERR_ARG; m = 0 turns it off (the plane is kbest).  For a kept
+ *     pixel: the kbest of the kept pixels of its box, itself included, sorted ascending; the pixel's plane is element
+ *     (n - 1) / 2 of that list, the lower median.  The medians are taken from the kbest of M5, not from each other.
+ * M8. Outputs.  The plane index int32 [h][w], -1 for a pixel that is not kept; the confidence c uint32 [h][w]; the depth
+ *     double [h][w], z_k of the pixel's plane and 0.0 where not kept; the point list in row-major pixel order,
+ *     (a * z, b * z, z) in the reference camera frame with a and b as in M2.
+ * M9. Every output is bit-equal to the restatement.
+ *
+ * ebo_dsi_begin: checks camera and parameters (NULL: the defaults), grows the volume to Nz * h * w uint32 and clears
+ *   it.  A begin while a volume is open starts over.
+ * ebo_dsi_add_windows: votes the resident windows, poses [Wn][12]; use_or_null [Wn]: a window with use 0 is left out.
+ *   May be called after every load, and accumulates.
+ * ebo_dsi_volume: H as uint32 [Nz][h][w].
+ * ebo_dsi_depth: M5-M8 of the volume as it stands (it may be called more than once, and voting may go on).  Every
+ *   output may be NULL; points [max_points][3] receives the first max_points kept pixels' points, *n_points_out the
+ *   number of kept pixels (which may exceed max_points).
+ * ebo_dsi_end: closes the volume; its memory stays with the context for the next begin.
+ * Host pointers, synchronous.  Errors: EBO_ERR_STATE without a begin (all but begin), with no windows loaded or units
+ *   loaded by ebo_set_patches (add_windows: begin may come before the first load), and while a graph is being recorded
+ *   (all); EBO_ERR_ARG /
+ *   EBO_ERR_RANGE as in the rules; EBO_ERR_ARG for a needed pointer that is NULL or a negative max_points. */
+typedef struct ebo_depth_params
+{
+	int nz;            /* M1 */
+	int box_radius;    /* M6's r */
+	int median_radius; /* M7's m */
+	int reserved;      /* 0 */
+	double z_near;     /* M1 */
+	double z_far;
+	double min_excess; /* M6, in votes */
+} ebo_depth_params;
+/* nz 64, z_near 0.5, z_far 8, box_radius 2, min_excess 3, median_radius 2 */
+void ebo_default_depth_params(ebo_depth_params* params);
+int ebo_dsi_begin(ebo_ctx* ctx, const ebo_camera* cam, const double* ref_pose, const ebo_depth_params* params_or_null);
+int ebo_dsi_add_windows(ebo_ctx* ctx, const double* poses, const uint8_t* use_or_null);
+int ebo_dsi_volume(ebo_ctx* ctx, uint32_t* out);
+int ebo_dsi_depth(ebo_ctx* ctx, int32_t* index_or_null, uint32_t* conf_or_null, double* depth_or_null, double* points_or_null,
+				  int max_points, int* n_points_out);
+int ebo_dsi_end(ebo_ctx* ctx);
+
 /* Device-side timing of everything enqueued between begin and end on the
  * context's stream (hipEvent based). */
 int ebo_timer_begin(ebo_ctx* ctx);
