@@ -1015,6 +1015,29 @@ class Context:
             self._check(f(self._h, _vp(out), C.c_size_t(n.value), C.byref(n)))
         return out
 
+    def unit_extents(self):
+        """diagnostic: the time-extent table as it lies in device memory -> np.int32[units, 258]
+        (status, 0, then (dtMin, dtMax) per source column and per source row; ebo.h: ebo_unit_extents)"""
+        f = lib().ebo_unit_extents
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        n = C.c_size_t()
+        rc = f(self._h, None, C.c_size_t(0), C.byref(n))
+        if rc and not (rc == ERR_ARG and n.value > 0):
+            self._check(rc)
+        out = np.zeros(n.value, dtype=np.int32)
+        if n.value:
+            self._check(f(self._h, _vp(out), C.c_size_t(n.value), C.byref(n)))
+        return out.reshape(-1, 258)
+
+    def box_path_counts(self):
+        """diagnostic, A/B library only: (units whose box came from the event pass, from the table) in the last
+        variance evaluation"""
+        f = lib().ebo_box_path_counts
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        a, b = C.c_uint(), C.c_uint()
+        self._check(f(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def eval_launch_shape(self, want_jac=True):
         """diagnostic: (row tiles per unit, lanes per workgroup, flow sets) of the variance evaluation's launch"""
         v = [C.c_int() for _ in range(3)]

@@ -45,7 +45,16 @@ inline int ab_launch_order()
 	}
 	return std::strcmp(v, "index") == 0 ? 1 : std::strcmp(v, "light") == 0 ? 2 : 0;
 }
+// EBO_EVAL_BOX = events | extents: where k_eval3 and k_solve_independent take a unit's bounding box from -- a pass over
+// its events, or the load's time-extent table where that gives the box exactly (box_extents.h; the default, and always
+// in the shipped build).  Read at every launch.
+inline bool ab_box_from_extents()
+{
+	const char* v = ab_env("EBO_EVAL_BOX");
+	return !(v && std::strcmp(v, "events") == 0);
+}
 }  // namespace ebo_ab
+using ebo_ab::ab_box_from_extents;
 using ebo_ab::ab_env;
 using ebo_ab::ab_launch_order;
 using ebo_ab::ab_size;

@@ -425,6 +425,15 @@ int run_eval_device(ebo_ctx* c, const double* d_flows, int want_jac, double* d_o
 	L.d_events = c->d_events;
 	L.d_units = c->d_units;
 	L.d_order = c->d_order;
+	L.box.ext = ab_box_from_extents() ? c->d_unit_ext.get() : nullptr;
+#ifdef EBO_AB
+	L.box.stats = c->d_box_stats;
+	rc = c->hip(hipMemsetAsync(c->d_box_stats, 0, 2 * sizeof(unsigned int), c->stream), "box path counters");
+	if (rc)
+	{
+		return rc;
+	}
+#endif
 	L.d_flows = d_flows;
 	rc = c->grow(c->d_partials, static_cast<size_t>(L.flow_sets) * L.n_units * L.tiles * kPartialStride, "hipMalloc partials");
 	if (rc)
@@ -881,6 +890,7 @@ int run_solve_device(ebo_ctx* c, const ebo_solver_opts* o, double* d_flows_out, 
 	L.d_events = c->d_events;
 	L.d_units = c->d_units;
 	L.d_order = c->d_order;
+	L.d_unit_ext = ab_box_from_extents() ? c->d_unit_ext.get() : nullptr;
 	L.n_units = static_cast<int>(c->units.size());
 	// k_solve_independent runs three waves per SIMD (152-166 VGPRs since round 3: one next_step() site in the
 	// solver; 205 and two waves before), i.e. 12 waves per CU.  By the canvas of the regular patch, as the
@@ -1375,6 +1385,12 @@ int ebo_create(const ebo_params* p, ebo_ctx** out)
 	if (rc == EBO_OK) rc = c->grow(c->d_events, c->cap_events, what);
 	if (rc == EBO_OK) rc = c->grow(c->d_units, nu, what);
 	if (rc == EBO_OK) rc = c->grow(c->d_order, nu, what);  // (its only allocation: loads check the capacity, never grow it)
+	if (rc == EBO_OK) rc = c->grow(c->d_unit_ext, nu * kExtStride, what);  // (likewise; all zero = no unit has a table)
+	if (rc == EBO_OK) rc = c->hip(hipMemset(c->d_unit_ext, 0, nu * kExtStride * sizeof(int32_t)), what);
+#ifdef EBO_AB
+	if (rc == EBO_OK) rc = c->grow(c->d_box_stats, 2, what);
+	if (rc == EBO_OK) rc = c->hip(hipMemset(c->d_box_stats, 0, 2 * sizeof(unsigned int)), what);
+#endif
 	if (rc == EBO_OK) rc = c->grow(c->d_unit_maxdt, nu, what);
 	if (rc == EBO_OK) rc = c->grow(c->d_flows, nf * 2, what);
 	if (rc == EBO_OK) rc = c->grow(c->d_out, nf * 3, what);

@@ -22,6 +22,7 @@
 #include <thread>
 
 #include "../../include/ebo.h"
+#include "box_extents.h"
 #include "dev_buf.h"
 #include "ebo_internal.h"
 #include "field_tv.h"
@@ -112,6 +113,8 @@ struct ebo_ctx
 	Dev<uint64_t> d_events;
 	Dev<Unit> d_units;
 	Dev<uint32_t> d_order;  // [units] the order in which a launch hands them to workgroups, heaviest first (launch_order.h); rewritten by every load
+	Dev<int32_t> d_unit_ext;  // [units][kExtStride] per-column / per-row time extents behind k_eval3's bounding box (box_extents.h); sized once by ebo_create, rewritten by every load
+	Dev<unsigned int> d_box_stats;  // A/B build only: [2] units whose box came from the event pass / from the table in the last variance evaluation
 	Dev<int32_t> d_unit_maxdt;  // [units] max |t_ref(window) - t| over the unit's events (count kernels' displacement bound)
 	Dev<double> d_flows;
 	Dev<double> d_out;

@@ -109,7 +109,9 @@ template <bool SMALL, bool D1S>
 __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, const Unit& u, double m0,
 											double m1, bool wantJac, int tile, int tiles,
 											int capDoubles, const EvalConsts& c, double* lds,
-											double (&S)[7], EvalReuse* ru = nullptr)
+											double (&S)[7], EvalReuse* ru = nullptr,
+											const int32_t* __restrict__ ext = nullptr,
+											[[maybe_unused]] unsigned int* boxStats = nullptr)
 {
 	EDGE_TICK_DECL;
 	double* red = lds;
@@ -168,6 +170,25 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 	int xmin = 0x7fffffff, xmax = -0x7fffffff, ymin = 0x7fffffff, ymax = -0x7fffffff;
 	if (!reuse)
 	{
+	// The box from the unit's time extents where they give it exactly (box_extents.h, ebo_extents.inc; ext: the unit's
+	// slot, or null), else by a pass over the events.  Uniform over the workgroup: slot and flow alone decide.
+	// With the table, the scatter would be the first to ask for the events, behind two barriers and the zeroing of
+	// the image: the workgroup's first records are asked for HERE, beside the slot, and only waited for (their
+	// cache lines are what is wanted, not their values: the scatter loads them again, from the cache).
+	// (k_eval3 only: of a solve's evaluations only the first finds the events cold)
+	uint64_t warm = 0;
+	if (D1S && ext && threadIdx.x < nEv)
+	{
+		warm = ev[threadIdx.x];
+	}
+	const bool tabled = ext && box_from_extents(ext, rx, ry, rw, rh, m0, m1, c, xmin, xmax, ymin, ymax);
+	if (tabled)
+	{
+		asm volatile("" ::"v"(warm));
+		__syncthreads();  // what block_minmax's last barrier is relied on for below: red and ru are read no more
+	}
+	else
+	{
 	for_each_event([&](uint64_t rec) {
 		int pxc, pyc;
 		double fx, fy, tau;
@@ -180,9 +201,16 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 		}
 	});
 	block_minmax(xmin, xmax, ymin, ymax, ired);
+	}
+#ifdef EBO_AB
+	if (boxStats && threadIdx.x == 0 && tile == 0)
+	{
+		atomicAdd(&boxStats[tabled ? 1 : 0], 1u);  // ebo_box_path_counts
+	}
+#endif
 	if (ru && threadIdx.x == 0)
 	{
-		ru->valid = 0.0;  // the image is about to be rebuilt (every thread has read the record: block_minmax's barriers)
+		ru->valid = 0.0;  // the image is about to be rebuilt (every thread has read the record: the barriers above)
 	}
 	}
 	EDGE_TICK(16);
@@ -208,7 +236,7 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 #pragma unroll
 		for (int k = 0; k < 7; ++k)
 		{
-			slot[k] = 0.0;  // block_minmax ended with a barrier: nobody reads red any more
+			slot[k] = 0.0;  // the box ended with a barrier on either path: nobody reads red any more
 		}
 	}
 	int x0 = max(xmin - 3, 0), x1 = min(xmax + 3, W3 - 1);
@@ -624,7 +652,7 @@ __global__ void __launch_bounds__(512, SMALL ? 4 : 3) k_eval3(const uint64_t* __
 												int capDoubles, double fdStep, double* __restrict__ partials,
 												double* __restrict__ out, EvalConsts c,
 												const unsigned char* __restrict__ modes, LiveWindows live,
-												const uint32_t* __restrict__ order)
+												const uint32_t* __restrict__ order, BoxTable box)
 {
 	extern __shared__ double lds[];
 	int unit = blockIdx.x / tiles;
@@ -677,7 +705,10 @@ __global__ void __launch_bounds__(512, SMALL ? 4 : 3) k_eval3(const uint64_t* __
 	double m1 = flows[2 * u.flow_idx + 1];
 	fd_offset(set, fdStep, m0, m1);
 	double S[7];
-	eval_unit3<SMALL, true>(events + u.ev_off, u, m0, m1, wantJac != 0, tile, tiles, capDoubles, c, lds, S);
+	// (the slot is the unit's, not the workgroup's: scalar address, scalar status)
+	const int32_t* ext = box.ext ? box.ext + static_cast<size_t>(unit) * kExtStride : nullptr;
+	eval_unit3<SMALL, true>(events + u.ev_off, u, m0, m1, wantJac != 0, tile, tiles, capDoubles, c, lds, S, nullptr, ext,
+							set == 0 ? box.stats : nullptr);
 	if (threadIdx.x == 0)
 	{
 		if (fused)

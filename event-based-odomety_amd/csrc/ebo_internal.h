@@ -117,6 +117,13 @@ struct LiveWindows
 // Per-block partial sums of the variance objective: S1, S2, n, D1[2], D2[2], pad.
 static const int kPartialStride = 8;
 
+// The per-unit time-extent table of a load (box_extents.h), as an evaluation's launch sees it.
+struct BoxTable
+{
+	const int32_t* ext = nullptr;   // [units][kExtStride], or null: every unit's box by the event pass (A/B: EBO_EVAL_BOX=events)
+	unsigned int* stats = nullptr;  // A/B build only: DEVICE counters [2] of ebo_box_path_counts, else null
+};
+
 // ---- launch wrappers implemented in ebo_kernels.hip (hipStream_t as void*) ----
 struct EvalLaunch
 {
@@ -137,9 +144,12 @@ struct EvalLaunch
 	double fd_step;        // > 0: combine as central differences
 	const unsigned char* d_modes = nullptr;  // per flow slot: 0 skip, 1 value, 2 value + Jacobian (tiles == 1, one flow set)
 	LiveWindows live;      // n > 0: only these windows (tiles == 1, one flow set)
+	BoxTable box;
 	EvalConsts c;
 };
 int launch_eval_variance(const EvalLaunch& L, void* stream);
+// k_unit_extents over units [0, n_units): rewrites their slots of d_unit_ext from the resident events and units
+int launch_unit_extents(const uint64_t* d_events, const Unit* d_units, int n_units, int32_t* d_unit_ext, void* stream);
 int launch_dump_image(const EvalLaunch& L, int unit, double* d_image, void* stream);
 
 // Edge (structure-tensor) loss, contrast_functor.h:152-277.
@@ -241,6 +251,7 @@ struct SolveLaunch
 	const uint64_t* d_events;
 	const Unit* d_units;
 	const uint32_t* d_order = nullptr;  // [n_units] launch order of the units (launch_order.h)
+	const int32_t* d_unit_ext = nullptr;  // BoxTable::ext
 	int n_units;
 	int cap_doubles;
 	int block;

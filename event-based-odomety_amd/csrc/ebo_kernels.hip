@@ -23,6 +23,7 @@
 #include <type_traits>
 #include <cstdlib>
 
+#include "box_extents.h"
 #include "ebo_internal.h"
 #include "exp_taps.h"
 
@@ -575,6 +576,7 @@ __global__ void k_dump_image(const uint64_t* __restrict__ events, const Unit* __
 // feature_detector.cpp:401-410.  Every thread carries the (uniform) solver state;
 // the objective is evaluated cooperatively.  No host round trips.
 // ---------------------------------------------------------------------------
+#include "ebo_extents.inc"
 #include "ebo_eval3.inc"
 
 // The objective and its Jacobian at (m0, m1) of a unit evaluated as one row band.  (A function of its own: written
@@ -582,10 +584,10 @@ __global__ void k_dump_image(const uint64_t* __restrict__ events, const Unit* __
 template <bool SMALL>
 __device__ __forceinline__ void eval_unit(const uint64_t* __restrict__ ev, const Unit& u, double m0, double m1,
 										   bool wantJac, int capDoubles, const EvalConsts& c, double* lds, double& r,
-										   double& j0, double& j1, EvalReuse* ru)
+										   double& j0, double& j1, EvalReuse* ru, const int32_t* __restrict__ ext)
 {
 	double S[7];
-	eval_unit3<SMALL, false>(ev, u, m0, m1, wantJac, 0, 1, capDoubles, c, lds, S, ru);  // (the gather forms D1: ebo_eval3.inc)
+	eval_unit3<SMALL, false>(ev, u, m0, m1, wantJac, 0, 1, capDoubles, c, lds, S, ru, ext);  // (the gather forms D1: ebo_eval3.inc)
 	j0 = 0.0;
 	j1 = 0.0;
 	variance_from_sums(S, wantJac, m0, m1, c.max_res, r, j0, j1);
@@ -867,10 +869,13 @@ template <bool SMALL>
 __global__ void __launch_bounds__(512) k_solve_independent(const uint64_t* __restrict__ events,
 									const Unit* __restrict__ units, int capDoubles,
 									double* __restrict__ flowsOut, int32_t* __restrict__ stats,
-									EvalConsts c, SolveConsts o, int noReuse, const uint32_t* __restrict__ order)
+									EvalConsts c, SolveConsts o, int noReuse, const uint32_t* __restrict__ order,
+									const int32_t* __restrict__ unitExt)
 {
 	extern __shared__ double lds[];
-	const Unit u = units[order[blockIdx.x]];  // heaviest first (launch_order.h): n_ev is the known part of a solve's length
+	const uint32_t unit = order[blockIdx.x];  // heaviest first (launch_order.h): n_ev is the known part of a solve's length
+	const Unit u = units[unit];
+	const int32_t* ext = unitExt ? unitExt + static_cast<size_t>(unit) * kExtStride : nullptr;  // box_extents.h
 	const uint64_t* ev = events + u.ev_off;
 	int iteration = 0, evalsCost = 0, evalsJac = 0, termination = 0;
 	double best0 = 0.0, best1 = 0.0;
@@ -905,7 +910,7 @@ __global__ void __launch_bounds__(512) k_solve_independent(const uint64_t* __res
 			const double q0 = lm.q0, q1 = lm.q1;
 			const bool qJac = lm.qJac;
 			double r, a, b;
-			eval_unit<SMALL>(ev, u, q0, q1, qJac, capDoubles, c, lds, r, a, b, ru);
+			eval_unit<SMALL>(ev, u, q0, q1, qJac, capDoubles, c, lds, r, a, b, ru, ext);
 			if (threadIdx.x == 0)
 			{
 				lm.more = lm.advance(r, a, b, o) ? 1 : 0;
@@ -1318,6 +1323,16 @@ int allow_big_lds(K kernel, size_t bytes)
 
 }  // namespace
 
+int launch_unit_extents(const uint64_t* d_events, const Unit* d_units, int n_units, int32_t* d_unit_ext, void* stream)
+{
+	if (n_units == 0)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_unit_extents, dim3(n_units), dim3(256), 0, static_cast<hipStream_t>(stream), d_events, d_units, d_unit_ext);
+	return check_launch();
+}
+
 int launch_eval_variance(const EvalLaunch& L, void* stream)
 {
 	hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1343,7 +1358,7 @@ int launch_eval_variance(const EvalLaunch& L, void* stream)
 	}
 	hipLaunchKernelGGL(kern, live.n > 0 ? dim3(live.n * live.upw) : grid, dim3(L.block), L.lds_bytes, s, L.d_events, L.d_units,
 					   L.d_flows, L.tiles, L.channels == 3 ? 1 : 0, L.cap_doubles, L.fd_step,
-					   L.d_partials, L.d_out, L.c, fusedPath ? L.d_modes : nullptr, live, L.d_order);
+					   L.d_partials, L.d_out, L.c, fusedPath ? L.d_modes : nullptr, live, L.d_order, L.box);
 	if (check_launch())
 	{
 		return -2;
@@ -2423,7 +2438,7 @@ int launch_solve_independent(const SolveLaunch& L, void* stream)
 		return -2;
 	}
 	hipLaunchKernelGGL(kern, dim3(L.n_units), dim3(L.block), L.lds_bytes, s, L.d_events,
-					   L.d_units, L.cap_doubles, L.d_flows_out, L.d_stats, L.c, L.s, ab_env("EBO_SOLVE_NO_REUSE") ? 1 : 0, L.d_order);
+					   L.d_units, L.cap_doubles, L.d_flows_out, L.d_stats, L.c, L.s, ab_env("EBO_SOLVE_NO_REUSE") ? 1 : 0, L.d_order, L.d_unit_ext);
 	return check_launch();
 }
 

@@ -34,6 +34,10 @@ void canonical_order(uint64_t* p, uint32_t n)
 // writes before the next load's synchronisation, marks the copy with order_done and returns -- everything that reads the
 // table is ordered behind the copy on the same stream (ebo_set_stream waits for the mark before it changes streams).
 // d_order is sized with d_units by ebo_create and never moves: a recorded graph holds its address.
+//
+// Behind it on the same stream, k_unit_extents rewrites the time-extent table of the same units (box_extents.h) from the
+// resident d_events and d_units, which every path has put on the stream before it comes here: one place for the host
+// load, the device bucketing and ebo_set_patches, and for whatever reaches them.  d_unit_ext never moves either.
 int upload_launch_order(ebo_ctx* c, const std::vector<Unit>& units, uint32_t* staging)
 {
 	if (units.empty())
@@ -46,8 +50,17 @@ int upload_launch_order(ebo_ctx* c, const std::vector<Unit>& units, uint32_t* st
 	}
 	fill_launch_order(&units[0].n_ev, &units[0].flags, sizeof(Unit), units.size(), kUnitActive, staging,
 					  static_cast<LaunchOrderKind>(ab_launch_order()));
-	return c->hip(hipMemcpyAsync(c->d_order, staging, units.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream),
-				  "H2D launch order");
+	int rc = c->hip(hipMemcpyAsync(c->d_order, staging, units.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream),
+					"H2D launch order");
+	if (rc == EBO_OK && units.size() * kExtStride > c->d_unit_ext.cap())
+	{
+		rc = c->fail(EBO_ERR_STATE, "more units than the context's time-extent table holds");
+	}
+	if (rc == EBO_OK && launch_unit_extents(c->d_events, c->d_units, static_cast<int>(units.size()), c->d_unit_ext, c->stream))
+	{
+		rc = c->hip(hipGetLastError(), "unit extents launch");
+	}
+	return rc;
 }
 }  // namespace
 
@@ -953,6 +966,62 @@ int ebo_launch_order(ebo_ctx* c, uint32_t* out, size_t cap, size_t* n)
 		rc = c->hip(hipMemcpy(out, c->d_order.get(), *n * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H launch order");
 	}
 	return rc;
+}
+
+int ebo_unit_extents(ebo_ctx* c, int32_t* out, size_t cap, size_t* n)
+{
+	if (!c)
+	{
+		return EBO_ERR_ARG;
+	}
+	if (c->capturing)
+	{
+		return c->fail(EBO_ERR_STATE, kNotWhileRecording);
+	}
+	if (!n || c->n_windows == 0)
+	{
+		return c->fail(EBO_ERR_ARG, "ebo_unit_extents: nothing loaded, or a null count");
+	}
+	*n = c->units.size() * kExtStride;
+	if (*n > cap || (*n && !out))
+	{
+		return c->fail(EBO_ERR_ARG, "ebo_unit_extents: the table holds more entries than cap (*n says how many)");
+	}
+	(void)hipSetDevice(c->prm.device);
+	int rc = c->hip(hipStreamSynchronize(c->stream), "sync before the table read-back");
+	if (rc == EBO_OK && *n)
+	{
+		rc = c->hip(hipMemcpy(out, c->d_unit_ext.get(), *n * sizeof(int32_t), hipMemcpyDeviceToHost), "D2H unit extents");
+	}
+	return rc;
+}
+
+int ebo_box_path_counts(ebo_ctx* c, unsigned int* from_events, unsigned int* from_extents)
+{
+	if (!c)
+	{
+		return EBO_ERR_ARG;
+	}
+	if (c->capturing)
+	{
+		return c->fail(EBO_ERR_STATE, kNotWhileRecording);
+	}
+#ifdef EBO_AB
+	unsigned int v[2] = {0, 0};
+	(void)hipSetDevice(c->prm.device);
+	int rc = c->hip(hipStreamSynchronize(c->stream), "sync before the counter read-back");
+	if (rc == EBO_OK)
+	{
+		rc = c->hip(hipMemcpy(v, c->d_box_stats.get(), sizeof(v), hipMemcpyDeviceToHost), "D2H box path counters");
+	}
+	if (from_events) *from_events = v[0];
+	if (from_extents) *from_extents = v[1];
+	return rc;
+#else
+	(void)from_events;
+	(void)from_extents;
+	return c->fail(EBO_ERR_STATE, "ebo_box_path_counts: counted in the A/B build only");
+#endif
 }
 
 }  // extern "C"

@@ -455,6 +455,19 @@ int ebo_unit_records(ebo_ctx* ctx, int window, int bucket, uint64_t* out, size_t
  * then); EBO_ERR_STATE while a graph is being recorded.  Synchronous; changes nothing. */
 int ebo_launch_order(ebo_ctx* ctx, uint32_t* out, size_t cap, size_t* n);
 
+/* Diagnostic (tests/test_gpu_box_extents.py): the time-extent table behind the variance evaluation's bounding box as it
+ * lies in device memory -- per unit (index as in ebo_launch_order) a slot of 258 int32: status (1 valid, 0 no table: stray
+ * bucket, rect wider or taller than 64, or an event outside the rect) | 0 | (dtMin, dtMax) of source columns 0 .. rw-1 |
+ * of source rows 0 .. rh-1, dt = int32(t_ref(unit) - t); an empty column or row, and every pair behind the last row,
+ * holds (INT32_MAX, INT32_MIN).  *n receives the number of int32.  Errors as ebo_launch_order.  Synchronous; changes
+ * nothing. */
+int ebo_unit_extents(ebo_ctx* ctx, int32_t* out, size_t cap, size_t* n);
+
+/* Diagnostic, A/B build only (same test): of the units the last ebo_eval / ebo_eval_device variance evaluation evaluated
+ * (first flow set), how many took their bounding box from a pass over their events and how many from the table.  Either
+ * pointer may be null.  EBO_ERR_STATE in the shipped build and while a graph is being recorded.  Synchronous. */
+int ebo_box_path_counts(ebo_ctx* ctx, unsigned int* from_events, unsigned int* from_extents);
+
 /* Diagnostic (same test): the shape ebo_eval / ebo_eval_device give the variance evaluation of the loaded units -- row
  * tiles per unit, lanes per workgroup, flow sets (5 with EBO_GRAD_CENTRAL and a Jacobian, else 1).  Any pointer may be
  * null.  Launches nothing.  EBO_ERR_STATE with nothing loaded or the edge loss. */
