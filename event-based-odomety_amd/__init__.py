@@ -264,6 +264,40 @@ def default_ba_opts(**over):
     return o
 
 
+class MapTrackResult(C.Structure):
+    """ebo_map_track_result: one unit's answer (rules E1-E9)."""
+    _fields_ = [("termination", C.c_int32), ("iterations", C.c_int32), ("num_evals_jac", C.c_int32), ("num_evals_cost", C.c_int32),
+                ("visible_start", C.c_int32), ("visible_final", C.c_int32), ("reserved0", C.c_int32), ("reserved1", C.c_int32),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double), ("scale", C.c_double), ("reserved2", C.c_double)]
+
+
+MAP_TRACK_FIELDS = ("termination", "iterations", "num_evals_jac", "num_evals_cost", "visible_start", "visible_final", "initial_cost",
+                    "final_cost", "scale")
+MAP_TRACK_DTYPE = np.dtype([(f, "<i4") for f in ("termination", "iterations", "num_evals_jac", "num_evals_cost", "visible_start",
+                                                  "visible_final", "reserved0", "reserved1")] +
+                           [(f, "<f8") for f in ("initial_cost", "final_cost", "scale", "reserved2")])
+
+
+def default_map_track_opts(**over):
+    """ebo_default_map_track_opts as a SolverOpts; keyword arguments override fields."""
+    o = SolverOpts()
+    lib().ebo_default_map_track_opts(C.addressof(o))
+    for k, v in over.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def map_track_starts(pose, translation_step, rotation_step):
+    """ebo_map_track_starts: pose [12] -> the 13 starts [13][12] of a multi-start (the pose, then +- a step along each of
+    B4's six update directions)."""
+    p = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+    out = np.zeros((13, 12))
+    lib().ebo_map_track_starts(_dp(p), C.c_double(translation_step), C.c_double(rotation_step), _dp(out))
+    return out
+
+
 class Camera(C.Structure):
     """ebo_camera: common::CameraModelParams<double>, in its field order."""
     _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "k3", "p1", "p2")]
@@ -389,6 +423,18 @@ def lib():
         _lib.ebo_eval_rotation_device.argtypes = [C.c_void_p] * 6
         _lib.ebo_rotation_image.argtypes = [C.c_void_p] * 5
         _lib.ebo_solve_rotation.argtypes = [C.c_void_p] * 7
+        _lib.ebo_event_images.argtypes = [C.c_void_p] * 5
+        _lib.ebo_event_images_device.argtypes = [C.c_void_p] * 5
+        _lib.ebo_default_map_track_opts.argtypes = [C.c_void_p]
+        _lib.ebo_default_map_track_opts.restype = None
+        _mt = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+               C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ebo_map_track.argtypes = _mt
+        _lib.ebo_map_track_device.argtypes = _mt
+        _lib.ebo_map_track_starts.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_void_p]
+        _lib.ebo_map_track_starts.restype = None
+        _lib.ebo_map_track_resident.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.ebo_rot_solver_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.ebo_rot_solver_request.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.ebo_rot_solver_supply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1911,6 +1957,80 @@ class Context:
         self._check(lib().ebo_solve_rotation(self._h, C.addressof(k), C.addressof(prm), C.byref(opts) if opts is not None else None,
                                              _dp(o0) if o0 is not None else None, _dp(out), summ))
         return out, list(summ)
+
+    # -- pose from events against a map (map-to-event-image alignment, rules E1-E9) ------------------------
+    def event_images(self, cam, omegas=None, params=None):
+        """ebo_event_images: the blurred event image B float64 [Wn][h][w] of every resident window at omegas [Wn][3]
+        (None: zeros, the un-warped count image blurred)."""
+        k, prm = self._rot_args(cam, params)
+        om = None if omegas is None else np.ascontiguousarray(omegas, dtype=np.float64).reshape(self.n_windows, 3)
+        out = np.zeros((self.n_windows, self.params.image_h, self.params.image_w))
+        self._check(lib().ebo_event_images(self._h, C.addressof(k), C.addressof(prm), _dp(om) if om is not None else None, _dp(out)))
+        return out
+
+    def event_images_device(self, cam, d_images, d_omegas=0, params=None):
+        """ebo_event_images_device: device pointers as int; asynchronous on the context's stream."""
+        k, prm = self._rot_args(cam, params)
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        self._check(lib().ebo_event_images_device(self._h, C.addressof(k), C.addressof(prm), p(d_omegas), p(d_images)))
+
+    def map_track(self, cam, images, points, unit_image, poses, z_min=0.05, opts=None, trace=False):
+        """ebo_map_track: images float64 [n][h][w], points [P][3], unit_image int [U], poses [U][12] (camera to world, R
+        row-major, then t) -> (poses [U][12], list of result dicts, trace [U][max_num_iterations + 1][4] or None)."""
+        o = opts if opts is not None else default_map_track_opts()
+        k = camera(cam)
+        im = np.ascontiguousarray(images, dtype=np.float64)
+        assert im.ndim == 3, im.shape
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        ui = np.ascontiguousarray(unit_image, dtype=np.int32).reshape(-1)
+        po = np.array(poses, dtype=np.float64).reshape(-1, 12)
+        n = len(ui)
+        if len(po) != n:
+            raise ValueError("one pose per unit")
+        res = (MapTrackResult * max(n, 1))()
+        tr = np.zeros((max(n, 1), int(o.max_num_iterations) + 1, 4)) if trace else None
+        self._check(lib().ebo_map_track(self._h, C.addressof(k), im.shape[2], im.shape[1], im.shape[0], _dp(im) if im.size else None,
+                                        len(pts), _dp(pts) if len(pts) else None, n, _vp(ui) if n else None, _dp(po) if n else None,
+                                        C.c_double(z_min), C.addressof(o), C.addressof(res), _dp(tr) if trace else None))
+        out = [{f: getattr(res[u], f) for f in MAP_TRACK_FIELDS} for u in range(n)]
+        return po, out, (tr[:n] if trace else None)
+
+    def map_track_resident(self, cam, points, unit_window, poses, make_images=True, omegas=None, params=None, z_min=0.05, opts=None,
+                           trace=False):
+        """ebo_map_track_resident: map_track against the blurred event images of the RESIDENT windows, which are made on the
+        device (make_images) and kept there for later calls; unit_window names a resident window per unit."""
+        o = opts if opts is not None else default_map_track_opts()
+        k, prm = self._rot_args(cam, params)
+        om = None if omegas is None else np.ascontiguousarray(omegas, dtype=np.float64).reshape(self.n_windows, 3)
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        ui = np.ascontiguousarray(unit_window, dtype=np.int32).reshape(-1)
+        po = np.array(poses, dtype=np.float64).reshape(-1, 12)
+        n = len(ui)
+        res = (MapTrackResult * max(n, 1))()
+        tr = np.zeros((max(n, 1), int(o.max_num_iterations) + 1, 4)) if trace else None
+        self._check(lib().ebo_map_track_resident(self._h, C.addressof(k), C.addressof(prm), _dp(om) if om is not None else None,
+                                                 1 if make_images else 0, len(pts), _dp(pts) if len(pts) else None, n,
+                                                 _vp(ui) if n else None, _dp(po) if n else None, C.c_double(z_min), C.addressof(o),
+                                                 C.addressof(res), _dp(tr) if trace else None))
+        out = [{f: getattr(res[u], f) for f in MAP_TRACK_FIELDS} for u in range(n)]
+        return po, out, (tr[:n] if trace else None)
+
+    def map_track_device(self, cam, w, h, n_images, d_images, n_points, d_points, n_units, d_unit_image, d_poses, d_results,
+                         z_min=0.05, opts=None, d_trace=0):
+        """ebo_map_track_device: device pointers as int; poses are updated in place, d_results receives n_units
+        ebo_map_track_result records (MAP_TRACK_DTYPE, 64 bytes each).  Asynchronous on the context's stream."""
+        o = opts if opts is not None else default_map_track_opts()
+        k = camera(cam)
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        self._check(lib().ebo_map_track_device(self._h, C.addressof(k), int(w), int(h), int(n_images), p(d_images), int(n_points),
+                                               p(d_points), int(n_units), p(d_unit_image), p(d_poses), C.c_double(z_min),
+                                               C.addressof(o), p(d_results), p(d_trace)))
+
+    @staticmethod
+    def map_track_results(raw):
+        """The bytes of ebo_map_track_result records copied back from the device -> list of result dicts."""
+        a = np.ascontiguousarray(raw, dtype=np.uint8).reshape(-1).view(MAP_TRACK_DTYPE)
+        return [{f: a[f][u].item() for f in MAP_TRACK_FIELDS} for u in range(len(a))]
 
     # -- depth from events (space-sweep voting, rules M1-M9) --------------------------------------------------
     def dsi_begin(self, cam, ref_pose, params=None):

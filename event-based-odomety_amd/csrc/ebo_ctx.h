@@ -176,6 +176,11 @@ struct ebo_ctx
 
 	Dev<void> d_rot;  // ebo_rotation.cpp: a chunk's three images and folds (RotScratch)
 	Dev<double> d_rot_io;  // its host entries' omegas [Wn][3], r [Wn], g [Wn][3]
+	Dev<double> d_evimg_om;  // ebo_event_images: zeros [Wn][3] standing in for omegas that are NULL
+	Dev<double> d_evimg;  // ebo_map_track_resident: B [Wn][h][w] of the resident windows, kept between its calls
+	uint64_t evimg_gen = 0;  // units_gen they were made for (0: none)
+	int evimg_windows = 0;
+	Dev<void> d_maptrack;  // ebo_maptrack.cpp: the host form's images, points, unit images, poses, results and trace
 
 	// ebo_depth.cpp: the space-sweep volume between ebo_dsi_begin and ebo_dsi_end
 	Dev<uint32_t> d_dsi;  // H [nz][h][w]

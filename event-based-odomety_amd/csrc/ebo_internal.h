@@ -20,6 +20,7 @@
 #include "ebo_landmark.h"
 #include "ebo_rotation.h"
 #include "ebo_depth.h"
+#include "ebo_maptrack.h"
 
 namespace ebo
 {
@@ -597,6 +598,16 @@ int launch_rot_votes(const uint64_t* d_events, const Unit* d_units, const RotWin
 // r (and g unless d_g is null) of the chunk's windows into d_r[win] / d_g[win][3]
 int launch_rot_eval(const uint64_t* d_events, const Unit* d_units, const RotWindows& L, const RotConsts& k, const double* d_omegas,
 					const RotScratch& s, double* d_r, double* d_g, void* stream);
+
+// V5's blur B of V4's image of the chunk's windows into d_B ([slots][h][w]): the vote and the two passes of
+// launch_rot_eval, nothing else (s.imgX and s.imgY are overwritten)
+int launch_rot_images(const uint64_t* d_events, const Unit* d_units, const RotWindows& L, const RotConsts& k, const double* d_omegas,
+					  const RotScratch& s, double* d_B, void* stream);
+
+// pose from events against a map (ebo_maptrack.inc, ebo_maptrack.cpp): unit u aligns k.points to image d_unit_image[u]
+// from d_poses[u] ([12], updated in place); d_trace may be null
+int launch_map_track(const MtCall& k, int n_units, const int* d_unit_image, double* d_poses, const ebo_solver_opts& o,
+					 ebo_map_track_result* d_results, double* d_trace, void* stream);
 
 // depth from events by space sweep (ebo_depth.inc, ebo_depth.cpp; DsiWindows, DsiConsts, DsiPose: ebo_depth.h).
 // the votes of one chunk of windows (slot s is window win[s], BY VALUE as RotWindows is) into the volume d_H [nz][h][w];

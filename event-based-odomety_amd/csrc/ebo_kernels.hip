@@ -1296,6 +1296,7 @@ __global__ void __launch_bounds__(64) k_route(const uint32_t* __restrict__ xy, u
 #include "ebo_landmark.inc"
 #include "ebo_rotation.inc"
 #include "ebo_depth.inc"
+#include "ebo_maptrack.inc"
 #include "ebo_field.inc"
 #include "ebo_fieldtv.inc"
 #include "ebo_optimizer.inc"
@@ -2137,6 +2138,38 @@ int launch_rot_eval(const uint64_t* d_events, const Unit* d_units, const RotWind
 	}
 	hipLaunchKernelGGL(k_rot_finish, dim3(L.n), dim3(64), 0, st, L, k, nb, static_cast<const double*>(s.partV),
 					   static_cast<const double*>(s.partG), d_r, d_g);
+	return check_launch();
+}
+
+int launch_rot_images(const uint64_t* d_events, const Unit* d_units, const RotWindows& L, const RotConsts& k, const double* d_omegas,
+					  const RotScratch& s, double* d_B, void* stream)
+{
+	if (L.n <= 0)
+	{
+		return 0;
+	}
+	if (launch_rot_votes(d_events, d_units, L, k, d_omegas, s, nullptr, stream))
+	{
+		return -2;
+	}
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	const dim3 px(rot_blocks(k.w, k.h), L.n), blk(kRotBlock);
+	hipLaunchKernelGGL((k_rot_hpass<false, true>), px, blk, 0, st, k, static_cast<const void*>(s.imgX), static_cast<const double*>(nullptr),
+					   s.imgY, static_cast<double*>(nullptr));
+	hipLaunchKernelGGL((k_rot_vpass<false>), px, blk, 0, st, k, static_cast<const double*>(s.imgY), d_B, static_cast<double*>(nullptr));
+	return check_launch();
+}
+
+// pose from events against a map (ebo_maptrack.inc): one workgroup per unit
+int launch_map_track(const MtCall& k, int n_units, const int* d_unit_image, double* d_poses, const ebo_solver_opts& o,
+					 ebo_map_track_result* d_results, double* d_trace, void* stream)
+{
+	if (n_units <= 0)
+	{
+		return 0;
+	}
+	hipLaunchKernelGGL(k_map_track, dim3(n_units), dim3(kMtLanes), 0, static_cast<hipStream_t>(stream), k, d_unit_image, d_poses, o,
+					   d_results, d_trace);
 	return check_launch();
 }
 

@@ -299,6 +299,91 @@ int ebo_rotation_image(ebo_ctx* c, const ebo_camera* cam, const double* omegas, 
 	return c->hip(e, "rotation image");
 }
 
+// B of every resident window, chunk by chunk: to dB ([Wn][h][w], device) or, with hostArrays through the chunk's
+// third image to the host array
+static int event_images(ebo_ctx* c, const char* entry, const ebo_camera* cam, const ebo_rotation_params* prm, const double* omegas,
+						bool hostArrays, double* out, bool hostOmegas)
+{
+	RotConsts k;
+	int rc = prepare(c, entry, cam, prm, out != nullptr, k);
+	if (rc)
+	{
+		return rc;
+	}
+	const size_t Wn = static_cast<size_t>(c->n_windows), np = static_cast<size_t>(k.w) * k.h;
+	const double* dOm = omegas;
+	if (!omegas || hostOmegas)
+	{
+		rc = c->grow(c->d_evimg_om, 3 * Wn, "hipMalloc event-image omegas");
+		if (rc)
+		{
+			return rc;
+		}
+		const hipError_t e = omegas ? hipMemcpyAsync(c->d_evimg_om.get(), omegas, 3 * Wn * sizeof(double), hipMemcpyHostToDevice, c->stream)
+									: hipMemsetAsync(c->d_evimg_om.get(), 0, 3 * Wn * sizeof(double), c->stream);
+		if (e != hipSuccess)
+		{
+			return c->hip(e, "event-image omegas");
+		}
+		dOm = c->d_evimg_om.get();
+	}
+	const int slots = chunk_slots(c, c->n_windows);
+	const RotCarve cv(slots, k.w, k.h, k.P);
+	rc = c->grow(c->d_rot, cv.bytes, "hipMalloc rotation scratch");
+	if (rc)
+	{
+		return rc;
+	}
+	const RotScratch s = cv.at(c->d_rot.get());
+	hipError_t e = hipSuccess;
+	for (int at = 0; at < c->n_windows && e == hipSuccess; at += slots)
+	{
+		RotWindows L;
+		L.n = std::min(slots, c->n_windows - at);
+		for (int i = 0; i < L.n; ++i)
+		{
+			L.win[i] = at + i;
+		}
+		if (launch_rot_images(c->d_events, c->d_units, L, k, dOm, s, hostArrays ? s.imgZ : out + at * np, c->stream))
+		{
+			return c->hip(hipGetLastError(), "event-image kernel launch");
+		}
+		if (hostArrays)
+		{
+			e = hipMemcpyAsync(out + at * np, s.imgZ, static_cast<size_t>(L.n) * np * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+		}
+	}
+	if (e == hipSuccess && hostArrays)
+	{
+		e = hipStreamSynchronize(c->stream);
+	}
+	return c->hip(e, "event images");
+}
+
+int ebo_event_images(ebo_ctx* c, const ebo_camera* cam, const ebo_rotation_params* prm, const double* omegas, double* images)
+{
+	return event_images(c, "ebo_event_images", cam, prm, omegas, true, images, true);
+}
+
+int ebo_event_images_device(ebo_ctx* c, const ebo_camera* cam, const ebo_rotation_params* prm, const double* d_omegas, double* d_images)
+{
+	return event_images(c, "ebo_event_images_device", cam, prm, d_omegas, false, d_images, false);
+}
+
+}  // extern "C"
+
+namespace ebo_host
+{
+// for ebo_map_track_resident (ebo_maptrack.cpp): the omegas on the host, the images left on the device
+int event_images_resident(ebo_ctx* c, const char* entry, const ebo_camera* cam, const ebo_rotation_params* prm, const double* omegas,
+						  double* d_out)
+{
+	return event_images(c, entry, cam, prm, omegas, false, d_out, true);
+}
+}  // namespace ebo_host
+
+extern "C" {
+
 int ebo_rot_solver_create(int n, const ebo_rot_solver_opts* opts, const double* omega0, ebo_rot_solver** out)
 {
 	if (n < 1 || !opts || !out || !RotSolver::optsOk(*opts))

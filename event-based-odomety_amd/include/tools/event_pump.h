@@ -22,6 +22,7 @@
 #include "../feature_tracker/angular_velocity.h"
 #include "../feature_tracker/feature_detector.h"
 #include "../visual_odometry/depth_mapper.h"
+#include "../visual_odometry/map_tracker.h"
 
 namespace tools
 {
@@ -71,6 +72,13 @@ struct EvaluatorParams
 	ebo_depth_params depthParams = visual_odometry::defaultDepthParams();
 	common::GroundTruth depthPoses;
 	common::timestamp_t depthReferenceTime{0};
+	// true (needs depthMap): one pass over the recording maps and then tracks.  Windows whose reference time is before
+	// trackMapSplit are voted into the volume as above; at the first window at or past it the map is extracted, and that
+	// window and every later one is tracked against it (visual_odometry::MapTracker, visual_odometry/map_tracker.h) instead
+	// of voted, chained from depthPoses' pose at the split, with trackStarts (1 or 13) starts a window.
+	bool trackMap = false;
+	common::timestamp_t trackMapSplit{0};
+	int trackStarts = 1;
 };
 
 class EventPump
@@ -154,7 +162,7 @@ class EventPump
 			}
 			if (depth_)
 			{
-				depth_->addResidentWindows(tracker_.handle());
+				voteOrTrack(tracker_.handle());
 			}
 			if (onWindow_)
 			{
@@ -223,7 +231,19 @@ class EventPump
 			int resident = 0;
 			if (batch && ebo_num_windows(batch, &resident) == EBO_OK && resident == static_cast<int>(offsets.size() - 1))
 			{
-				depth_->addResidentWindows(batch);
+				voteOrTrack(batch);
+			}
+			else if (params_.trackMap)
+			{
+				// window by window: a window the loader refuses alone is neither voted nor tracked
+				for (size_t w = 0; w + 1 < offsets.size(); ++w)
+				{
+					const size_t one[2] = {0, offsets[w + 1] - offsets[w]};
+					if (batch && ebo_set_windows(batch, events.data() + offsets[w], one, 1) == EBO_OK)
+					{
+						voteOrTrack(batch);
+					}
+				}
 			}
 			else
 			{
@@ -242,7 +262,13 @@ class EventPump
 			throw std::runtime_error("tools::EventPump: EvaluatorParams::depthMap is not set");
 		}
 		flush();
-		return depth_->finish();
+		return mapTracker_ ? trackedMap_ : depth_->finish();  // trackMap: the map the tracker was given at the split
+	}
+	// EvaluatorParams::trackMap: one entry per tracked window, in order (empty before the split is reached)
+	const std::vector<visual_odometry::MapTrackWindow>& trackedWindows() const
+	{
+		static const std::vector<visual_odometry::MapTrackWindow> none;
+		return mapTracker_ ? mapTracker_->windows() : none;
 	}
 	const std::vector<visual_odometry::DepthWindow>& depthWindows() const
 	{
@@ -306,6 +332,50 @@ class EventPump
 		angularVelocities_.insert(angularVelocities_.end(), est.begin(), est.end());
 	}
 
+	// the windows resident in ctx: voted into the volume, or -- EvaluatorParams::trackMap, from the split on -- tracked
+	void voteOrTrack(ebo_ctx* ctx)
+	{
+		if (!params_.trackMap)
+		{
+			depth_->addResidentWindows(ctx);
+			return;
+		}
+		const int64_t split = params_.trackMapSplit.count();
+		int n = 0, first = 0;
+		if (!ctx || ebo_num_windows(ctx, &n) != EBO_OK)
+		{
+			throw std::runtime_error("tools::EventPump: no context to map or track in");
+		}
+		for (first = 0; first < n; ++first)
+		{
+			int64_t tRef = 0;
+			uint64_t count = 0;
+			if (ebo_window_info(ctx, first, &tRef, &count) != EBO_OK || tRef >= split)
+			{
+				break;
+			}
+		}
+		if (!mapTracker_)
+		{
+			depth_->addResidentWindows(ctx, split);
+			if (first == n)
+			{
+				return;
+			}
+			const auto at = visual_odometry::syncGroundTruth(params_.depthPoses, params_.trackMapSplit);
+			if (!at.has_value())
+			{
+				throw std::runtime_error("tools::EventPump: trackMapSplit lies outside depthPoses' time span");
+			}
+			trackedMap_ = depth_->finish();
+			mapTracker_.reset(new visual_odometry::MapTracker(
+				visual_odometry::DepthMapper::cameraFor(ctx, params_.cameraModelParams), trackedMap_.points));
+			mapTracker_->starts = params_.trackStarts;
+			visual_odometry::DepthMapper::toAbi(at.value(), trackPose_);
+		}
+		mapTracker_->trackResidentWindows(ctx, first, trackPose_);
+	}
+
 	// the batched form of the compensation branch: the held events join the queue, the detector's list is
 	// cleared and lastCompensation moves to the window's last timestamp as compensateEventsContrast would move it
 	void queueWindow(const common::EventSample& sample)
@@ -333,6 +403,9 @@ class EventPump
 	std::unique_ptr<tracker::AngularVelocityEstimator> rotation_;
 	std::vector<tracker::AngularVelocityEstimate> angularVelocities_;
 	std::unique_ptr<visual_odometry::DepthMapper> depth_;
+	std::unique_ptr<visual_odometry::MapTracker> mapTracker_;
+	visual_odometry::DepthMap trackedMap_;
+	double trackPose_[12] = {};
 };
 
 // tools::Replayer (tools/replayer/src/replayer.cpp:42-131) for the two streams that decide WHEN the

@@ -90,6 +90,10 @@ class Evaluator
 		{
 			depthMap_ = pump_->finishDepthMap();
 			saveDepthMap(depthMap_, pump_->depthWindows());
+			if (params_.trackMap)
+			{
+				saveTrackedPoses(pump_->trackedWindows());
+			}
 		}
 	}
 
@@ -297,6 +301,43 @@ class Evaluator
 		std::fclose(fp);
 		std::fclose(fw);
 	}
+	// Not in the reference (EvaluatorParams::trackMap): <outputDir>/tracked_poses.txt, one line per tracked window: "t_ref_us"
+	// and the tracked pose, camera to world (R row-major, then t) -- the pose lines of depth_windows.txt; and
+	// <outputDir>/map_track.txt, one line per tracked window: "t_ref_us winner termination iterations num_evals_jac
+	// num_evals_cost initial_cost final_cost visible_start visible_final lost" of the window's winner (zeros when lost)
+	void saveTrackedPoses(const std::vector<visual_odometry::MapTrackWindow>& windows) const
+	{
+		FILE* fp = std::fopen((params_.outputDir + "/tracked_poses.txt").c_str(), "w");
+		FILE* fm = std::fopen((params_.outputDir + "/map_track.txt").c_str(), "w");
+		if (!fp || !fm)
+		{
+			for (FILE* f : {fp, fm})
+			{
+				if (f)
+				{
+					std::fclose(f);
+				}
+			}
+			throw std::runtime_error("tools::Evaluator: cannot write tracked_poses.txt or map_track.txt in " + params_.outputDir);
+		}
+		for (const auto& w : windows)
+		{
+			std::fprintf(fp, "%lld", static_cast<long long>(w.tRefUs));
+			for (const double v : w.pose)
+			{
+				std::fprintf(fp, " %.17g", v);
+			}
+			std::fprintf(fp, "\n");
+			const ebo_map_track_result& r = w.result;
+			std::fprintf(fm, "%lld %d %d %d %d %d %.17g %.17g %d %d %d\n", static_cast<long long>(w.tRefUs), w.winner, r.termination,
+						 r.iterations, r.num_evals_jac, r.num_evals_cost, r.initial_cost, r.final_cost, r.visible_start, r.visible_final,
+						 w.lost ? 1 : 0);
+		}
+		std::fclose(fp);
+		std::fclose(fm);
+	}
+	const std::vector<visual_odometry::MapTrackWindow>& trackedWindows() const { return pump_->trackedWindows(); }
+
 	// after finish(): the map that was written
 	const visual_odometry::DepthMap& depthMap() const { return depthMap_; }
 	const std::vector<visual_odometry::DepthWindow>& depthWindows() const { return pump_->depthWindows(); }

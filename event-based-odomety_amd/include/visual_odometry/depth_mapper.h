@@ -110,7 +110,9 @@ class DepthMapper
 	}
 
 	// Votes every window resident in ctx with the pose at its reference time.  Returns the number of windows voted.
-	size_t addResidentWindows(ebo_ctx* ctx)
+	// beforeUs: a window whose reference time is not before it takes no part and is not recorded (the windows a
+	// tools::EventPump tracks against the map instead of voting them, visual_odometry/map_tracker.h).
+	size_t addResidentWindows(ebo_ctx* ctx, int64_t beforeUs = INT64_MAX)
 	{
 		int n = 0;
 		if (!begun_ || !ctx || ebo_num_windows(ctx, &n) != EBO_OK)
@@ -125,6 +127,10 @@ class DepthMapper
 		{
 			DepthWindow info;
 			check(ebo_window_info(ctx, w, &info.tRefUs, &info.events));
+			if (info.tRefUs >= beforeUs)
+			{
+				continue;
+			}
 			const auto pose = syncGroundTruth(poses_, common::timestamp_t(info.tRefUs));
 			if (pose.has_value())
 			{

@@ -1,6 +1,6 @@
 // track_recording — the reference's feature-tracking experiment on a DAVIS240C recording directory, without OpenCV:
 //
-//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--angular-velocity] [--depth-map] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--maintain-map] [--ate] [--rpe]]
+//   track_recording --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--angular-velocity] [--depth-map [--track-map [--map-until SECONDS] [--track-starts 1|13]]] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--maintain-map] [--ate] [--rpe]]
 //
 // DIR holds events.txt, images.txt + the frames (8-bit grey PNG), optionally groundtruth.txt / calib.txt.
 // --rectify: the events of every compensation window are undistorted with the recording's calib.txt as they are
@@ -23,6 +23,12 @@
 // per kept pixel, OUT/points.txt the same pixels' points in the ground truth's frame and OUT/depth_windows.txt the
 // reference pose and every window's reference time, event count, whether it was voted, and pose.  The camera is chosen
 // as for --angular-velocity: with a distorted calib.txt the run is refused without --rectify.
+// --track-map (needs --depth-map): mapping and tracking in one pass.  Windows whose reference time is before the split
+// (--map-until SECONDS; default the middle of the ground truth's span) are voted as above; at the first window past it the
+// map is extracted and that window and every later one is tracked against it (visual_odometry::MapTracker; include/ebo.h
+// E1-E9), chained from the ground truth's pose at the split, with --track-starts 1 (default) or 13 starts a window.
+// OUT/tracked_poses.txt gets "t_ref_us" and the pose (R row-major, then t) per tracked window, OUT/map_track.txt "t_ref_us
+// winner termination iterations num_evals_jac num_evals_cost initial_cost final_cost visible_start visible_final lost".
 // --odometry: visual_odometry::VisualOdometryFrontEnd (visual_odometry/visual_odometry.h) runs as the keyframe hook on a
 // context of its own and OUT/keyframe_poses.txt gets one line per keyframe, stored ones first: the timestamp and the
 // camera-to-world pose [R | t] row by row (the first keyframe is the world frame, the first baseline the unit of length).
@@ -73,7 +79,7 @@
 
 static int usage(const char* argv0)
 {
-	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--angular-velocity] [--depth-map] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--maintain-map] [--ate] [--rpe]]\n", argv0);
+	std::fprintf(stderr, "usage: %s --dataset DIR --out DIR [--tracker-experiment] [--window-batch N] [--rectify] [--rectify-frames] [--angular-velocity] [--depth-map [--track-map [--map-until SECONDS] [--track-starts 1|13]]] [--track-error [--track-error-threshold PX]] [--odometry [--bundle-adjust] [--refine] [--refine-two-view] [--maintain-map] [--ate] [--rpe]]\n", argv0);
 	return 2;
 }
 
@@ -84,7 +90,9 @@ int main(int argc, char** argv)
 	size_t windowBatch = 1;
 	bool rectify = false, rectifyFrames = false;
 	bool angularVelocity = false;
-	bool depthMap = false;
+	bool depthMap = false, trackMap = false;
+	double mapUntil = -1.0;  // seconds; < 0: the middle of the ground truth's span
+	int trackStarts = 1;
 	bool trackError = false;
 	double trackErrorThreshold = 5.0;
 	bool odometry = false, bundleAdjust = false, refine = false, refineTwoView = false, maintainMap = false, ate = false, rpe = false;
@@ -118,6 +126,28 @@ int main(int argc, char** argv)
 		else if (a == "--depth-map")
 		{
 			depthMap = true;
+		}
+		else if (a == "--track-map")
+		{
+			trackMap = true;
+		}
+		else if (a == "--map-until" && i + 1 < argc)
+		{
+			char* end = nullptr;
+			mapUntil = std::strtod(argv[++i], &end);
+			if (!end || *end || !(mapUntil >= 0.0))
+			{
+				return usage(argv[0]);
+			}
+		}
+		else if (a == "--track-starts" && i + 1 < argc)
+		{
+			const std::string v = argv[++i];
+			if (v != "1" && v != "13")
+			{
+				return usage(argv[0]);
+			}
+			trackStarts = v == "1" ? 1 : 13;
 		}
 		else if (a == "--odometry")
 		{
@@ -179,6 +209,11 @@ int main(int argc, char** argv)
 	{
 		return usage(argv[0]);
 	}
+	if (trackMap && !depthMap)
+	{
+		std::fprintf(stderr, "track_recording: --track-map tracks against the map of --depth-map and needs it\n");
+		return 2;
+	}
 	if ((ate || rpe) && !odometry)
 	{
 		std::fprintf(stderr, "track_recording: --ate and --rpe evaluate the odometry's trajectory and need --odometry\n");
@@ -224,8 +259,14 @@ int main(int argc, char** argv)
 			p.depthPoses = groundTruth;
 			p.depthReferenceTime =
 				common::timestamp_t((groundTruth.front().timestamp.count() + groundTruth.back().timestamp.count()) / 2);
+			if (trackMap)
+			{
+				p.trackMap = true;
+				p.trackStarts = trackStarts;
+				p.trackMapSplit = mapUntil < 0.0 ? p.depthReferenceTime : common::timestamp_t(static_cast<long long>(mapUntil * 1e6 + 0.5));
+			}
 		}
-		size_t events = 0, frames = 0, tracks = 0, windows = 0, keyframes = 0, landmarks = 0, depthPixels = 0, depthWindows = 0;
+		size_t events = 0, frames = 0, tracks = 0, windows = 0, keyframes = 0, landmarks = 0, depthPixels = 0, depthWindows = 0, trackedWindows = 0, lostWindows = 0;
 		ebo_track_error_summary_result trackSummary{};
 		ebo_ctx* odometryCtx = nullptr;
 		if (odometry)
@@ -303,6 +344,11 @@ int main(int argc, char** argv)
 			if (depthMap)
 			{
 				depthPixels = evaluator.depthMap().points.size();
+				for (const auto& w : evaluator.trackedWindows())
+				{
+					++trackedWindows;
+					lostWindows += w.lost ? 1 : 0;
+				}
 				for (const auto& w : evaluator.depthWindows())
 				{
 					depthWindows += w.used ? 1 : 0;
@@ -479,6 +525,10 @@ int main(int argc, char** argv)
 		if (depthMap)
 		{
 			std::printf(", \"depth_pixels\": %zu, \"depth_windows\": %zu", depthPixels, depthWindows);
+			if (trackMap)
+			{
+				std::printf(", \"tracked_windows\": %zu, \"lost_windows\": %zu", trackedWindows, lostWindows);
+			}
 		}
 		if (trackError)
 		{

@@ -1789,6 +1789,111 @@ int ebo_dsi_depth(ebo_ctx* ctx, int32_t* index_or_null, uint32_t* conf_or_null, 
 				  int max_points, int* n_points_out);
 int ebo_dsi_end(ebo_ctx* ctx);
 
+/* ---- pose from events against a map: map-to-event-image alignment ------------------------------------
+ * The six-degree-of-freedom camera pose that lays a list of world points (a semi-dense map, for instance the point list
+ * of ebo_dsi_depth moved to the world) onto an image, in use the blurred image of a window's events: where the map's
+ * points project the image should be bright.  A Levenberg-Marquardt over a dense, image-sampling residual, for many
+ * (image, start pose) units in one launch.  The rules are this project's own (the reference has no counterpart);
+ * tests/maptrack_ref.py restates them in numpy.  Conventions as in "bundle adjustment": float64, one rounding per
+ * operation in exactly the association written here, no contraction, only + - * / sqrt, floor and comparisons; a
+ * comparison with a NaN is false.  dot(a, b) = (a0 * b0 + a1 * b1) + a2 * b2.  A pose is 12 doubles, R row-major [3][3]
+ * and then t [3], camera to world, as in the depth section (NOT the [3][4] of the bundle adjustment).
+ *
+ * Inputs: a pinhole camera under C1; n_images images double [n][h][w]; n_points world points [n][3]; n_units units, unit u
+ * naming image unit_image[u] and carrying its own start pose.  Several units may name one image (multi-start), several
+ * images may be solved at once (a batch).
+ *
+ * E1. Image scale.  bmax = the largest pixel of the unit's image that is > 0, 0 when there is none (a NaN pixel is never
+ *     taken: the result does not depend on the order).  When bmax is not finite or not > 0 the unit is not solved:
+ *     termination 2, every other field of its result 0, its trace rows 0, its pose returned bit for bit.  Otherwise
+ *     s = 1 / bmax.
+ * E2. Projection.  d = X - t;  q_j = dot(R[:][j], d) as in B1;  iz = 1 / q2;  xP = q0 * iz;  yP = q1 * iz;
+ *     u = fx * xP + cx;  v = fy * yP + cy.  A point is visible iff q2 > z_min and u >= 0 and u < w - 1 and v >= 0 and
+ *     v < h - 1, every test made in double before any conversion: all four taps are inside the image, and a NaN anywhere
+ *     makes the point not visible.  Nothing of the image is read for a point that is not visible.
+ * E3. Sample.  x0 = floor(u); y0 = floor(v); al = u - x0; be = v - y0; ial = 1 - al; ibe = 1 - be (V3).  b00 b10 b01 b11
+ *     = the image at (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1).
+ *       b = ibe * (ial * b00 + al * b10) + be * (ial * b01 + al * b11)
+ *       Du = ibe * (b10 - b00) + be * (b11 - b01);   Dv = ial * (b01 - b00) + al * (b11 - b10)      (V8's, on the image)
+ * E4. Residual.  r = 1 - s * b for a visible point;  r = 1 with a zero Jacobian row for one that is not, so that pushing
+ *     points out of view never lowers the cost.  No loss function: r lies in [0, 1] wherever the image is not negative.
+ * E5. Jacobian row for B4's right-hand update.  au = Du * fx;  av = Dv * fy;
+ *       A0 = -(s * (au * iz));   A1 = -(s * (av * iz));   A2 = s * ((au * xP + av * yP) * iz)          (A = dr/dq)
+ *       J = (-A0, -A1, -A2, A1 * q2 - A2 * q1, A2 * q0 - A0 * q2, A0 * q1 - A1 * q0)
+ *     and every entry is then multiplied by the scale of its column (B6).
+ * E6. Update.  B4 as it stands: (ups, om) = the step's entries 0-2 and 3-5, each first multiplied by its column's scale.
+ * E7. Sums.  The 21 entries J[a] * J[b], b <= a, of J'J, the 6 entries J[a] * r of J'r and r * r, each summed over ALL
+ *     points in index order by B9's tree(v): a unit's bits do not depend on the launch.  cost = 0.5 * tree(r * r).
+ * E8. Step.  B6's scale_c = 1 / (1 + sqrt(n_c)) from the diagonal of J'J at the start with all scales 1.  B7's damping on
+ *     the six diagonal entries; B8's Cholesky and substitutions on that one 6 x 6 block with rhs = J'r; step = -x.  B9's
+ *     trust region unchanged, with one free frame and no point variables: model cost change = -tree(m) over the points,
+ *     m = mr * (r + mr / 2), mr = dot6(J, step) added as ((((J0 * s0 + J1 * s1) + J2 * s2) + J3 * s3) + J4 * s4) + J5 * s5,
+ *     m = 0 for a point that is not visible; |x| and the step norm by tree over the 12 pose entries in the pose's own
+ *     order (R, then t); the gradient norm max_c |(J'r)_c / scale_c|; every exit, the non-monotonic bookkeeping, and the
+ *     result being the lowest-cost point visited.  A cost that is not finite at the start is termination 2 with the pose
+ *     returned bit for bit.
+ * E9. Outputs.  The pose, updated in place.  One ebo_map_track_result per unit: termination (0 converged, 1 iteration
+ *     limit, 2 failed or not solved), iterations, Jacobian and candidate evaluation counts (as ebo_summary counts them),
+ *     initial and final cost, the number of visible points at the start and at the returned pose, and s.  The optional
+ *     trace has ebo_bundle_adjust's form, double [n_units][opts->max_num_iterations + 1][4].  Every double and integer is
+ *     bit-equal to the restatement (a NaN cost, which E3 gives when a tap reads a NaN, equals any NaN); a unit has the
+ *     same bits alone, in any batch, at any position in it and from run to run.
+ *
+ * ebo_default_map_track_opts: as ebo_default_ba_opts, max_num_iterations 50; opts->mode is not read.
+ * ebo_map_track: host pointers, synchronous; uploads what it is given.  z_min: E2's, 0.05 is a sensible value.
+ * ebo_map_track_device: device pointers for images, points, unit_image, poses, results and trace; asynchronous on the
+ *   context's stream.  It cannot look at unit_image: a unit whose image index is out of range is not solved (termination 2,
+ *   the other fields 0, its pose untouched).
+ * Limits: 65535 units, 2^20 points, max_num_iterations 10000 (it sizes the trace).  EBO_ERR_ARG beyond them and for a
+ *   needed pointer that is NULL, a unit_image out of
+ *   range (host form), a camera with distortion, a negative count or max_num_iterations, w or h < 2, z_min not finite;
+ *   EBO_ERR_RANGE for fx or fy zero or not finite; EBO_ERR_STATE while a graph is being recorded.  Images, points and
+ *   poses are not validated: E1 and E2 say what a bad value does.
+ *
+ * ebo_event_images: B double [Wn][h][w], V5's blur of V4's image of every resident window at one omega per window
+ *   (omegas [Wn][3]; NULL: zeros, and F is then the un-warped integer count image).  params NULL: the defaults.  The
+ *   kernels and the chunks are ebo_eval_rotation's.  The _device form takes device pointers and is asynchronous on the
+ *   context's stream, so that it chains into ebo_map_track_device without leaving the device.  State and argument errors
+ *   as for ebo_rotation_image. */
+typedef struct ebo_map_track_result
+{
+	int termination;    /* 0 converged, 1 iteration limit, 2 failed or not solved */
+	int iterations;
+	int num_evals_jac;
+	int num_evals_cost;
+	int visible_start;  /* visible points at the start pose */
+	int visible_final;  /* and at the returned one */
+	int reserved0;      /* 0 */
+	int reserved1;      /* 0 */
+	double initial_cost;
+	double final_cost;
+	double scale;       /* E1's s */
+	double reserved2;   /* 0 */
+} ebo_map_track_result;
+void ebo_default_map_track_opts(ebo_solver_opts* opts);
+/* The 13 starts of a multi-start: starts [13][12] = pose, then pose moved through B4 by +step and -step along each of the six
+ * update directions in turn (translation_step for ups 0-2, rotation_step for om 0-2): start 1 + 2 a is +, 2 + 2 a is -.
+ * Host only, the rule's operations. */
+void ebo_map_track_starts(const double* pose, double translation_step, double rotation_step, double* starts);
+/* ebo_map_track on the windows resident in ctx, for a caller without device memory of its own: with make_images non-zero
+ * the images are ebo_event_images_device's (params, host omegas [Wn][3] or NULL) of every resident window, made into a
+ * buffer of the context and kept; with make_images 0 the images of the last such call are used again (EBO_ERR_STATE when
+ * there are none or a loader has run since).  unit_window[u] names a resident window; everything else as ebo_map_track,
+ * host pointers, synchronous.  The images never leave the device. */
+int ebo_map_track_resident(ebo_ctx* ctx, const ebo_camera* cam, const ebo_rotation_params* params_or_null, const double* omegas_or_null,
+						   int make_images, int n_points, const double* points, int n_units, const int* unit_window, double* poses,
+						   double z_min, const ebo_solver_opts* opts, ebo_map_track_result* results, double* trace_or_null);
+int ebo_map_track(ebo_ctx* ctx, const ebo_camera* cam, int w, int h, int n_images, const double* images, int n_points,
+				  const double* points, int n_units, const int* unit_image, double* poses, double z_min,
+				  const ebo_solver_opts* opts, ebo_map_track_result* results, double* trace_or_null);
+int ebo_map_track_device(ebo_ctx* ctx, const ebo_camera* cam, int w, int h, int n_images, const double* d_images, int n_points,
+						 const double* d_points, int n_units, const int* d_unit_image, double* d_poses, double z_min,
+						 const ebo_solver_opts* opts, ebo_map_track_result* d_results, double* d_trace_or_null);
+int ebo_event_images(ebo_ctx* ctx, const ebo_camera* cam, const ebo_rotation_params* params_or_null, const double* omegas_or_null,
+					 double* images);
+int ebo_event_images_device(ebo_ctx* ctx, const ebo_camera* cam, const ebo_rotation_params* params_or_null,
+							const double* d_omegas_or_null, double* d_images);
+
 /* Device-side timing of everything enqueued between begin and end on the
  * context's stream (hipEvent based). */
 int ebo_timer_begin(ebo_ctx* ctx);
