@@ -316,3 +316,143 @@ def batch(n, gname="small"):
     wins = [random_window(200 + i, int(rng.integers(3, 400)), w, h, strays=int(i % 3)) for i in range(n)]
     names = [k for k in POSES if k not in NO_VOTE]
     return wins, [POSES[names[i % len(names)]] for i in range(n)]
+
+
+# ---- the launch shapes: dsi_tile's outcomes, the plane split and the point list's scan (tests/test_gpu_depth_shapes.py) ----
+
+TILE_MARGIN, TILE_PX, WAVES, BLOCK = 1, 1024, 4, 256  # kDsiMargin, kDsiTilePx, kDsiWaves and kDsiBlock of csrc/ebo_depth.inc
+OUTCOMES = ("tile", "lam", "far", "off", "large")
+
+# a view turned by 90 degrees about y, 4 units along -x: d2 = cos(90 deg) - sin(90 deg) * a changes sign where x passes
+# cx, so lam is of either sign and of any size; the rays left of cx come back into the image
+SHAPE_POSE_TABLE = dict(POSES)  # POSES itself stays as tests/test_gpu_depth.py's parameters
+SHAPE_POSE_TABLE["ry90"] = _rel(rot(1, 90.0), (-4.0, 0.0, 0.0))
+SHAPE_POSE_TABLE["drift_a"] = _rel(t=(0.02, 0.01, 0.0))  # a few pixels: a region without events stays without votes
+SHAPE_POSE_TABLE["drift_b"] = _rel(rot(2, 1.0), (-0.015, 0.02, 0.0))
+SHAPE_POSES = ("rz5", "tz_near", "behind", "tx", "ry5", "ry90")  # test_gpu_depth.py's A/B list and the near-90-degree view
+BIG_PATCH = dict(w=64, h=48, patch_w=32, patch_h=32, cam=(60.0, 60.0, 32.0, 24.0))  # two units of 32 x 48: no box fits a tile
+FINE = dict(w=37, h=29, patch_w=4, patch_h=4, cam=SMALL["cam"])  # 63 units: 17 windows are 1071 (patch, window) pairs
+SCAN_GEOS = {
+    "255_blocks": dict(w=256, h=255, patch_w=20, patch_h=20, cam=(240.0, 241.0, 127.5, 127.25), hole_x=64),
+    "256_blocks": dict(w=256, h=256, patch_w=20, patch_h=20, cam=(240.0, 241.0, 127.5, 127.25), hole_x=64),
+    "257_blocks": dict(w=257, h=256, patch_w=20, patch_h=20, cam=(240.0, 241.0, 128.0, 127.25), hole_x=20),
+    "352_blocks": dict(w=346, h=260, patch_w=20, patch_h=20, cam=(260.0, 261.0, 172.5, 129.25), hole_x=120),
+}
+SCAN_POSES = ("tx_neg", "tx_pos", "ty_neg", "ty_pos", "drift_a", "drift_b")
+SCAN_NZ, SCAN_EXCESS = 5, 0.125
+PLANE_COUNTS = (253, 255, 256)
+
+
+def rects(geo):
+    """The units' rects (rx, ry, rw, rh) in unit order, as the loader's rect_of: the last patch of an axis takes the rest."""
+    npx, npy = geo["w"] // geo["patch_w"], geo["h"] // geo["patch_h"]
+    out = []
+    for py in range(npy):
+        for px in range(npx):
+            rw = geo["w"] - px * geo["patch_w"] if px == npx - 1 else geo["patch_w"]
+            rh = geo["h"] - py * geo["patch_h"] if py == npy - 1 else geo["patch_h"]
+            out.append((px * geo["patch_w"], py * geo["patch_h"], rw, rh))
+    return out
+
+
+def tile_of(geo, rect, Rr, tr, zk):
+    """dsi_tile of one (unit, plane) -> (outcome, (tx0, ty0, tw, th)): "tile"; "lam": a corner with lam <= 0; "far": a
+    corner mapped beyond 1e6 or not finite; "off": the box misses the image; "large": more than kDsiTilePx pixels.  The
+    corners go through M2 and M3 in their written order, one rounding per operation, and are tested in the kernel's order."""
+    fx, fy, cx, cy = [np.float64(v) for v in geo["cam"]]
+    w, h = geo["w"], geo["h"]
+    rx, ry, rw, rh = rect
+    zk = np.float64(zk)
+    us, vs = [], []
+    with np.errstate(all="ignore"):
+        for c in range(4):
+            x = np.float64(rx + (rw - 1 if c & 1 else 0))
+            y = np.float64(ry + (rh - 1 if c >> 1 else 0))
+            a = (x - cx) / fx
+            b = (y - cy) / fy
+            d0 = (Rr[0, 0] * a + Rr[0, 1] * b) + Rr[0, 2]
+            d1 = (Rr[1, 0] * a + Rr[1, 1] * b) + Rr[1, 2]
+            d2 = (Rr[2, 0] * a + Rr[2, 1] * b) + Rr[2, 2]
+            lam = (zk - tr[2]) / d2
+            if not lam > 0.0:
+                return "lam", (0, 0, 0, 0)
+            X = tr[0] + lam * d0
+            Y = tr[1] + lam * d1
+            u = fx * (X / zk) + cx
+            v = fy * (Y / zk) + cy
+            if not (u > -1e6 and u < 1e6 and v > -1e6 and v < 1e6):
+                return "far", (0, 0, 0, 0)
+            us.append(u)
+            vs.append(v)
+    x0, x1 = max(int(math.floor(min(us))) - TILE_MARGIN, 0), min(int(math.floor(max(us))) + 1 + TILE_MARGIN, w - 1)
+    y0, y1 = max(int(math.floor(min(vs))) - TILE_MARGIN, 0), min(int(math.floor(max(vs))) + 1 + TILE_MARGIN, h - 1)
+    if x1 < x0 or y1 < y0:
+        return "off", (0, 0, 0, 0)
+    if (x1 - x0 + 1) * (y1 - y0 + 1) > TILE_PX:
+        return "large", (0, 0, 0, 0)
+    return "tile", (x0, y0, x1 - x0 + 1, y1 - y0 + 1)
+
+
+def tile_census(geo, nz, pose_names, planes=None):
+    """Over (unit, plane, pose): outcome -> count, the poses seen per outcome, and "mixed": the rounds of four consecutive
+    planes of a workgroup (that walks `planes` planes from a multiple of it; None: all nz) in which a tile and a non-tile
+    outcome meet."""
+    z = planes_table(nz)
+    planes = nz if planes is None else planes
+    count = {o: 0 for o in OUTCOMES}
+    poses = {o: set() for o in OUTCOMES}
+    mixed = 0
+    for pname in pose_names:
+        Rr, tr = relative_pose(REF_POSE, SHAPE_POSE_TABLE[pname])
+        for rect in rects(geo):
+            got = [tile_of(geo, rect, Rr, tr, zk)[0] for zk in z]
+            for o in got:
+                count[o] += 1
+                poses[o].add(pname)
+            for k0 in range(0, nz, planes):
+                k1 = min(k0 + planes, nz)
+                for kr in range(k0, k1, WAVES):
+                    kinds = {o == "tile" for o in got[kr:min(kr + WAVES, k1)]}
+                    mixed += len(kinds) == 2
+    return dict(count=count, poses=poses, mixed=mixed)
+
+
+def planes_table(nz):
+    return planes(nz, *Z_RANGE)
+
+
+def planes_per_group(n_cus, pairs, nz):
+    """csrc/ebo_depth.cpp's planes_per_group of the shipped build"""
+    want = 4 * (n_cus if n_cus > 0 else 256)
+    chunks = min(nz, max(1, (want + pairs - 1) // max(pairs, 1)))
+    return (nz + chunks - 1) // chunks
+
+
+def shape_windows(gname):
+    """Six windows of a sensor, one for each of SHAPE_POSES: case_windows and 2000 more spread events"""
+    key = "shape_" + gname
+    if key not in _WINDOWS:
+        _WINDOWS[key] = case_windows(gname) + [random_window(8, 2000, GEOS[gname]["w"], GEOS[gname]["h"], strays=30)]
+    return _WINDOWS[key]
+
+
+def scan_windows(gname):
+    """Six windows of 20 000 uniform events of a SCAN_GEOS sensor, one for each of SCAN_POSES, less the events from
+    column hole_x on within 24 rows of the middle row (fewer than 256 pixels a row, so every workgroup keeps some): under SCAN_POSES' few pixels of motion no ray reaches the middle of
+    that region, so whole waves of k_dsi_count's workgroups keep nothing there."""
+    key = "scan_" + gname
+    if key not in _WINDOWS:
+        w, h = SCAN_GEOS[gname]["w"], SCAN_GEOS[gname]["h"]
+        wins = [random_window(300 + i, 20000, w, h) for i in range(len(SCAN_POSES))]
+        _WINDOWS[key] = [ev[~((ev["x"] >= SCAN_GEOS[gname]["hole_x"]) & (np.abs(ev["y"] - h // 2) <= 24))] for ev in wins]
+    return _WINDOWS[key]
+
+
+def block_census(index):
+    """Of k_dsi_count's workgroups of 256 consecutive pixels: (kept pixels per block, kept pixels in each block's last
+    wave, the exclusive offsets)"""
+    kept = (np.asarray(index).reshape(-1) >= 0).astype(np.int64)
+    nb = (len(kept) + BLOCK - 1) // BLOCK
+    pad = np.concatenate([kept, np.zeros(nb * BLOCK - len(kept), dtype=np.int64)]).reshape(nb, BLOCK)
+    per = pad.sum(axis=1)
+    return per, pad[:, BLOCK - 64:].sum(axis=1), np.concatenate([[0], np.cumsum(per)[:-1]])

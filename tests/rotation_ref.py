@@ -55,7 +55,8 @@ def blur(img, g):
 
 
 def warp(ev, t_ref, cam, w, h, omega):
-    """V1-V3 for the in-sensor events -> dict of per-voting-event arrays (x0, y0, al, be, ial, ibe, a, b, X, Y, Z, tau)."""
+    """V1-V3 for the in-sensor events -> dict of per-voting-event arrays (x0, y0, al, be, ial, ibe, a, b, X, Y, Z, tau, and
+    the source pixel x, y)."""
     fx, fy, cx, cy = [np.float64(v) for v in cam]
     wx, wy, wz = [np.float64(v) for v in omega]
     inside = (ev["x"] >= 0) & (ev["x"] < w) & (ev["y"] >= 0) & (ev["y"] < h)  # the stray unit takes no part
@@ -76,7 +77,7 @@ def warp(ev, t_ref, cam, w, h, omega):
         u = fx * (X / Z) + cx
         v = fy * (Y / Z) + cy
         ok &= (u > -1.0) & (u < float(w)) & (v > -1.0) & (v < float(h))
-    k = {n: arr[ok] for n, arr in dict(a=a, b=b, X=X, Y=Y, Z=Z, tau=tau, u=u, v=v).items()}
+    k = {n: arr[ok] for n, arr in dict(a=a, b=b, X=X, Y=Y, Z=Z, tau=tau, u=u, v=v, x=x, y=y).items()}
     fx0 = np.floor(k["u"])
     fy0 = np.floor(k["v"])
     k["x0"] = fx0.astype(np.int64)
@@ -356,3 +357,161 @@ def same_bits(a, b):
     a = np.ascontiguousarray(a, dtype=np.float64)
     b = np.ascontiguousarray(b, dtype=np.float64)
     return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
+# ---- the launch shapes: k_rot_vote's tile and eval_windows' chunks (tests/test_gpu_rotation_shapes.py) ----
+
+MARGIN, TILE_PX = 8, 4096  # kRotMargin and kRotTilePx of csrc/ebo_rotation.inc
+CHUNK_MAX, BLOCK = 64, 256  # kRotChunkMax and kRotBlock of csrc/ebo_rotation.h
+
+T150 = dict(w=150, h=128, patch_w=48, patch_h=48, cam=(140.0, 141.0, 74.5, 63.25))  # 48 x 48, 54 x 48, 48 x 80 and 54 x 80
+T64 = dict(w=64, h=64, patch_w=64, patch_h=64, cam=(60.0, 61.0, 31.5, 32.25))  # one unit of 4096 px: the last tile
+T65 = dict(w=64, h=65, patch_w=64, patch_h=64, cam=(60.0, 61.0, 31.5, 32.25))  # one unit of 4160 px: no tile
+T40 = dict(w=40, h=40, patch_w=20, patch_h=20, cam=(38.0, 39.0, 19.5, 20.25))  # four grown tiles, each clipped at two edges
+DAVIS346 = dict(w=346, h=260, patch_w=20, patch_h=20, cam=(260.0, 261.0, 172.5, 129.25))  # 352 pixel blocks, 221 patches
+TILE_GEOS = dict(t150=T150, t64=T64, t65=T65, t40=T40)
+SLOW = (0.006, -0.004, 0.01)  # OMEGAS["small"] / 50: over a 1.5 s window the events stay in view
+
+
+def grid(geo):
+    return geo["w"] // geo["patch_w"], geo["h"] // geo["patch_h"]
+
+
+def rects(geo):
+    """The units' rects (rx, ry, rw, rh) in unit order, as the loader's rect_of: the last patch of an axis takes the rest."""
+    npx, npy = grid(geo)
+    out = []
+    for py in range(npy):
+        for px in range(npx):
+            rw = geo["w"] - px * geo["patch_w"] if px == npx - 1 else geo["patch_w"]
+            rh = geo["h"] - py * geo["patch_h"] if py == npy - 1 else geo["patch_h"]
+            out.append((px * geo["patch_w"], py * geo["patch_h"], rw, rh))
+    return out
+
+
+def unit_of(geo, x, y):
+    """The unit of in-sensor pixels, as the loader's bucket_of."""
+    npx, npy = grid(geo)
+    return np.minimum(y // geo["patch_h"], npy - 1) * npx + np.minimum(x // geo["patch_w"], npx - 1)
+
+
+def tile_margin(rect):
+    rx, ry, rw, rh = rect
+    return 0 if (rw + 2 * MARGIN) * (rh + 2 * MARGIN) > TILE_PX else MARGIN
+
+
+def tile_of(rect, w, h):
+    """k_rot_vote's LDS tile of a unit (tx0, ty0, tw, th): the margin rule, then the clip to the image, then the size
+    rule; tw = th = 0: no tile."""
+    rx, ry, rw, rh = rect
+    m = tile_margin(rect)
+    tx0, ty0 = max(rx - m, 0), max(ry - m, 0)
+    tw, th = min(rx + rw + m, w) - tx0, min(ry + rh + m, h) - ty0
+    if tw <= 0 or th <= 0 or tw * th > TILE_PX:
+        tw = th = 0
+    return tx0, ty0, tw, th
+
+
+def tile_form(rect, w, h):
+    """"grown": the rect with its margin; "bare": the rect alone; "none": no tile."""
+    if tile_of(rect, w, h)[2] == 0:
+        return "none"
+    return "grown" if tile_margin(rect) else "bare"
+
+
+def tap_census(case):
+    """form -> dict(units: the (window, unit) pairs of that form with a voting event, inside: their taps that land in the
+    unit's tile, direct: their taps that go straight to H).  A tap counts as in k_rot_vote: in the image, weight not 0."""
+    geo = case["geo"]
+    w, h = geo["w"], geo["h"]
+    rs = rects(geo)
+    tiles = np.array([tile_of(r, w, h) for r in rs])
+    forms = [tile_form(r, w, h) for r in rs]
+    out = {f: dict(units=set(), inside=0, direct=0) for f in ("grown", "bare", "none")}
+    for i, (ev, om) in enumerate(zip(case["windows"], case["omegas"])):
+        k = warp(ev, ref_time(ev), geo["cam"], w, h, om)
+        unit = unit_of(geo, k["x"].astype(np.int64), k["y"].astype(np.int64))
+        for b in np.unique(unit):
+            out[forms[b]]["units"].add((i, int(b)))
+        tx0, ty0, tw, th = tiles[unit].T
+        for dx, dy, wt in taps(k):
+            px, py = k["x0"] + dx, k["y0"] + dy
+            counted = (np.rint(wt * Q) != 0) & (px >= 0) & (px < w) & (py >= 0) & (py < h)
+            inside = counted & (px - tx0 >= 0) & (px - tx0 < tw) & (py - ty0 >= 0) & (py - ty0 < th)
+            for f in out:
+                of_form = np.array([forms[b] == f for b in unit], dtype=bool)
+                out[f]["inside"] += int((inside & of_form).sum())
+                out[f]["direct"] += int((counted & ~inside & of_form).sum())
+    return out
+
+
+_SHAPES = {}
+
+
+def tile_cases():
+    """The four tile geometries at OMEGAS "small" (taps land in the margin) and "x40" (taps leave the tile): 4000 uniform
+    events with strays, and the border window.  Built once, read only."""
+    if "tile" not in _SHAPES:
+        cases = {}
+        for gname, geo in TILE_GEOS.items():
+            wins = [random_window(21, 4000, geo["w"], geo["h"], strays=20), border_window(geo["w"], geo["h"])]
+            for oname in ("small", "x40"):
+                cases["%s_%s" % (gname, oname)] = dict(geo=geo, windows=wins, omegas=np.tile(np.array(OMEGAS[oname]), (2, 1)), sigma=1.0)
+        _SHAPES["tile"] = cases
+    return _SHAPES["tile"]
+
+
+def davis_cases():
+    """346 x 260 with 20 x 20 patches: a scene window of 15 000 events and 15 000 uniform events with 500 strays."""
+    if "davis" not in _SHAPES:
+        geo = DAVIS346
+        wins = [scene(5, (1.0, -2.0, 3.0), cam=geo["cam"], w=geo["w"], h=geo["h"]), random_window(9, 15000, geo["w"], geo["h"], strays=500)]
+        om = np.array([[0.8, -1.5, 2.0], [2.0, 1.0, -4.0]])
+        _SHAPES["davis"] = {"davis_sigma_%g" % s: dict(geo=geo, windows=wins, omegas=om, sigma=s) for s in (1.0, 2.5)}
+    return _SHAPES["davis"]
+
+
+def long_window(seed, t0):
+    """1.5 s of 37 x 29 from t0: the first patch column falls silent after 0.5 s and the last patch of the first row
+    wakes after 1.0 s, so their units' own reference times lie far from the window's."""
+    ev = random_window(seed, 1500, SMALL["w"], SMALL["h"], duration_us=1500000, strays=10)
+    early = (ev["x"] < 8) & (ev["t_us"] > 500000)
+    late = (ev["x"] >= 24) & (ev["y"] < 8) & (ev["t_us"] < 1000000)
+    ev = ev[~(early | late)]
+    ev["t_us"] += t0
+    return ev
+
+
+def long_cases():
+    """Two windows of 1.5 s, one from 0 and one from 2 000 000 000 us, at omega 0 and at SLOW."""
+    if "long" not in _SHAPES:
+        wins = [long_window(31, 0), long_window(32, 2000000000)]
+        _SHAPES["long"] = {"long_" + n: dict(geo=SMALL, windows=wins, omegas=np.tile(np.array(om), (2, 1)), sigma=1.0)
+                           for n, om in (("zero", OMEGAS["zero"]), ("slow", SLOW))}
+    return _SHAPES["long"]
+
+
+def unit_dt_win(ev, geo):
+    """unit -> the loader's dt_win = t_ref(window) - t_ref(unit) of the units that hold events: a unit's reference time
+    is the mid of its earliest and latest stamp, truncated."""
+    inside = (ev["x"] >= 0) & (ev["x"] < geo["w"]) & (ev["y"] >= 0) & (ev["y"] < geo["h"])
+    unit = unit_of(geo, ev["x"][inside].astype(np.int64), ev["y"][inside].astype(np.int64))
+    t = ev["t_us"][inside]
+    return {int(b): ref_time(ev) - int(float(int(t[unit == b].min()) + int(t[unit == b].max())) * 0.5) for b in np.unique(unit)}
+
+
+def carve_bytes(geo):
+    """The scratch of one chunk slot, as csrc/ebo_rotation.cpp's RotCarve(1, w, h, P): every piece ends on 256 bytes."""
+    npx, npy = grid(geo)
+    npix = geo["w"] * geo["h"]
+    img, part = npix * 8, ((npix + BLOCK - 1) // BLOCK) * 8
+    at = 0
+    for piece in (img, img, img, part, part, 8, npx * npy * 3 * 8):
+        at = (at + piece + 255) & ~255
+    return at
+
+
+def chunk_slots(geo, budget_mb, n):
+    """eval_windows' windows per chunk for n windows under EBO_ROTATION_SCRATCH_MB = budget_mb (None: unset, 256)."""
+    budget = (256 if budget_mb is None else int(budget_mb)) << 20
+    return min(max(1, budget // carve_bytes(geo)), CHUNK_MAX, max(n, 1))

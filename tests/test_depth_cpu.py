@@ -226,3 +226,56 @@ def test_the_defaults_and_the_bindings(ebo):
     with pytest.raises(AttributeError):
         ebo.default_depth_params(planes=3)
     assert all(hasattr(ebo.Context, n) for n in ("dsi_begin", "dsi_add_windows", "dsi_volume", "dsi_depth", "dsi_end"))
+
+
+# ---- the launch shapes of tests/test_gpu_depth_shapes.py -------------------------------------------
+
+def test_the_shape_cases_reach_every_tile_outcome():
+    """dsi_tile has five outcomes (depth_ref.tile_of restates it).  Over (unit, plane, pose), the older cases
+    (depth_ref.POSES on both sensors, 32 planes) find four of them; the cases of tests/test_gpu_depth_shapes.py find all
+    five, rounds of four planes where a tile and a non-tile outcome meet, and the not-finite corner in a view that votes."""
+    seen = set()
+    for gname, geo in D.GEOS.items():
+        c = D.tile_census(geo, 32, sorted(D.POSES))
+        print("older cases", gname, c["count"], "mixed rounds", c["mixed"])
+        seen |= {o for o, n in c["count"].items() if n}
+    assert seen == {"tile", "lam", "off", "large"}
+    total = {o: 0 for o in D.OUTCOMES}
+    lists = [("small", D.SMALL, nz) for nz in D.PLANE_COUNTS] + [("medium", D.MEDIUM, 32), ("big_patch", D.BIG_PATCH, 32)]
+    for gname, geo, nz in lists:
+        c = D.tile_census(geo, nz, D.SHAPE_POSES)
+        print(gname, nz, c["count"], "mixed rounds", c["mixed"])
+        for o, n in c["count"].items():
+            total[o] += n
+        if gname == "small":
+            # a workgroup that walks every plane, and the shipped split of a single window on 256 CUs
+            split = D.planes_per_group(256, len(D.rects(geo)), nz)
+            few = D.tile_census(geo, nz, D.SHAPE_POSES, split)["mixed"]
+            print(gname, nz, "mixed rounds at %d planes a workgroup: %d" % (split, few))
+            assert split == 3 and c["mixed"] >= 1 and few >= 1
+        if gname == "medium":
+            assert all(c["count"][o] for o in D.OUTCOMES) and c["mixed"] >= 1 and c["poses"]["far"] == {"ry90"}
+        if gname == "big_patch":
+            assert c["count"]["far"] and c["count"]["large"] > c["count"]["tile"]
+            plain = D.tile_census(geo, nz, ("rz5", "ry5"))["count"]
+            assert plain["large"] == 2 * len(D.rects(geo)) * nz  # these views vote by global atomics alone
+    print("the shape cases:", total)
+    assert all(total[o] for o in D.OUTCOMES)
+    # the near-90-degree view votes: on 64 x 48 beside the not-finite corner at x == cx, on 37 x 29 with d2 changing sign
+    # inside the patches of the third column
+    z = D.planes_table(32)
+    for gname in ("small", "medium"):
+        geo = D.GEOS[gname]
+        own = D.volume(D.shape_windows(gname)[5:], [D.SHAPE_POSE_TABLE["ry90"]], D.REF_POSE, geo["cam"], geo["w"], geo["h"], z)
+        print(gname, "ry90 alone: %d votes of 1024" % (int(own.astype(np.int64).sum()) >> 10))
+        assert own.any()
+    Rr, _ = D.relative_pose(D.REF_POSE, D.SHAPE_POSE_TABLE["ry90"])
+    fx, _, cx, _ = D.SMALL["cam"]
+    d2 = [(Rr[2, 0] * ((float(x) - cx) / fx) + Rr[2, 1] * 0.0) + Rr[2, 2] for x in range(16, 24)]
+    assert min(d2) < 0.0 < max(d2) and D.rects(D.SMALL)[2] == (16, 0, 8, 8)
+    # 37 x 29 in 4 x 4 patches: 17 windows fill a 256-CU device four times over, so one workgroup walks every plane
+    assert len(D.rects(D.FINE)) == 63 and [D.planes_per_group(256, 63 * 17, nz) for nz in D.PLANE_COUNTS] == list(D.PLANE_COUNTS)
+    assert D.tile_census(D.FINE, 7, D.SHAPE_POSES)["mixed"] >= 1
+    # the scan sensors: 255, 256, 257 and 352 workgroups of 256 pixels
+    assert [(g["w"] * g["h"] + 255) // 256 for g in D.SCAN_GEOS.values()] == [255, 256, 257, 352]
+    assert all(g["w"] - g["hole_x"] < 256 for g in D.SCAN_GEOS.values())

@@ -265,3 +265,67 @@ def test_the_facade_driver_compiles(ebo, tmp_path):
                          capture_output=True, text=True)
     assert out.returncode == 0 and os.path.exists(tmp_path / "angular_velocity_test"), out.stderr[-2000:]
     assert "warning" not in out.stderr
+
+
+# ---- the launch shapes of tests/test_gpu_rotation_shapes.py ---------------------------------------
+
+def test_the_tile_cases_reach_every_tile_form():
+    """k_rot_vote picks its LDS tile from the unit's rect alone (rotation_ref.tile_of restates it): the cases of
+    tests/test_gpu_rotation_shapes.py hold units with the grown tile, the bare tile and no tile, one at each limit, grown
+    tiles clipped at each image edge, and for every form that has a tile taps inside it and taps that miss it.  The
+    older cases (rotation_ref.gpu_cases) hold the grown form only."""
+    assert {R.tile_form(r, g["w"], g["h"]) for g in (R.SMALL, R.LARGE, R.DAVIS346) for r in R.rects(g)} == {"grown"}
+    units = [(g, r, R.tile_form(r, g["w"], g["h"])) for g in R.TILE_GEOS.values() for r in R.rects(g)]
+    assert {f for _, _, f in units} == {"grown", "bare", "none"}
+    assert any(f == "grown" and (r[2] + 2 * R.MARGIN) * (r[3] + 2 * R.MARGIN) == R.TILE_PX for _, r, f in units)  # the last margin
+    assert any(f == "bare" and r[2] * r[3] == R.TILE_PX for _, r, f in units)                                       # the last tile
+    assert any(f == "bare" and r[2] * r[3] < R.TILE_PX for _, r, f in units)           # too big for its margin, not for a tile
+    above = [r[2] * r[3] for _, r, f in units if f == "none"]
+    assert min(above) == R.TILE_PX + 64 and all(f != "none" or r[2] * r[3] > R.TILE_PX for _, r, f in units)  # one row of 64 more
+    assert R.tile_form(R.rects(R.T150)[-1], 150, 128) == "none" and R.rects(R.T150)[-1] == (96, 48, 54, 80)  # the remainder rect
+    clipped = set()
+    for g, r, f in units:
+        tx0, ty0, tw, th = R.tile_of(r, g["w"], g["h"])
+        if f == "grown":
+            edges = {e for e, hit in (("left", r[0] - R.MARGIN < 0), ("top", r[1] - R.MARGIN < 0),
+                                      ("right", r[0] + r[2] + R.MARGIN > g["w"]), ("bottom", r[1] + r[3] + R.MARGIN > g["h"])) if hit}
+            assert (tw * th < (r[2] + 2 * R.MARGIN) * (r[3] + 2 * R.MARGIN)) == bool(edges)
+            clipped |= edges
+        assert 0 <= tx0 and 0 <= ty0 and tx0 + tw <= g["w"] and ty0 + th <= g["h"] and tw * th <= R.TILE_PX
+    assert clipped == {"left", "top", "right", "bottom"}
+    total = {f: dict(inside=0, direct=0) for f in ("grown", "bare", "none")}
+    for name, case in sorted(R.tile_cases().items()):
+        census = R.tap_census(case)
+        print(name, {f: (len(v["units"]), v["inside"], v["direct"]) for f, v in census.items()})
+        for f, v in census.items():
+            total[f]["inside"] += v["inside"]
+            total[f]["direct"] += v["direct"]
+        if name.endswith("_small"):  # every unit of every window accumulates taps
+            n_units = len(R.rects(case["geo"]))
+            assert sum(len(v["units"]) for v in census.values()) == len(case["windows"]) * n_units, name
+    print("taps (in the tile, straight to H):", {f: (v["inside"], v["direct"]) for f, v in total.items()})
+    assert total["grown"]["inside"] and total["grown"]["direct"] and total["bare"]["inside"] and total["bare"]["direct"]
+    assert total["none"]["direct"] and not total["none"]["inside"]
+    t150 = R.tap_census(R.tile_cases()["t150_x40"])  # the A/B comparison's geometry holds all of it by itself
+    assert all(t150[f]["direct"] for f in t150) and t150["grown"]["inside"] and t150["bare"]["inside"]
+
+
+def test_the_chunk_budgets_and_the_long_windows_are_what_they_are_meant_to_be():
+    """eval_windows' slots per chunk under the budgets the GPU test sets (rotation_ref.chunk_slots restates the carve), and
+    the units' dt_win of the 1.5 s windows as the loader derives them."""
+    small = [R.chunk_slots(R.SMALL, mb, 70) for mb in (0, 1, None)]
+    print("37 x 29: %d bytes a slot, slots at 0 MB, 1 MB, unset: %s" % (R.carve_bytes(R.SMALL), small))
+    assert small[0] == 1 and 1 < small[1] < R.CHUNK_MAX and 70 % small[1] != 0 and small[2] == R.CHUNK_MAX
+    large = R.chunk_slots(R.LARGE, 5, 12)
+    print("240 x 180: %d bytes a slot, slots at 5 MB: %d" % (R.carve_bytes(R.LARGE), large))
+    assert 1 < large <= 5 and 12 % large != 0 and R.chunk_slots(R.LARGE, None, 12) == 12
+    for name, case in R.long_cases().items():
+        for ev in case["windows"]:
+            dt = R.unit_dt_win(ev, R.SMALL)
+            span = int(ev["t_us"][-1]) - int(ev["t_us"][0])
+            print(name, "span %d us, t_ref %d, dt_win %s" % (span, R.ref_time(ev), dt))
+            assert span > 1400000 and R.ref_time(ev) < 2 ** 31 and len(dt) == 12
+            assert max(dt.values()) > 100000 and min(dt.values()) < -100000
+    assert R.ref_time(R.long_cases()["long_zero"]["windows"][1]) > 2000000000
+    k = R.warp(R.long_cases()["long_slow"]["windows"][0], 750000, R.SMALL["cam"], 37, 29, R.SLOW)
+    assert len(k["x0"]) > 1000 and np.any(k["al"] != 0.0)  # the events stay in view, off the integers
