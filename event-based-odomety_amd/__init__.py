@@ -1090,6 +1090,12 @@ class Context:
         self._check(lib().ebo_eval_launch_shape(self._h, int(want_jac), *[C.byref(a) for a in v]))
         return tuple(a.value for a in v)
 
+    def eval_resident_workgroups(self, want_jac=True):
+        """diagnostic: (planned, actual) workgroups of the variance evaluation's launch resident on one CU"""
+        v = [C.c_int() for _ in range(2)]
+        self._check(lib().ebo_eval_resident_workgroups(self._h, int(want_jac), *[C.byref(a) for a in v]))
+        return tuple(a.value for a in v)
+
     def stream_yardstick_device(self, d_image):
         """diagnostic: the bytes of a count-image launch with no work; returns the bytes moved"""
         n = C.c_uint64()

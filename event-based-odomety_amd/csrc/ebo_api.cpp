@@ -3,6 +3,7 @@
 // There is no CPU compute path here: every objective value, Jacobian, solved flow
 // and count image comes from the HIP kernels in ebo_kernels.hip.
 #include "ebo_ctx.h"
+#include "eval_plan.h"
 #include "lockstep.h"
 
 #include <atomic>
@@ -99,7 +100,7 @@ int min_tiles(int channels, int rw, int rh, size_t budget)
 	return -1;
 }
 
-// LDS of one k_eval3 / k_solve_independent workgroup.  The image is the bounding box of
+// LDS of one k_solve_independent workgroup (k_eval3's: eval_plan.h).  The image is the bounding box of
 // the warped events; one workgroup owns `capDoubles` pixels of LDS behind a header and
 // walks larger boxes in sequential sub-bands.  A full canvas row must fit.
 int image_capacity(ebo_ctx* c, int& capDoubles, size_t& lds, size_t defaultKb = 40)
@@ -458,39 +459,40 @@ int eval_launch_shape(ebo_ctx* c, int want_jac, EvalLaunch& L)
 	L.flow_sets = central ? 5 : 1;
 	L.channels = (want_jac && !central) ? 3 : 1;
 	L.fd_step = central ? c->prm.fd_step : 0.0;
-	// Many units: k_eval3 runs four waves per SIMD (128 VGPRs), i.e. 16 waves per CU, and what a launch
-	// chooses is how to cut them into workgroups -- more, smaller workgroups overlap their barrier-separated
-	// passes better on the CU's one LDS, but each gets less of it, and a box that does not fit is counted in
-	// sequential sub-bands (every event warped again per sub-band).  By the canvas of the REGULAR patch (the
-	// geometry only, never the data: a window evaluates bit-identically alone and inside any batch):
-	//    canvas <= 32 KB (the reference's 20x20 patches, C3's 21x16): 7 workgroups of 128 lanes, 22 KB
-	//    larger (C2 30x22, C4 40x22):                                  4 workgroups of 256 lanes, 39 KB
-	// Measured against three waves per SIMD with four 192-lane workgroups of 40 KB (round 2), evaluation with
-	// Jacobian at flows 0 / 0.5 / 1.0 x ground truth: 20x20 patches of 139 events -23 / -19 / -13 % time,
-	// C3 -8.5 / -5.3 / +0.8 %, C2 -6.3 / -2.5 / -2.3 %, C4 -3.9 / -2.9 / -4.4 % (profiles/r03_eval3_waves4_ab.txt;
-	// 128 lanes x 19 KB: better still at small flows, +6 % at the ground truth of C3; 192 lanes x 31 KB:
-	// -2 ... -4 % everywhere at C3, but only -8 ... -11 % on the 20x20 patches).
-	const int nUnits = std::max(1, static_cast<int>(c->n_flows()));
-	const int regW = c->reg_rw, regH = c->reg_rh;
-	const bool smallCanvas = static_cast<size_t>(9) * regW * regH * sizeof(double) <= 32 * 1024;
-	const int manyBlock = smallCanvas ? 128 : 256;
-	int rc = image_capacity(c, L.cap_doubles, L.lds_bytes, nUnits < 1024 ? 40 : (smallCanvas ? 22 : 39));
-	if (rc)
-	{
-		return rc;
-	}
-	// Measured (tools/sweep_eval.py): one row band per unit is best at every batch size
-	// (each band workgroup pays the bounding-box pass over all events); with few units
-	// a 512-thread workgroup shortens the per-unit critical path (29 vs 46 us for one
-	// 64-patch window); with many units the smaller workgroups chosen above pack the CU better and
-	// waste fewer lanes in a unit's last round of events.  (The sums of a unit are reduced over the
-	// workgroup, so the two regimes differ in the last bits: a window is bit-identical alone
-	// and inside a batch as long as both are on the same side of 1024 units.)
-	L.block = static_cast<int>(ab_size("EBO_EVAL_BLOCK", nUnits < 1024 ? 512 : manyBlock));
-	if (L.block < 64 || L.block > 512 || (L.block & 63))
+	// Block, LDS per workgroup, header and capacity: the plan (eval_plan.h), from the geometry, the number of flow slots
+	// and the waves per CU the instantiation is compiled for -- never the data.  Many units: as many 128- or 256-lane
+	// workgroups per CU as fill every wave slot, the LDS divided among them.  Measured against three waves per SIMD with
+	// four 192-lane workgroups of 40 KB (round 2), evaluation with Jacobian at flows 0 / 0.5 / 1.0 x ground truth, seven
+	// workgroups of 22 KB: 20x20 patches of 139 events -23 / -19 / -13 % time, C3 -8.5 / -5.3 / +0.8 %, C2 -6.3 / -2.5 /
+	// -2.3 %, C4 -3.9 / -2.9 / -4.4 % (profiles/r03_eval3_waves4_ab.txt); eight of 20 KB: DESIGN.md 4.1 item 18.
+	// Few units: a 512-thread workgroup shortens the per-unit critical path (29 vs 46 us for one 64-patch window;
+	// tools/sweep_eval.py: one row band per unit is best at every batch size).  (The sums of a unit are reduced over the
+	// workgroup, so the two regimes differ in the last bits: a window is bit-identical alone and inside a batch as long
+	// as both are on the same side of 1024 units.)
+	L.c = make_consts(c);
+	ebo::EvalShape S;
+	S.reg_rw = c->reg_rw;
+	S.reg_rh = c->reg_rh;
+	S.max_rw = c->max_rw;
+	S.flow_slots = std::max(1, static_cast<int>(c->n_flows()));
+	S.lds_budget = kLdsBudget;
+	S.waves_per_cu = eval_variance_waves_per_cu(L.c);
+	S.block = static_cast<int>(ab_size("EBO_EVAL_BLOCK", 0));
+	S.lds_kb = ab_size("EBO_LDS_KB", 0);
+	if (S.block != 0 && (S.block < 64 || S.block > 512 || (S.block & 63)))
 	{
 		return c->fail(EBO_ERR_ARG, "EBO_EVAL_BLOCK must be a multiple of 64 in [64,512]");
 	}
+	const ebo::EvalPlan plan = ebo::plan_eval(S);
+	if (!plan.ok)
+	{
+		return c->fail(EBO_ERR_UNSUPPORTED, "patch too wide: one canvas row does not fit LDS");
+	}
+	L.block = plan.block;
+	L.lds_bytes = plan.lds_bytes;
+	L.cap_doubles = plan.cap_doubles;
+	L.header_waves = plan.header_waves;
+	L.groups_per_cu = plan.workgroups_per_cu;
 	int t = static_cast<int>(ab_size("EBO_EVAL_TILES", 0));
 	if (t <= 0)
 	{
@@ -1576,6 +1578,33 @@ int ebo_eval_launch_shape(ebo_ctx* c, int want_jac, int* tiles, int* block, int*
 		if (flow_sets) *flow_sets = L.flow_sets;
 	}
 	return rc;
+}
+
+int ebo_eval_resident_workgroups(ebo_ctx* c, int want_jac, int* planned, int* actual)
+{
+	if (!c)
+	{
+		return EBO_ERR_ARG;
+	}
+	if (c->n_windows == 0 || c->prm.loss != EBO_LOSS_VARIANCE)
+	{
+		return c->fail(EBO_ERR_STATE, "ebo_eval_resident_workgroups: needs loaded windows and the variance loss");
+	}
+	(void)hipSetDevice(c->prm.device);
+	EvalLaunch L;
+	int rc = eval_launch_shape(c, want_jac, L);
+	if (rc)
+	{
+		return rc;
+	}
+	int groups = 0;
+	if (eval_variance_resident(L, &groups))
+	{
+		return c->hip(hipGetLastError(), "k_eval3 occupancy");
+	}
+	if (planned) *planned = L.groups_per_cu;
+	if (actual) *actual = groups;
+	return EBO_OK;
 }
 
 int ebo_contrast_image(ebo_ctx* c, int window, int patch, const double* flow, int channels,

@@ -109,14 +109,15 @@ template <bool SMALL, bool D1S>
 __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, const Unit& u, double m0,
 											double m1, bool wantJac, int tile, int tiles,
 											int capDoubles, const EvalConsts& c, double* lds,
-											double (&S)[7], EvalReuse* ru = nullptr,
+											double (&S)[7], int hdrWaves, EvalReuse* ru = nullptr,
 											const int32_t* __restrict__ ext = nullptr,
 											[[maybe_unused]] unsigned int* boxStats = nullptr)
 {
 	EDGE_TICK_DECL;
+	// the header is sized for hdrWaves waves (eval_plan.h; uniform): the sums, block_minmax's scratch, then the image
 	double* red = lds;
-	int* ired = reinterpret_cast<int*>(lds + kRedDoubles);
-	double* img = lds + kLdsHeader;
+	int* ired = reinterpret_cast<int*>(lds + ebo::eval_sum_doubles(hdrWaves));
+	double* img = lds + ebo::eval_header_doubles(hdrWaves);
 	unsigned long long* imgq = reinterpret_cast<unsigned long long*>(img);
 	const int rx = u.rx, ry = u.ry, rw = u.rw, rh = u.rh;
 	const int W3 = 3 * rw, H3 = 3 * rh;
@@ -649,7 +650,7 @@ template <bool SMALL>
 __global__ void __launch_bounds__(512, SMALL ? 4 : 3) k_eval3(const uint64_t* __restrict__ events,
 												const Unit* __restrict__ units,
 												const double* __restrict__ flows, int tiles, int wantJac,
-												int capDoubles, double fdStep, double* __restrict__ partials,
+												int capDoubles, int hdrWaves, double fdStep, double* __restrict__ partials,
 												double* __restrict__ out, EvalConsts c,
 												const unsigned char* __restrict__ modes, LiveWindows live,
 												const uint32_t* __restrict__ order, BoxTable box)
@@ -707,8 +708,8 @@ __global__ void __launch_bounds__(512, SMALL ? 4 : 3) k_eval3(const uint64_t* __
 	double S[7];
 	// (the slot is the unit's, not the workgroup's: scalar address, scalar status)
 	const int32_t* ext = box.ext ? box.ext + static_cast<size_t>(unit) * kExtStride : nullptr;
-	eval_unit3<SMALL, true>(events + u.ev_off, u, m0, m1, wantJac != 0, tile, tiles, capDoubles, c, lds, S, nullptr, ext,
-							set == 0 ? box.stats : nullptr);
+	eval_unit3<SMALL, true>(events + u.ev_off, u, m0, m1, wantJac != 0, tile, tiles, capDoubles, c, lds, S, hdrWaves, nullptr,
+							ext, set == 0 ? box.stats : nullptr);
 	if (threadIdx.x == 0)
 	{
 		if (fused)

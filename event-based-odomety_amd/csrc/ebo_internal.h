@@ -140,6 +140,8 @@ struct EvalLaunch
 	int block;             // threads per workgroup
 	int cap_doubles;       // k_eval3: image capacity of one workgroup's LDS, in pixels
 	size_t lds_bytes;
+	int header_waves;      // k_eval3: waves the LDS header in front of the image is sized for (eval_plan.h)
+	int groups_per_cu;     // k_eval3: resident workgroups per CU the plan intends
 	double* d_partials;    // [flow sets][n_units][tiles][kPartialStride]
 	double* d_out;         // [n_flow][3]
 	double fd_step;        // > 0: combine as central differences
@@ -149,6 +151,10 @@ struct EvalLaunch
 	EvalConsts c;
 };
 int launch_eval_variance(const EvalLaunch& L, void* stream);
+// waves per CU the k_eval3 instantiation of these constants is compiled for, and the workgroups of L's block and LDS the
+// runtime keeps resident on one CU (c, block and lds_bytes are read)
+int eval_variance_waves_per_cu(const EvalConsts& c);
+int eval_variance_resident(const EvalLaunch& L, int* groups);
 // k_unit_extents over units [0, n_units): rewrites their slots of d_unit_ext from the resident events and units
 int launch_unit_extents(const uint64_t* d_events, const Unit* d_units, int n_units, int32_t* d_unit_ext, void* stream);
 int launch_dump_image(const EvalLaunch& L, int unit, double* d_image, void* stream);

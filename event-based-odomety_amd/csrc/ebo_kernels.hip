@@ -25,6 +25,7 @@
 
 #include "box_extents.h"
 #include "ebo_internal.h"
+#include "eval_plan.h"
 #include "exp_taps.h"
 
 namespace ebo
@@ -368,6 +369,10 @@ __device__ __forceinline__ void fd_offset(int set, double h, double& m0, double&
 // ===========================================================================
 constexpr int kRedDoubles = 128;  // 16 waves x 8
 constexpr int kLdsHeader = 160;   // red[128] + 32 doubles of int scratch
+// (k_eval3's header follows its workgroup's waves, eval_plan.h; this is the one of 16 waves, which k_solve_independent,
+// the dump kernel and the edge loss keep)
+static_assert(kRedDoubles == ebo::eval_sum_doubles(ebo::kEvalHeaderWavesMax) && kLdsHeader == ebo::eval_header_doubles(ebo::kEvalHeaderWavesMax),
+			  "eval_unit3's header of 16 waves is the shared one");
 
 __device__ __forceinline__ bool warp_event(uint64_t rec, int rx, int ry, int rw, int rh,
 											double m0, double m1, const EvalConsts& c, int& pxc,
@@ -587,7 +592,7 @@ __device__ __forceinline__ void eval_unit(const uint64_t* __restrict__ ev, const
 										   double& j0, double& j1, EvalReuse* ru, const int32_t* __restrict__ ext)
 {
 	double S[7];
-	eval_unit3<SMALL, false>(ev, u, m0, m1, wantJac, 0, 1, capDoubles, c, lds, S, ru, ext);  // (the gather forms D1: ebo_eval3.inc)
+	eval_unit3<SMALL, false>(ev, u, m0, m1, wantJac, 0, 1, capDoubles, c, lds, S, ebo::kEvalHeaderWavesMax, ru, ext);  // (the gather forms D1: ebo_eval3.inc)
 	j0 = 0.0;
 	j1 = 0.0;
 	variance_from_sums(S, wantJac, m0, m1, c.max_res, r, j0, j1);
@@ -1334,6 +1339,35 @@ int launch_unit_extents(const uint64_t* d_events, const Unit* d_units, int n_uni
 	return check_launch();
 }
 
+namespace
+{
+// the instantiation of k_eval3 a launch runs: sigma >= 1 (and not the A/B build's guarded biased form) takes <true>
+bool eval_variance_small(const EvalConsts& c)
+{
+	return c.inv_sigsq <= 1.0 && c.fix_form != kFixBiasedGuard;
+}
+auto eval_variance_kernel(const EvalConsts& c)
+{
+	return eval_variance_small(c) ? k_eval3<true> : k_eval3<false>;
+}
+}  // namespace
+
+int eval_variance_waves_per_cu(const EvalConsts& c)
+{
+	// __launch_bounds__(512, 4) / (512, 3): four resp. three waves on each of a CU's four SIMDs
+	return eval_variance_small(c) ? 16 : 12;
+}
+
+int eval_variance_resident(const EvalLaunch& L, int* groups)
+{
+	auto kern = eval_variance_kernel(L.c);
+	if (allow_big_lds(kern, L.lds_bytes))
+	{
+		return -2;
+	}
+	return hipOccupancyMaxActiveBlocksPerMultiprocessor(groups, kern, L.block, L.lds_bytes) == hipSuccess ? 0 : -2;
+}
+
 int launch_eval_variance(const EvalLaunch& L, void* stream)
 {
 	hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1346,7 +1380,7 @@ int launch_eval_variance(const EvalLaunch& L, void* stream)
 		return -2;  // no launch without the units' order table
 	}
 	const dim3 grid(L.n_units * L.tiles, L.flow_sets);
-	auto kern = (L.c.inv_sigsq <= 1.0 && L.c.fix_form != kFixBiasedGuard) ? k_eval3<true> : k_eval3<false>;
+	auto kern = eval_variance_kernel(L.c);
 	if (allow_big_lds(kern, L.lds_bytes))
 	{
 		return -2;
@@ -1358,7 +1392,7 @@ int launch_eval_variance(const EvalLaunch& L, void* stream)
 		live.n = 0;
 	}
 	hipLaunchKernelGGL(kern, live.n > 0 ? dim3(live.n * live.upw) : grid, dim3(L.block), L.lds_bytes, s, L.d_events, L.d_units,
-					   L.d_flows, L.tiles, L.channels == 3 ? 1 : 0, L.cap_doubles, L.fd_step,
+					   L.d_flows, L.tiles, L.channels == 3 ? 1 : 0, L.cap_doubles, L.header_waves, L.fd_step,
 					   L.d_partials, L.d_out, L.c, fusedPath ? L.d_modes : nullptr, live, L.d_order, L.box);
 	if (check_launch())
 	{

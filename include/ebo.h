@@ -473,6 +473,12 @@ int ebo_box_path_counts(ebo_ctx* ctx, unsigned int* from_events, unsigned int* f
  * null.  Launches nothing.  EBO_ERR_STATE with nothing loaded or the edge loss. */
 int ebo_eval_launch_shape(ebo_ctx* ctx, int want_jac, int* tiles, int* block, int* flow_sets);
 
+/* Diagnostic (tests/test_gpu_eval_residency.py): the workgroups of that launch one CU keeps resident -- *planned as the
+ * launch plan intends (csrc/eval_plan.h), *actual as the runtime's occupancy query answers for the kernel instantiation,
+ * the block and the dynamic LDS the launch would use.  Either pointer may be null.  Launches nothing.  Errors as
+ * ebo_eval_launch_shape. */
+int ebo_eval_resident_workgroups(ebo_ctx* ctx, int want_jac, int* planned, int* actual);
+
 /* Diagnostic (bench.py): the traffic of ebo_count_image_device with no work -- every packed event of the
  * loaded windows read once (16-byte loads), every pixel of d_image [Wn][image_h][image_w] written once
  * (16-byte stores, all 0.0) -- as the in-run yardstick of the HBM-bound count kernels: what a plain stream
