@@ -1084,6 +1084,18 @@ class Context:
         self._check(f(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def unit_deal(self, unit, d_flows, want_jac, d_out):
+        """diagnostic, A/B library only: the dealt list of one unit (index as in launch_order) in one variance evaluation
+        at the device flows d_flows into d_out -> np.uint16[events of the unit], empty where the unit is not dealt
+        (ebo.h: ebo_unit_deal)"""
+        f = lib().ebo_unit_deal
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        out = np.zeros(65536, dtype=np.uint16)
+        n = C.c_size_t()
+        self._check(f(self._h, int(unit), C.c_void_p(int(d_flows)), int(want_jac), C.c_void_p(int(d_out)), _vp(out),
+                      C.c_size_t(len(out)), C.byref(n)))
+        return out[:n.value].copy()
+
     def eval_launch_shape(self, want_jac=True):
         """diagnostic: (row tiles per unit, lanes per workgroup, flow sets) of the variance evaluation's launch"""
         v = [C.c_int() for _ in range(3)]

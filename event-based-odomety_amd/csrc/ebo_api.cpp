@@ -434,6 +434,10 @@ int run_eval_device(ebo_ctx* c, const double* d_flows, int want_jac, double* d_o
 	{
 		return rc;
 	}
+	const char* dealSwitch = ab_env("EBO_EVAL_DEAL");  // "0": every unit in the canonical order (eval_deal.h); read at every launch
+	L.box.deal_off = (dealSwitch && !std::strcmp(dealSwitch, "0")) ? 1 : 0;
+	L.box.deal_unit = c->deal_dump_unit;
+	L.box.deal_dump = c->deal_dump_unit >= 0 ? c->d_deal_dump.get() : nullptr;
 #endif
 	L.d_flows = d_flows;
 	rc = c->grow(c->d_partials, static_cast<size_t>(L.flow_sets) * L.n_units * L.tiles * kPartialStride, "hipMalloc partials");
@@ -1557,6 +1561,66 @@ int ebo_eval_device(ebo_ctx* c, const double* d_flows, int want_jac, double* d_o
 		return c->fail(EBO_ERR_ARG, "null device pointer");
 	}
 	return run_eval_device(c, d_flows, want_jac, d_out);
+}
+
+int ebo_unit_deal(ebo_ctx* c, int unit, const double* d_flows, int want_jac, double* d_out, uint16_t* out, size_t cap, size_t* n)
+{
+	if (!c)
+	{
+		return EBO_ERR_ARG;
+	}
+	if (c->capturing)
+	{
+		return c->fail(EBO_ERR_STATE, kNotWhileRecording);
+	}
+#ifdef EBO_AB
+	if (!d_flows || !d_out || !n || unit < 0 || static_cast<size_t>(unit) >= c->units.size())
+	{
+		return c->fail(EBO_ERR_ARG, "ebo_unit_deal: a null pointer or no such unit");
+	}
+	if (c->prm.loss == EBO_LOSS_EDGE)
+	{
+		return c->fail(EBO_ERR_STATE, "ebo_unit_deal: the variance evaluation only");
+	}
+	const size_t nEv = c->units[unit].n_ev;
+	*n = 0;
+	if (cap < nEv || (nEv && !out))
+	{
+		return c->fail(EBO_ERR_ARG, "ebo_unit_deal: the unit holds more events than cap");
+	}
+	int rc = c->grow(c->d_deal_dump, 1 + nEv, "hipMalloc deal read-back");
+	if (rc == EBO_OK)
+	{
+		rc = c->hip(hipMemsetAsync(c->d_deal_dump, 0, (1 + nEv) * sizeof(uint32_t), c->stream), "deal read-back");
+	}
+	if (rc == EBO_OK)
+	{
+		c->deal_dump_unit = unit;
+		rc = run_eval_device(c, d_flows, want_jac, d_out);
+		c->deal_dump_unit = -1;
+	}
+	std::vector<uint32_t> host(1 + nEv, 0u);
+	if (rc == EBO_OK)
+	{
+		rc = c->hip(hipStreamSynchronize(c->stream), "sync before the deal read-back");
+	}
+	if (rc == EBO_OK)
+	{
+		rc = c->hip(hipMemcpy(host.data(), c->d_deal_dump.get(), host.size() * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H dealt list");
+	}
+	if (rc == EBO_OK)
+	{
+		*n = host[0];
+		for (size_t q = 0; q < *n && q < nEv; ++q)
+		{
+			out[q] = static_cast<uint16_t>(host[1 + q]);
+		}
+	}
+	return rc;
+#else
+	(void)unit; (void)d_flows; (void)want_jac; (void)d_out; (void)out; (void)cap; (void)n;
+	return c->fail(EBO_ERR_STATE, "ebo_unit_deal: in the A/B build only");
+#endif
 }
 
 int ebo_eval_launch_shape(ebo_ctx* c, int want_jac, int* tiles, int* block, int* flow_sets)

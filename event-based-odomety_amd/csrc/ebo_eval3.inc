@@ -17,7 +17,8 @@
 // number.  Integer adds commute: the image, and with the fixed reduction order the whole result, is
 // bit-reproducible from run to run; it is also faster than ds_add_f64 under same-address conflicts
 // (tools/microbench/lds_atomics.hip); (c) the 7 taps of an axis come from 3 exps:
-// exp(hs (k-f)^2) = exp(hs k^2) exp(hs f^2) exp(f/s^2)^k.
+// exp(hs (k-f)^2) = exp(hs k^2) exp(hs f^2) exp(f/s^2)^k; (d) k_eval3 deals a unit's events once per evaluation so that
+// the lanes of one LDS instruction fall on different bank pairs (eval_deal.h; the block in front of the sub-band loop).
 //
 // What binds is the instruction count per tap (a straightforward version of this algorithm took ~1000
 // VALU instructions per event by its PMC profile), hence:
@@ -111,7 +112,8 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 											int capDoubles, const EvalConsts& c, double* lds,
 											double (&S)[7], int hdrWaves, EvalReuse* ru = nullptr,
 											const int32_t* __restrict__ ext = nullptr,
-											[[maybe_unused]] unsigned int* boxStats = nullptr)
+											[[maybe_unused]] unsigned int* boxStats = nullptr,
+											[[maybe_unused]] bool dealOff = false, [[maybe_unused]] uint32_t* dealDump = nullptr)
 {
 	EDGE_TICK_DECL;
 	// the header is sized for hdrWaves waves (eval_plan.h; uniform): the sums, block_minmax's scratch, then the image
@@ -143,6 +145,9 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 			recs[k] = (e < nEv) ? ev[e] : 0ull;
 		}
 	}
+	// D1S: the unit's dealt list (eval_deal.h), null until it is built and where the unit is not dealt; position q holds the
+	// canonical index of the event that lane q mod blockDim takes in round q div blockDim
+	[[maybe_unused]] const uint16_t* dlist = nullptr;
 	auto for_each_event = [&](auto&& body) {
 		if (cached)
 		{
@@ -159,7 +164,14 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 		{
 			for (uint32_t e = threadIdx.x; e < nEv; e += blockDim.x)
 			{
-				body(ev[e]);
+				if constexpr (D1S)
+				{
+					body(ev[dlist ? dlist[e] : e]);  // (uniform: the dealt list, once the unit has one)
+				}
+				else
+				{
+					body(ev[e]);
+				}
 			}
 		}
 	};
@@ -274,6 +286,124 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 	// (powers of two: the quotient is exact)
 	const double unX = subTaps ? 0x1p511 : 1.0;
 	const double unY = subTaps ? 1.0 / preY : 1.0;
+
+	// ---- the bank deal (k_eval3 only; eval_deal.h, DESIGN.md 4.1 item 19) ----
+	// Both tap passes below are bound by the LDS, and two thirds of its cycles are conflicts between the lanes of one
+	// instruction: in the canonical order the bank pairs of the lanes' first taps are random.  Once per evaluation the
+	// workgroup sorts its events by that bank pair (mod 16, relative to y0: a sub-band shifts every residue alike) and deals
+	// them so that the lanes of a 16-lane group hold different ones.  A counting sort with PRIVATE counters hist[key][lane]
+	// (plain read-modify-write by their owner) and an exclusive prefix in memory order: no atomic's return order decides
+	// anything, the order is unique.  The counters and the sorted indices live in the image, which is not zeroed yet; what
+	// survives is the list of 16-bit canonical indices at the END of the image area, behind the largest sub-band.  Image
+	// place, pitch and sub-bands are untouched, so the three value sums keep their bits; J changes by summation order only.
+	if constexpr (D1S)
+	{
+		const int B = blockDim.x;
+		bool deal = ebo::deal_admits(nEv, B, tiles) && ebo::deal_fits(nEv, B, capDoubles, min(maxRows, ty1 - ty0) * cols);
+#ifdef EBO_AB
+		deal = deal && !dealOff;
+		if (dealDump && threadIdx.x == 0)
+		{
+			dealDump[0] = deal ? nEv : 0u;  // ebo_unit_deal
+		}
+#endif
+		if (deal)
+		{
+			const int tid = threadIdx.x;
+			uint16_t* list = reinterpret_cast<uint16_t*>(img + (capDoubles - ebo::deal_list_doubles(nEv)));
+			uint32_t* hist = reinterpret_cast<uint32_t*>(img);
+			uint16_t* sorted = reinterpret_cast<uint16_t*>(img + ebo::deal_counter_doubles(B));
+			// (the box ended with a barrier on either path: block_minmax's scratch is free, and nothing has used the image yet)
+#pragma unroll
+			for (int k = 0; k < ebo::kDealKeys; ++k)
+			{
+				hist[k * B + tid] = 0u;
+			}
+			// the keys of the lane's events, 5 bits a round, and their counts
+			unsigned long long keys = 0ull;
+			{
+				int sh = 0;
+				for (uint32_t e = tid; e < nEv; e += B, sh += ebo::kDealKeyBits)
+				{
+					int pxc, pyc;
+					double fx, fy, tau;
+					uint32_t key = ebo::kDealGroup;
+					if (warp_event(ev[e], rx, ry, rw, rh, m0, m1, c, pxc, pyc, fx, fy, tau))
+					{
+						key = static_cast<uint32_t>(__mul24(pyc - 3 - y0, cols) + (pxc - 3 - x0)) & (ebo::kDealGroup - 1);
+					}
+					keys |= static_cast<unsigned long long>(key) << sh;
+					hist[key * B + tid] += 1u;
+				}
+			}
+			__syncthreads();
+			// exclusive prefix over the counters in memory order = (key, lane): thread t owns entries [17 t, 17 t + 17)
+			{
+				uint32_t v[ebo::kDealKeys];
+				uint32_t sum = 0u;
+#pragma unroll
+				for (int k = 0; k < ebo::kDealKeys; ++k)
+				{
+					v[k] = hist[tid * ebo::kDealKeys + k];
+					sum += v[k];
+				}
+				uint32_t incl = sum;
+#pragma unroll
+				for (int d = 1; d < 64; d <<= 1)
+				{
+					const uint32_t t = __shfl_up(incl, d, 64);
+					incl += ((tid & 63) >= d) ? t : 0u;
+				}
+				if ((tid & 63) == 63)
+				{
+					ired[tid >> 6] = static_cast<int>(incl);
+				}
+				__syncthreads();
+				uint32_t run = incl - sum;
+				for (int w = 0; w < (tid >> 6); ++w)
+				{
+					run += static_cast<uint32_t>(ired[w]);
+				}
+#pragma unroll
+				for (int k = 0; k < ebo::kDealKeys; ++k)
+				{
+					hist[tid * ebo::kDealKeys + k] = run;
+					run += v[k];
+				}
+			}
+			__syncthreads();
+			// place: the lane's events in round order, each at its (key, lane) counter
+			{
+				int sh = 0;
+				for (uint32_t e = tid; e < nEv; e += B, sh += ebo::kDealKeyBits)
+				{
+					const uint32_t key = static_cast<uint32_t>(keys >> sh) & 31u;
+					const uint32_t pos = hist[key * B + tid];
+					hist[key * B + tid] = pos + 1u;
+					sorted[pos] = static_cast<uint16_t>(e);
+				}
+			}
+			__syncthreads();
+			// the layout: position q = round * B + lane takes the round-th element of the lane's slot
+			{
+				uint32_t s = ebo::deal_start(tid, nEv, B);
+				for (uint32_t q = tid; q < nEv; q += B, ++s)
+				{
+					list[q] = sorted[s];
+				}
+			}
+			dlist = list;  // (visible behind the sub-band loop's first barrier, which also precedes the zeroing)
+#ifdef EBO_AB
+			if (dealDump)
+			{
+				for (uint32_t q = tid; q < nEv; q += B)  // (the positions the lane wrote itself)
+				{
+					dealDump[1 + q] = list[q];
+				}
+			}
+#endif
+		}
+	}
 
 	for (int sy0 = ty0; sy0 < ty1; sy0 += maxRows)
 	{
@@ -708,8 +838,14 @@ __global__ void __launch_bounds__(512, SMALL ? 4 : 3) k_eval3(const uint64_t* __
 	double S[7];
 	// (the slot is the unit's, not the workgroup's: scalar address, scalar status)
 	const int32_t* ext = box.ext ? box.ext + static_cast<size_t>(unit) * kExtStride : nullptr;
+#ifdef EBO_AB
 	eval_unit3<SMALL, true>(events + u.ev_off, u, m0, m1, wantJac != 0, tile, tiles, capDoubles, c, lds, S, hdrWaves, nullptr,
-							ext, set == 0 ? box.stats : nullptr);
+							ext, set == 0 ? box.stats : nullptr, box.deal_off != 0,
+							(set == 0 && unit == box.deal_unit) ? box.deal_dump : nullptr);
+#else
+	eval_unit3<SMALL, true>(events + u.ev_off, u, m0, m1, wantJac != 0, tile, tiles, capDoubles, c, lds, S, hdrWaves, nullptr,
+							ext);
+#endif
 	if (threadIdx.x == 0)
 	{
 		if (fused)

@@ -123,6 +123,11 @@ struct BoxTable
 {
 	const int32_t* ext = nullptr;   // [units][kExtStride], or null: every unit's box by the event pass (A/B: EBO_EVAL_BOX=events)
 	unsigned int* stats = nullptr;  // A/B build only: DEVICE counters [2] of ebo_box_path_counts, else null
+	// A/B build only, the bank deal of k_eval3 (eval_deal.h): EBO_EVAL_DEAL=0 evaluates every unit in the canonical order;
+	// ebo_unit_deal reads one unit's dealt list back ([0] its length, 0 where the unit is not dealt, then the list)
+	int deal_off = 0;
+	int deal_unit = -1;
+	uint32_t* deal_dump = nullptr;
 };
 
 // ---- launch wrappers implemented in ebo_kernels.hip (hipStream_t as void*) ----

@@ -25,6 +25,7 @@
 
 #include "box_extents.h"
 #include "ebo_internal.h"
+#include "eval_deal.h"
 #include "eval_plan.h"
 #include "exp_taps.h"
 

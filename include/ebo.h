@@ -468,6 +468,16 @@ int ebo_unit_extents(ebo_ctx* ctx, int32_t* out, size_t cap, size_t* n);
  * pointer may be null.  EBO_ERR_STATE in the shipped build and while a graph is being recorded.  Synchronous. */
 int ebo_box_path_counts(ebo_ctx* ctx, unsigned int* from_events, unsigned int* from_extents);
 
+/* Diagnostic, A/B build only (tests/test_gpu_eval_deal.py): the dealt list of ONE unit (index as in ebo_launch_order) --
+ * the order in which the variance evaluation's tap passes walk its events at the flows d_flows [slots][2] (device):
+ * entry q is the position, in the unit's canonical order (ebo_unit_records), of the event that lane q mod block takes in
+ * round q div block (csrc/eval_deal.h).  Runs one evaluation (want_jac as ebo_eval_device) into d_out [slots][3]
+ * (device).  *n receives the list's length: the unit's event count, or 0 where the unit is not dealt (inactive, outside
+ * the admission bounds, no room behind its image, EBO_EVAL_DEAL=0) -- it is then evaluated in the canonical order.
+ * EBO_ERR_ARG for a bad index, a null pointer or cap < the unit's event count; EBO_ERR_STATE in the shipped build, with the
+ * edge loss and while a graph is being recorded.  Synchronous. */
+int ebo_unit_deal(ebo_ctx* ctx, int unit, const double* d_flows, int want_jac, double* d_out, uint16_t* out, size_t cap, size_t* n);
+
 /* Diagnostic (same test): the shape ebo_eval / ebo_eval_device give the variance evaluation of the loaded units -- row
  * tiles per unit, lanes per workgroup, flow sets (5 with EBO_GRAD_CENTRAL and a Jacobian, else 1).  Any pointer may be
  * null.  Launches nothing.  EBO_ERR_STATE with nothing loaded or the edge loss. */
