@@ -118,6 +118,17 @@ int main()
 	}
 	// the headline's shape: 128 lanes, 2542 pixels -- a mean unit of 781 events leaves 2346 pixels to its image
 	CHECK(deal_fits(781, 128, 2542, 2346) && !deal_fits(781, 128, 2542, 2347), "the headline's capacity left");
+	// exact fits at the shipped capacities (eval_plan.h; tests/deal_fit_cases.py): both ends of the admitted counts at 2540
+	// (128 lanes), the upper end at 5080 (256 lanes), and the whole 90 x 66 canvas at its pitch of 91 in 6680, where the
+	// list alone is the boundary; one event more is one double of list more
+	CHECK(deal_admits(260, 128, 1) && deal_fits(260, 128, 2540, 45 * 55) && !deal_fits(261, 128, 2540, 45 * 55), "260 in 45 x 55");
+	CHECK(deal_fits(257, 128, 2540, 45 * 55) && !deal_fits(260, 128, 2540, 45 * 56), "the quad's first count; a row more");
+	CHECK(deal_admits(1536, 128, 1) && deal_fits(1536, 128, 2540, 49 * 44) && !deal_admits(1537, 128, 1), "1536 in 49 x 44");
+	CHECK(deal_admits(3072, 256, 1) && deal_fits(3072, 256, 5080, 77 * 56) && !deal_fits(3072, 256, 5080, 77 * 56 + 1), "3072 in 77 x 56");
+	CHECK(deal_fits(2696, 256, 6680, 91 * 66) && !deal_fits(2697, 256, 6680, 91 * 66), "the whole canvas at sigma < 1");
+	CHECK(deal_fits(820, 128, 3340, 55 * 57) && !deal_fits(820, 128, 3340, 55 * 58), "820 in 55 x 57 at 3340");
+	// two sub-bands: 2540 mod 91 = 83 doubles stay behind the 27 rows of a 91-pixel pitch
+	CHECK(deal_fits(332, 128, 2540, 27 * 91) && !deal_fits(333, 128, 2540, 27 * 91), "behind a full sub-band");
 	if (failures == 0)
 	{
 		std::printf("all passed\n");

@@ -14,7 +14,9 @@ the numpy restatement of warp_event and of the box rule (tools/ab/box_sizes.py),
 
 and every other unit sits at 0.5 x its ground truth.  Value and Jacobian against the oracle -- r at test_gpu_parity.py's
 rtol 1e-9 / atol 1e-12, J at jac_check.assert_jac_close's bounds -- and one window in a batch of its own (ten copies: 1080
-slots) against its bits inside the ten.  One oracle evaluation per window."""
+slots) against its bits inside the ten.  One oracle evaluation per window.  These units hold about 37 events, below the two
+full rounds the bank deal needs, so none of them is dealt: the dealt counterpart, boxes that leave exactly enough room for
+the list, lives in tests/test_gpu_eval_deal_fit.py."""
 import importlib.util
 import os
 
