@@ -1084,6 +1084,15 @@ class Context:
         self._check(f(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def interior_path_counts(self):
+        """diagnostic, A/B library only: units that took the all-interior path (csrc/eval_interior.h) in the last
+        variance evaluation"""
+        f = lib().ebo_interior_path_counts
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        a = C.c_uint()
+        self._check(f(self._h, C.byref(a)))
+        return a.value
+
     def unit_deal(self, unit, d_flows, want_jac, d_out):
         """diagnostic, A/B library only: the dealt list of one unit (index as in launch_order) in one variance evaluation
         at the device flows d_flows into d_out -> np.uint16[events of the unit], empty where the unit is not dealt

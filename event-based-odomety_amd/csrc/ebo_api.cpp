@@ -429,13 +429,15 @@ int run_eval_device(ebo_ctx* c, const double* d_flows, int want_jac, double* d_o
 	L.box.ext = ab_box_from_extents() ? c->d_unit_ext.get() : nullptr;
 #ifdef EBO_AB
 	L.box.stats = c->d_box_stats;
-	rc = c->hip(hipMemsetAsync(c->d_box_stats, 0, 2 * sizeof(unsigned int), c->stream), "box path counters");
+	rc = c->hip(hipMemsetAsync(c->d_box_stats, 0, kBoxStatInts * sizeof(unsigned int), c->stream), "box path counters");
 	if (rc)
 	{
 		return rc;
 	}
 	const char* dealSwitch = ab_env("EBO_EVAL_DEAL");  // "0": every unit in the canonical order (eval_deal.h); read at every launch
 	L.box.deal_off = (dealSwitch && !std::strcmp(dealSwitch, "0")) ? 1 : 0;
+	const char* interiorSwitch = ab_env("EBO_EVAL_INTERIOR");  // "0": every unit by the general path (eval_interior.h); read at every launch
+	L.box.interior_off = (interiorSwitch && !std::strcmp(interiorSwitch, "0")) ? 1 : 0;
 	L.box.deal_unit = c->deal_dump_unit;
 	L.box.deal_dump = c->deal_dump_unit >= 0 ? c->d_deal_dump.get() : nullptr;
 #endif
@@ -1394,8 +1396,8 @@ int ebo_create(const ebo_params* p, ebo_ctx** out)
 	if (rc == EBO_OK) rc = c->grow(c->d_unit_ext, nu * kExtStride, what);  // (likewise; all zero = no unit has a table)
 	if (rc == EBO_OK) rc = c->hip(hipMemset(c->d_unit_ext, 0, nu * kExtStride * sizeof(int32_t)), what);
 #ifdef EBO_AB
-	if (rc == EBO_OK) rc = c->grow(c->d_box_stats, 2, what);
-	if (rc == EBO_OK) rc = c->hip(hipMemset(c->d_box_stats, 0, 2 * sizeof(unsigned int)), what);
+	if (rc == EBO_OK) rc = c->grow(c->d_box_stats, kBoxStatInts, what);
+	if (rc == EBO_OK) rc = c->hip(hipMemset(c->d_box_stats, 0, kBoxStatInts * sizeof(unsigned int)), what);
 #endif
 	if (rc == EBO_OK) rc = c->grow(c->d_unit_maxdt, nu, what);
 	if (rc == EBO_OK) rc = c->grow(c->d_flows, nf * 2, what);

@@ -114,7 +114,7 @@ struct ebo_ctx
 	Dev<Unit> d_units;
 	Dev<uint32_t> d_order;  // [units] the order in which a launch hands them to workgroups, heaviest first (launch_order.h); rewritten by every load
 	Dev<int32_t> d_unit_ext;  // [units][kExtStride] per-column / per-row time extents behind k_eval3's bounding box (box_extents.h); sized once by ebo_create, rewritten by every load
-	Dev<unsigned int> d_box_stats;  // A/B build only: [2] units whose box came from the event pass / from the table in the last variance evaluation
+	Dev<unsigned int> d_box_stats;  // A/B build only: [kBoxStatInts] units whose box came from the event pass / from the table, and (64 counters) units that took the all-interior path, in the last variance evaluation
 	Dev<uint32_t> d_deal_dump;  // A/B build only: [1 + events of a unit] ebo_unit_deal's read-back of one unit's dealt list
 	int deal_dump_unit = -1;    // the unit the next variance evaluation dumps (inside ebo_unit_deal only)
 	Dev<int32_t> d_unit_maxdt;  // [units] max |t_ref(window) - t| over the unit's events (count kernels' displacement bound)

@@ -24,7 +24,8 @@
 // VALU instructions per event by its PMC profile), hence:
 //   * interior fast path: an event whose 7x7 footprint lies inside the band (almost all
 //     of them) runs unpredicated loops: per tap  v_mul_f64 + ds_add_u64
-//     with immediate offsets (scatter) /  ds_read_b64 + 2 v_fma_f64 (gather);
+//     with immediate offsets (scatter) /  ds_read_b64 + 2 v_fma_f64 (gather); in k_eval3 a unit whose every event is
+//     such an event, known from the box alone (eval_interior.h), runs its event loops without asking (INNER);
 //   * the fixed-point value is the bit pattern of the SUBNORMAL product of the two pre-scaled
 //     weights (value_tap): the exact product is rounded ONCE onto the 2^(k-52) grid.  Where the
 //     weights can be tiny (sigma < 1) it is  fma(wx, wy, bias): bias = 1.5 * 2^k has a zero low
@@ -113,7 +114,8 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 											double (&S)[7], int hdrWaves, EvalReuse* ru = nullptr,
 											const int32_t* __restrict__ ext = nullptr,
 											[[maybe_unused]] unsigned int* boxStats = nullptr,
-											[[maybe_unused]] bool dealOff = false, [[maybe_unused]] uint32_t* dealDump = nullptr)
+											[[maybe_unused]] bool dealOff = false, [[maybe_unused]] uint32_t* dealDump = nullptr,
+											[[maybe_unused]] bool interiorOff = false)
 {
 	EDGE_TICK_DECL;
 	// the header is sized for hdrWaves waves (eval_plan.h; uniform): the sums, block_minmax's scratch, then the image
@@ -181,6 +183,7 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 	const bool reuse = !D1S && ru && wantJac && ru->valid == 1.0 && __double_as_longlong(ru->m0) == __double_as_longlong(m0) &&
 					   __double_as_longlong(ru->m1) == __double_as_longlong(m1);
 	int xmin = 0x7fffffff, xmax = -0x7fffffff, ymin = 0x7fffffff, ymax = -0x7fffffff;
+	bool tabled = false;  // the box came from the extents table (uniform)
 	if (!reuse)
 	{
 	// The box from the unit's time extents where they give it exactly (box_extents.h, ebo_extents.inc; ext: the unit's
@@ -194,7 +197,7 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 	{
 		warm = ev[threadIdx.x];
 	}
-	const bool tabled = ext && box_from_extents(ext, rx, ry, rw, rh, m0, m1, c, xmin, xmax, ymin, ymax);
+	tabled = ext && box_from_extents(ext, rx, ry, rw, rh, m0, m1, c, xmin, xmax, ymin, ymax);
 	if (tabled)
 	{
 		asm volatile("" ::"v"(warm));
@@ -287,6 +290,37 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 	const double unX = subTaps ? 0x1p511 : 1.0;
 	const double unY = subTaps ? 1.0 / preY : 1.0;
 
+	// ---- all-interior units (k_eval3 only; eval_interior.h, DESIGN.md 4.1 item 20) ----
+	// Where the rule holds, warp_event rejects no event of the unit, the one sub-band's row test skips none and every
+	// footprint lies inside the image: the three event passes below run the statements of an accepted interior event
+	// without asking (INNER).  Uniform over the workgroup: scalars of the box alone.
+	bool allInterior = false;
+	if constexpr (D1S)
+	{
+		allInterior = ebo::unit_all_interior(tabled, tiles, xmin, xmax, ymin, ymax, rw, rh, rowsAll, maxRows);
+#ifdef EBO_AB
+		allInterior = allInterior && !interiorOff;
+		if (boxStats && allInterior && threadIdx.x == 0)
+		{
+			// ebo_interior_path_counts (tiles == 1: one workgroup per unit; its own line of kInteriorStatSlots)
+			atomicAdd(&boxStats[kInteriorStatStride * (1 + (blockIdx.x & (kInteriorStatSlots - 1)))], 1u);
+		}
+#endif
+	}
+	// a pass body takes INNER as a compile-time constant (as taps(form) takes the form): k_eval3 holds both variants of
+	// the three event loops behind this one uniform condition, every other caller the general one only
+	auto by_interior = [&](auto&& pass) {
+		if constexpr (D1S)
+		{
+			if (allInterior)
+			{
+				pass(std::true_type{});
+				return;
+			}
+		}
+		pass(std::false_type{});
+	};
+
 	// ---- the bank deal (k_eval3 only; eval_deal.h, DESIGN.md 4.1 item 19) ----
 	// Both tap passes below are bound by the LDS, and two thirds of its cycles are conflicts between the lanes of one
 	// instruction: in the canonical order the bank pairs of the lanes' first taps are random.  Once per evaluation the
@@ -321,21 +355,22 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 			}
 			// the keys of the lane's events, 5 bits a round, and their counts
 			unsigned long long keys = 0ull;
-			{
+			by_interior([&](auto inner) {
+				constexpr bool INNER = decltype(inner)::value;
 				int sh = 0;
 				for (uint32_t e = tid; e < nEv; e += B, sh += ebo::kDealKeyBits)
 				{
 					int pxc, pyc;
 					double fx, fy, tau;
 					uint32_t key = ebo::kDealGroup;
-					if (warp_event(ev[e], rx, ry, rw, rh, m0, m1, c, pxc, pyc, fx, fy, tau))
+					if (warp_event<INNER>(ev[e], rx, ry, rw, rh, m0, m1, c, pxc, pyc, fx, fy, tau))
 					{
 						key = static_cast<uint32_t>(__mul24(pyc - 3 - y0, cols) + (pxc - 3 - x0)) & (ebo::kDealGroup - 1);
 					}
 					keys |= static_cast<unsigned long long>(key) << sh;
 					hist[key * B + tid] += 1u;
 				}
-			}
+			});
 			__syncthreads();
 			// exclusive prefix over the counters in memory order = (key, lane): thread t owns entries [17 t, 17 t + 17)
 			{
@@ -424,15 +459,17 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 		if (!reuse)
 		{
 		double h3 = 0.0, h4 = 0.0;  // D1S: this sub-band's D1 sums
+		by_interior([&](auto inner) {
+		constexpr bool INNER = decltype(inner)::value;  // (all-interior unit: no event is rejected, skipped or clipped)
 		for_each_event([&](uint64_t rec) {
 			int pxc, pyc;
 			double fx, fy, tau;
-			if (!warp_event(rec, rx, ry, rw, rh, m0, m1, c, pxc, pyc, fx, fy, tau))
+			if (!warp_event<INNER>(rec, rx, ry, rw, rh, m0, m1, c, pxc, pyc, fx, fy, tau))
 			{
 				return;
 			}
 			const int rowLo = pyc - 3 - sy0;
-			if (rowLo + 6 < 0 || rowLo >= srows)
+			if (!INNER && (rowLo + 6 < 0 || rowLo >= srows))
 			{
 				return;
 			}
@@ -440,7 +477,7 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 			double wx[7], wy[7];
 			axis_taps3<SMALL>(fx, subTaps ? preX : c.norm, c, wx);
 			axis_taps3<SMALL>(fy, subTaps ? preY : 1.0, c, wy);
-			const bool interior = rowLo >= 0 && rowLo + 6 < srows && colLo >= 0 && colLo + 6 < bw;
+			const bool interior = INNER || (rowLo >= 0 && rowLo + 6 < srows && colLo >= 0 && colLo + 6 < bw);
 			if (D1S && wantJac)
 			{
 				// the sums of the weights and of the derivative weights over the taps this sub-band holds: the statements
@@ -543,6 +580,7 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 			taps(std::integral_constant<bool, subTaps>{});
 #endif
 		});
+		});
 		if (D1S && wantJac)
 		{
 			h3 = wave_sum(h3);
@@ -592,15 +630,17 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 		// ---- gather the derivative sums ----
 		[[maybe_unused]] double g3 = 0.0, g4 = 0.0;
 		double g5 = 0.0, g6 = 0.0;
+		by_interior([&](auto inner) {
+		constexpr bool INNER = decltype(inner)::value;
 		for_each_event([&](uint64_t rec) {
 			int pxc, pyc;
 			double fx, fy, tau;
-			if (!warp_event(rec, rx, ry, rw, rh, m0, m1, c, pxc, pyc, fx, fy, tau))
+			if (!warp_event<INNER>(rec, rx, ry, rw, rh, m0, m1, c, pxc, pyc, fx, fy, tau))
 			{
 				return;
 			}
 			const int rowLo = pyc - 3 - sy0;
-			if (rowLo + 6 < 0 || rowLo >= srows)
+			if (!INNER && (rowLo + 6 < 0 || rowLo >= srows))
 			{
 				return;
 			}
@@ -612,7 +652,7 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 			const double gfx = g * fx, gfy = g * fy;
 			double d2a = 0.0, d2b = 0.0;
 			[[maybe_unused]] double sumWy = 0.0, sumAy = 0.0, sumW = 0.0, sumA = 0.0;  // !D1S: the D1 sums are formed here
-			if (rowLo >= 0 && rowLo + 6 < srows && colLo >= 0 && colLo + 6 < bw)
+			if (INNER || (rowLo >= 0 && rowLo + 6 < srows && colLo >= 0 && colLo + 6 < bw))
 			{
 				// the seven x-derivative weights, as the clipped path below has them: 14 registers, which the kernel has
 				// since the D1 sums and their four accumulators left this pass (D1S); two fma per tap
@@ -710,6 +750,7 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 			}
 			g5 += d2a;
 			g6 += d2b;
+		});
 		});
 		if constexpr (!D1S)
 		{
@@ -841,7 +882,7 @@ __global__ void __launch_bounds__(512, SMALL ? 4 : 3) k_eval3(const uint64_t* __
 #ifdef EBO_AB
 	eval_unit3<SMALL, true>(events + u.ev_off, u, m0, m1, wantJac != 0, tile, tiles, capDoubles, c, lds, S, hdrWaves, nullptr,
 							ext, set == 0 ? box.stats : nullptr, box.deal_off != 0,
-							(set == 0 && unit == box.deal_unit) ? box.deal_dump : nullptr);
+							(set == 0 && unit == box.deal_unit) ? box.deal_dump : nullptr, box.interior_off != 0);
 #else
 	eval_unit3<SMALL, true>(events + u.ev_off, u, m0, m1, wantJac != 0, tile, tiles, capDoubles, c, lds, S, hdrWaves, nullptr,
 							ext);

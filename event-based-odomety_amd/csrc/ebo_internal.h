@@ -118,16 +118,25 @@ struct LiveWindows
 // Per-block partial sums of the variance objective: S1, S2, n, D1[2], D2[2], pad.
 static const int kPartialStride = 8;
 
+// A/B build only, the device counters of a variance evaluation: [0], [1] ebo_box_path_counts; ebo_interior_path_counts is
+// the sum of kInteriorStatSlots counters, one 64-byte line each, which the workgroups take by blockIdx -- one more atomic
+// per unit on ONE address costs the launch 10-20 ns a unit, more than the path it counts saves
+constexpr int kInteriorStatSlots = 64;
+constexpr int kInteriorStatStride = 16;
+constexpr int kBoxStatInts = kInteriorStatStride * (kInteriorStatSlots + 1);
+
 // The per-unit time-extent table of a load (box_extents.h), as an evaluation's launch sees it.
 struct BoxTable
 {
 	const int32_t* ext = nullptr;   // [units][kExtStride], or null: every unit's box by the event pass (A/B: EBO_EVAL_BOX=events)
-	unsigned int* stats = nullptr;  // A/B build only: DEVICE counters [2] of ebo_box_path_counts, else null
+	unsigned int* stats = nullptr;  // A/B build only: DEVICE counters [kBoxStatInts], else null
 	// A/B build only, the bank deal of k_eval3 (eval_deal.h): EBO_EVAL_DEAL=0 evaluates every unit in the canonical order;
 	// ebo_unit_deal reads one unit's dealt list back ([0] its length, 0 where the unit is not dealt, then the list)
 	int deal_off = 0;
 	int deal_unit = -1;
 	uint32_t* deal_dump = nullptr;
+	// A/B build only, k_eval3's all-interior path (eval_interior.h): EBO_EVAL_INTERIOR=0 evaluates every unit by the general path
+	int interior_off = 0;
 };
 
 // ---- launch wrappers implemented in ebo_kernels.hip (hipStream_t as void*) ----

@@ -26,6 +26,7 @@
 #include "box_extents.h"
 #include "ebo_internal.h"
 #include "eval_deal.h"
+#include "eval_interior.h"
 #include "eval_plan.h"
 #include "exp_taps.h"
 
@@ -375,6 +376,9 @@ constexpr int kLdsHeader = 160;   // red[128] + 32 doubles of int scratch
 static_assert(kRedDoubles == ebo::eval_sum_doubles(ebo::kEvalHeaderWavesMax) && kLdsHeader == ebo::eval_header_doubles(ebo::kEvalHeaderWavesMax),
 			  "eval_unit3's header of 16 waves is the shared one");
 
+// ACCEPTED: the caller knows that neither test rejects the event (eval_interior.h: every event of an all-interior
+// unit); the tests are then not compiled, the other statements are the same.
+template <bool ACCEPTED = false>
 __device__ __forceinline__ bool warp_event(uint64_t rec, int rx, int ry, int rw, int rh,
 											double m0, double m1, const EvalConsts& c, int& pxc,
 											int& pyc, double& fx, double& fy, double& tau)
@@ -384,7 +388,7 @@ __device__ __forceinline__ bool warp_event(uint64_t rec, int rx, int ry, int rw,
 	tau = static_cast<double>(dt) * c.scale;
 	const double cx = static_cast<double>(x) + tau * m0;  // not fused: -ffp-contract=off
 	const double cy = static_cast<double>(y) + tau * m1;
-	if (!convertible(cx) || !convertible(cy))
+	if (!ACCEPTED && (!convertible(cx) || !convertible(cy)))
 	{
 		return false;
 	}
@@ -392,7 +396,7 @@ __device__ __forceinline__ bool warp_event(uint64_t rec, int rx, int ry, int rw,
 	const int by = static_cast<int>(cy);
 	pxc = bx - rx + rw;  // canvas column / row of the centre tap
 	pyc = by - ry + rh;
-	if (pxc + 3 < 0 || pxc - 3 >= 3 * rw || pyc + 3 < 0 || pyc - 3 >= 3 * rh)
+	if (!ACCEPTED && (pxc + 3 < 0 || pxc - 3 >= 3 * rw || pyc + 3 < 0 || pyc - 3 >= 3 * rh))
 	{
 		return false;
 	}

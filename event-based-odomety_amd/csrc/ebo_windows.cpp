@@ -1024,4 +1024,35 @@ int ebo_box_path_counts(ebo_ctx* c, unsigned int* from_events, unsigned int* fro
 #endif
 }
 
+int ebo_interior_path_counts(ebo_ctx* c, unsigned int* interior)
+{
+	if (!c)
+	{
+		return EBO_ERR_ARG;
+	}
+	if (c->capturing)
+	{
+		return c->fail(EBO_ERR_STATE, kNotWhileRecording);
+	}
+#ifdef EBO_AB
+	unsigned int v[kBoxStatInts] = {};
+	(void)hipSetDevice(c->prm.device);
+	int rc = c->hip(hipStreamSynchronize(c->stream), "sync before the counter read-back");
+	if (rc == EBO_OK)
+	{
+		rc = c->hip(hipMemcpy(v, c->d_box_stats.get(), sizeof(v), hipMemcpyDeviceToHost), "D2H interior path counters");
+	}
+	unsigned int sum = 0;
+	for (int k = 1; k <= kInteriorStatSlots; ++k)
+	{
+		sum += v[kInteriorStatStride * k];
+	}
+	if (interior) *interior = sum;
+	return rc;
+#else
+	(void)interior;
+	return c->fail(EBO_ERR_STATE, "ebo_interior_path_counts: counted in the A/B build only");
+#endif
+}
+
 }  // extern "C"

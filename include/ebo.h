@@ -468,6 +468,13 @@ int ebo_unit_extents(ebo_ctx* ctx, int32_t* out, size_t cap, size_t* n);
  * pointer may be null.  EBO_ERR_STATE in the shipped build and while a graph is being recorded.  Synchronous. */
 int ebo_box_path_counts(ebo_ctx* ctx, unsigned int* from_events, unsigned int* from_extents);
 
+/* Diagnostic, A/B build only (tests/test_gpu_eval_interior.py): of the units the last ebo_eval / ebo_eval_device variance
+ * evaluation evaluated (first flow set), how many ran their event passes without the per-event reject, row and clip tests
+ * (csrc/eval_interior.h: box from the table, not cut by the canvas, one row tile, one sub-band); 0 with
+ * EBO_EVAL_INTERIOR=0.  The pointer may be null.  EBO_ERR_STATE in the shipped build and while a graph is being recorded.
+ * Synchronous. */
+int ebo_interior_path_counts(ebo_ctx* ctx, unsigned int* interior);
+
 /* Diagnostic, A/B build only (tests/test_gpu_eval_deal.py): the dealt list of ONE unit (index as in ebo_launch_order) --
  * the order in which the variance evaluation's tap passes walk its events at the flows d_flows [slots][2] (device):
  * entry q is the position, in the unit's canonical order (ebo_unit_records), of the event that lane q mod block takes in
