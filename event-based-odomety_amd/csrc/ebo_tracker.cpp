@@ -30,6 +30,21 @@ static int patch_integrate_common(ebo_ctx* c, const ebo_event* ev, const size_t*
 		return c->fail(EBO_ERR_ARG, "null mid_time/updated");
 	}
 	(void)hipSetDevice(c->prm.device);
+	// The kernel sizes its tile as int(w) x int(h) but admits an event while x < rx + w: a fractional size lets an event
+	// through at column int(w) (row int(h)), past the row (the tile).  The reference only builds whole sizes
+	// (Patch: 2 * extent + 1, patch.cpp:12, :58-62).  Refused before anything of the caller's is written.
+	for (int p = 0; p < n_patches; ++p)
+	{
+		const double rw = rects[4 * p + 2], rh = rects[4 * p + 3];
+		if (!std::isfinite(rw) || !std::isfinite(rh) || rw != std::floor(rw) || rh != std::floor(rh))
+		{
+			return c->fail(EBO_ERR_ARG, "patch rect width and height must be finite whole numbers");
+		}
+		if (!(rw >= 1.0) || !(rh >= 1.0) || rw * rh > 16384.0)
+		{
+			return c->fail(EBO_ERR_UNSUPPORTED, "patch image must have 1..16384 pixels");
+		}
+	}
 	const size_t e0 = offsets[0];
 	const size_t total = offsets[n_patches] - e0;
 	if (total >= (1ull << 32))
@@ -40,6 +55,7 @@ static int patch_integrate_common(ebo_ctx* c, const ebo_event* ev, const size_t*
 	std::vector<uint32_t> off32(n_patches + 1);
 	std::vector<double> tr(mc ? static_cast<size_t>(n_patches) * 4 : 0);
 	std::vector<uint64_t> noff(n_patches);
+	std::vector<std::pair<size_t, size_t>> spans(n_patches);  // [begin, end) of each image in nabla
 	size_t nablaEnd = 0;
 	for (int p = 0; p < n_patches; ++p)
 	{
@@ -50,13 +66,10 @@ static int patch_integrate_common(ebo_ctx* c, const ebo_event* ev, const size_t*
 		}
 		off32[p] = static_cast<uint32_t>(a - e0);
 		const double rw = rects[4 * p + 2], rh = rects[4 * p + 3];
-		const int cols = static_cast<int>(rw), rows = static_cast<int>(rh);
-		if (cols <= 0 || rows <= 0 || static_cast<size_t>(cols) * rows > 16384)
-		{
-			return c->fail(EBO_ERR_UNSUPPORTED, "patch image must have 1..16384 pixels");
-		}
+		const size_t pixels = static_cast<size_t>(rw) * static_cast<size_t>(rh);  // whole, 1..16384: checked above
 		noff[p] = nabla_offsets[p];
-		nablaEnd = std::max(nablaEnd, nabla_offsets[p] + static_cast<size_t>(cols) * rows);
+		nablaEnd = std::max(nablaEnd, nabla_offsets[p] + pixels);
+		spans[p] = {nabla_offsets[p], nabla_offsets[p] + pixels};
 		int64_t tref = 0;
 		bool pass = true;
 		if (mc)
@@ -108,6 +121,22 @@ static int patch_integrate_common(ebo_ctx* c, const ebo_event* ev, const size_t*
 		}
 	}
 	off32[n_patches] = static_cast<uint32_t>(total);
+	// The header promises an image at nabla + nabla_offsets[i] and nothing else: only the images travel, as the
+	// maximal runs of touching images (densely packed images, the usual case, are one run = one copy each way).
+	std::sort(spans.begin(), spans.end());
+	size_t nRuns = 0;
+	for (const auto& s : spans)
+	{
+		if (nRuns > 0 && s.first <= spans[nRuns - 1].second)
+		{
+			spans[nRuns - 1].second = std::max(spans[nRuns - 1].second, s.second);
+		}
+		else
+		{
+			spans[nRuns++] = s;
+		}
+	}
+	spans.resize(nRuns);
 	// staging layout: events | offsets | rects | traj | nabla offsets | nabla
 	auto align = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
 	const size_t bEv = align(total * 8), bOff = align(off32.size() * 4), bRect = align(static_cast<size_t>(n_patches) * 32);
@@ -131,9 +160,14 @@ static int patch_integrate_common(ebo_ctx* c, const ebo_event* ev, const size_t*
 	if (e == hipSuccess && mc) e = hipMemcpyAsync(dTraj, tr.data(), tr.size() * 8, hipMemcpyHostToDevice, c->stream);
 	if (e == hipSuccess) e = hipMemcpyAsync(dNoff, noff.data(), noff.size() * 8, hipMemcpyHostToDevice, c->stream);
 	// R6 leaves images of patches that fail the time test untouched: start from the caller's data
-	if (e == hipSuccess && mc) e = hipMemcpyAsync(dNabla, nabla, nablaEnd * 8, hipMemcpyHostToDevice, c->stream);
+	for (size_t r = 0; r < spans.size() && e == hipSuccess && mc; ++r)
+	{
+		e = hipMemcpyAsync(dNabla + spans[r].first * 8, nabla + spans[r].first, (spans[r].second - spans[r].first) * 8,
+						   hipMemcpyHostToDevice, c->stream);
+	}
 	if (e != hipSuccess)
 	{
+		(void)hipStreamSynchronize(c->stream);  // the copies read this call's vectors
 		return c->hip(e, "H2D patch data");
 	}
 	PatchIntLaunch L;
@@ -148,12 +182,13 @@ static int patch_integrate_common(ebo_ctx* c, const ebo_event* ev, const size_t*
 	{
 		return c->hip(hipGetLastError(), "patch integrate launch");
 	}
-	rc = c->hip(hipMemcpyAsync(nabla, dNabla, nablaEnd * 8, hipMemcpyDeviceToHost, c->stream), "D2H nabla");
-	if (rc)
+	for (size_t r = 0; r < spans.size() && e == hipSuccess; ++r)
 	{
-		return rc;
+		e = hipMemcpyAsync(nabla + spans[r].first, dNabla + spans[r].first * 8, (spans[r].second - spans[r].first) * 8,
+						   hipMemcpyDeviceToHost, c->stream);
 	}
-	return c->hip(hipStreamSynchronize(c->stream), "sync");
+	const hipError_t es = hipStreamSynchronize(c->stream);
+	return c->hip(e != hipSuccess ? e : es, "D2H nabla");
 }
 
 int ebo_route_set_events(ebo_ctx* c, const ebo_event* ev, size_t n)

@@ -597,7 +597,18 @@ int ebo_compensate_windows(ebo_ctx* ctx, const ebo_event* ev, const size_t* offs
  * ev[offsets[i]..offsets[i+1]) in deque order (front = newest), a cv::Rect2d
  * rects[i][4] = (x,y,w,h), and writes a [int(h)][int(w)] signed count image at
  * nabla + nabla_offsets[i].  For R6, traj[i][6] = (prelast x,y,t_us, last x,y,t_us)
- * and mid_time[i]; updated[i] tells whether R6's time test passed. */
+ * and mid_time[i]; updated[i] tells whether R6's time test passed.
+ * Rect sizes: w and h are whole numbers >= 1 with w * h <= 16384, as Patch builds them
+ * (2 * extent + 1); x and y may be fractional (updatePatchRect).  A w or h that is not finite
+ * or not whole returns EBO_ERR_ARG (the [int(h)][int(w)] image could not hold every event the
+ * rect contains); a whole one below 1, or w * h > 16384, returns EBO_ERR_UNSUPPORTED.  Every
+ * rect is checked before anything is written: on either error nabla, current_ts,
+ * time_last_update and updated are as the caller left them.
+ * Only the images are written: every word of nabla outside [nabla_offsets[i], nabla_offsets[i]
+ * + w * h) stays the caller's, whatever the order of the offsets and the gaps between them, and
+ * so does the image of a patch that fails R6's time test.  Images must not overlap.  Patch i
+ * without events (offsets[i] == offsets[i+1]) gets a zero image from ebo_patch_integrate and
+ * keeps its current_ts / time_last_update entry; R6 leaves it untouched with updated[i] = 0. */
 int ebo_patch_integrate(ebo_ctx* ctx, const ebo_event* ev, const size_t* offsets,
 						int n_patches, const double* rects, const size_t* nabla_offsets,
 						double* nabla, int64_t* current_ts, int64_t* time_last_update);

@@ -242,7 +242,8 @@ int orc_estimate_num_events(const double* grad, int img_w, int img_h, double rx,
 int orc_normalize_nabla(const double* nabla, int n, double* out);
 
 /* Patch::integrateEvents (patch.cpp:65-85). ev in deque order (front = newest).
- * nabla [int(rh)][int(rw)]. */
+ * nabla [int(rh)][int(rw)].  This and orc_patch_integrate_mc return -1 for an rw or rh that is
+ * not finite, not whole or below 1 (the image could not hold every event the rect contains). */
 int orc_patch_integrate(const orc_event* ev, size_t n, double rx, double ry,
 						double rw, double rh, double* nabla,
 						int64_t* current_ts, int64_t* time_last_update);

@@ -1828,13 +1828,24 @@ int orc_lm_powell(const orc_solver_opts* opts, double* x, double* trace, int cap
 	return 0;
 }
 
+// The two loops below index a [int(rh)][int(rw)] image with int(x - rx) for every x < rx + rw: a fractional width lets
+// x through at column int(rw), one past the row (past the caller's buffer in the last row); a fractional height does the
+// same one row further on.  Patch only builds whole sizes (2 * extent + 1, patch.cpp:12, :58-62), and
+// cv::Mat::zeros(height, width) would be overrun the same way: such a rect, and one that is not finite or below 1, is
+// refused.
+static bool patchSizeWhole(double rw, double rh)
+{
+	return std::isfinite(rw) && std::isfinite(rh) && rw == std::floor(rw) && rh == std::floor(rh) && rw >= 1.0 &&
+		   rh >= 1.0 && rw <= 2147483647.0 && rh <= 2147483647.0;
+}
+
 // patch.cpp:65-85.  cv::Rect2d::contains on the int point; frameToPatchCoords
 // (patch.cpp:184-189) converts (int - double) back to int by truncation.
 int orc_patch_integrate(const orc_event* ev, size_t n, double rx, double ry,
 						double rw, double rh, double* nabla,
 						int64_t* current_ts, int64_t* time_last_update)
 {
-	if (!ev || n == 0 || !nabla)
+	if (!ev || n == 0 || !nabla || !patchSizeWhole(rw, rh))
 	{
 		return -1;
 	}
@@ -1912,7 +1923,7 @@ int orc_patch_integrate_mc(const orc_event* ev, size_t n, double rx, double ry,
 						   int64_t last_t, int64_t mid_time, double* nabla,
 						   int32_t* updated)
 {
-	if (!nabla || !prelast_xy || !last_xy || !updated)
+	if (!nabla || !prelast_xy || !last_xy || !updated || !patchSizeWhole(rw, rh))
 	{
 		return -1;
 	}
