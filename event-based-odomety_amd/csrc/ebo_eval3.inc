@@ -24,7 +24,8 @@
 // VALU instructions per event by its PMC profile), hence:
 //   * interior fast path: an event whose 7x7 footprint lies inside the band (almost all
 //     of them) runs unpredicated loops: per tap  v_mul_f64 + ds_add_u64
-//     with immediate offsets (scatter) /  ds_read_b64 + 2 v_fma_f64 (gather); in k_eval3 a unit whose every event is
+//     with immediate offsets (scatter) /  ds_read_b64 + 2 v_fma_f64 (gather: the row's weighted sum and its first moment,
+//     tap_moments.h -- no derivative factor per tap); in k_eval3 a unit whose every event is
 //     such an event, known from the box alone (eval_interior.h), runs its event loops without asking (INNER);
 //   * the fixed-point value is the bit pattern of the SUBNORMAL product of the two pre-scaled
 //     weights (value_tap): the exact product is rounded ONCE onto the 2^(k-52) grid.  Where the
@@ -36,17 +37,19 @@
 // SMALL (sigma >= 1): hs f^2 lies in [-0.5, 0] and |a| <= 1 (|f| < 1), the ranges of exp_taps.h's polynomials; exp(a)
 // and exp(-a) come as a pair from one cosh / sinh evaluation.
 template <bool SMALL>
-__device__ __forceinline__ void axis_taps3(double f, double pre, const EvalConsts& c, double (&w)[7])
+__device__ __forceinline__ void axis_taps3(double f, double pre, const EvalConsts& c, double hsQ, double isQ, double (&w)[7])
 {
-	const double a = f * c.inv_sigsq;
-	const double e0 = pre * (SMALL ? exp_gauss(c.hs * (f * f)) : exp(c.hs * (f * f)));
+	// SMALL: the polynomials' quarter arguments straight from the quarter constants (exact: powers of two), one
+	// multiply less per exponential and per pair
+	const double e0 = pre * (SMALL ? exp_gauss_quarter(hsQ * (f * f)) : exp(c.hs * (f * f)));
 	double p, q;
 	if (SMALL)
 	{
-		exp_pair(a, p, q);
+		exp_pair_quarter(f * isQ, p, q);
 	}
 	else
 	{
+		const double a = f * c.inv_sigsq;
 		p = exp(a);
 		q = exp(-a);
 	}
@@ -101,8 +104,8 @@ struct EvalReuse
 
 // D1S: which pass forms the image-free Jacobian sums D1k (S[3], S[4]).  They need the weights only, so either pass
 // can.  k_eval3 forms them in the scatter (D1S = true; only where wantJac is set): that takes the four sums and their
-// two accumulators, 12 registers live across the gather's rows, out of the pass that needs registers for its table of
-// derivative weights (measured, DESIGN.md 4.1 item 16: the move alone costs 1 %, the table without the move 1.5 %,
+// two accumulators, 12 registers live across the gather's rows, out of the pass that needs registers for its rows
+// (measured, DESIGN.md 4.1 item 16: the move alone costs 1 %, the gather's table without the move 1.5 %,
 // both together nothing, and they leave the registers the cheaper exponentials need).  k_solve_independent keeps them
 // in the gather (D1S = false): an EvalReuse hit runs no scatter.  Same operations on the same operands in the same order
 // either way (the scatter's weights carry exact power-of-two prefactors in the subnormal form, taken off each sum
@@ -289,6 +292,10 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 	// (powers of two: the quotient is exact)
 	const double unX = subTaps ? 0x1p511 : 1.0;
 	const double unY = subTaps ? 1.0 / preY : 1.0;
+	// SMALL: the quarter arguments' constants (exact: powers of two), formed once per unit into two uniform register pairs.
+	// As two more kernel-argument doubles they cost scalar spills instead (k_eval3<true> 12 -> 17, k_solve_independent<true>
+	// 92 -> 103) and the c4 solve 1.5 % (measured, DESIGN.md 4.1 item 21).
+	const double hsQ = c.hs * 0.25, isQ = c.inv_sigsq * 0.25;
 
 	// ---- all-interior units (k_eval3 only; eval_interior.h, DESIGN.md 4.1 item 20) ----
 	// Where the rule holds, warp_event rejects no event of the unit, the one sub-band's row test skips none and every
@@ -475,34 +482,24 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 			}
 			const int colLo = pxc - 3 - x0;
 			double wx[7], wy[7];
-			axis_taps3<SMALL>(fx, subTaps ? preX : c.norm, c, wx);
-			axis_taps3<SMALL>(fy, subTaps ? preY : 1.0, c, wy);
+			axis_taps3<SMALL>(fx, subTaps ? preX : c.norm, c, hsQ, isQ, wx);
+			axis_taps3<SMALL>(fy, subTaps ? preY : 1.0, c, hsQ, isQ, wy);
 			const bool interior = INNER || (rowLo >= 0 && rowLo + 6 < srows && colLo >= 0 && colLo + 6 < bw);
 			if (D1S && wantJac)
 			{
 				// the sums of the weights and of the derivative weights over the taps this sub-band holds: the statements
 				// of the gather's two paths (below, !D1S), on weights that may carry the prefactors
 				const double g = tau * c.inv_sigsq;
-				const double gfx = g * fx, gfy = g * fy;
 				double sumWy = 0.0, sumAy = 0.0, sumW = 0.0, sumA = 0.0;
 				if (interior)
 				{
-#pragma unroll
-					for (int i = 0; i < 7; ++i)
-					{
-						sumW += wx[i];
-						sumA = fma(wx[i], fma(g, static_cast<double>(i - 3), -gfx), sumA);
-					}
-#pragma unroll
-					for (int j = 0; j < 7; ++j)
-					{
-						const double ay = wy[j] * fma(g, static_cast<double>(j - 3), -gfy);
-						sumWy += wy[j];
-						sumAy += ay;
-					}
+					// whole footprint: the derivative sums from the weights' first moments (tap_moments.h)
+					ebo::axis_d1(wx, g, fx, sumW, sumA);
+					ebo::axis_d1(wy, g, fy, sumWy, sumAy);
 				}
 				else
 				{
+					const double gfx = g * fx, gfy = g * fy;
 #pragma unroll
 					for (int i = 0; i < 7; ++i)
 					{
@@ -646,33 +643,28 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 			}
 			const int colLo = pxc - 3 - x0;
 			double wx[7], wy[7];
-			axis_taps3<SMALL>(fx, c.norm, c, wx);
-			axis_taps3<SMALL>(fy, 1.0, c, wy);
+			axis_taps3<SMALL>(fx, c.norm, c, hsQ, isQ, wx);
+			axis_taps3<SMALL>(fy, 1.0, c, hsQ, isQ, wy);
 			const double g = tau * c.inv_sigsq;
-			const double gfx = g * fx, gfy = g * fy;
 			double d2a = 0.0, d2b = 0.0;
 			[[maybe_unused]] double sumWy = 0.0, sumAy = 0.0, sumW = 0.0, sumA = 0.0;  // !D1S: the D1 sums are formed here
 			if (INNER || (rowLo >= 0 && rowLo + 6 < srows && colLo >= 0 && colLo + 6 < bw))
 			{
-				// the seven x-derivative weights, as the clipped path below has them: 14 registers, which the kernel has
-				// since the D1 sums and their four accumulators left this pass (D1S); two fma per tap
-				double ax[7];
-#pragma unroll
-				for (int i = 0; i < 7; ++i)
+				// moment form (tap_moments.h): no derivative factor per tap; four moment weights for the x axis, none for y.
+				// Per row 13 operations for rb and rc, then A, B and C; g, fx and fy come in once, behind the rows.
+				if constexpr (!D1S)
 				{
-					const double ci = fma(g, static_cast<double>(i - 3), -gfx);
-					ax[i] = wx[i] * ci;
-					if constexpr (!D1S)
-					{
-						sumW += wx[i];
-						sumA = fma(wx[i], ci, sumA);
-					}
+					ebo::axis_d1(wx, g, fx, sumW, sumA);
+					ebo::axis_d1(wy, g, fy, sumWy, sumAy);
 				}
+				double kx[4];
+				ebo::moment_table(wx, kx);
+				double mA = 0.0, mB = 0.0, mC = 0.0;
 				const double* rowp = img + __mul24(rowLo, cols) + colLo;
-#pragma unroll
-				for (int j = 0; j < 7; ++j)
-				{
-					// rb = sum_i wx_i I_i, ra = sum_i ax_i I_i
+				// (the row index as a compile-time constant, seven calls: as an unrolled loop over j with a run-time argument
+				// the same statements put k_eval3<true> at 26 spilled vector registers and 200 B of scratch, and the gate refuses it)
+				auto row = [&](auto jc) {
+					constexpr int J = decltype(jc)::value;
 					double v[7];
 #pragma unroll
 					for (int i = 0; i < 7; ++i)
@@ -680,26 +672,23 @@ __device__ __forceinline__ void eval_unit3(const uint64_t* __restrict__ ev, cons
 						v[i] = lds_ld(rowp + i);  // the row's seven reads back to back, then the arithmetic (measured: within
 												  // 0.5 % of reads interleaved with the arithmetic -- the pass is throughput-bound)
 					}
-					double rb = wx[0] * v[0], ra = ax[0] * v[0];
-#pragma unroll
-					for (int i = 1; i < 7; ++i)
-					{
-						rb = fma(wx[i], v[i], rb);
-						ra = fma(ax[i], v[i], ra);
-					}
-					const double ay = wy[j] * fma(g, static_cast<double>(j - 3), -gfy);
-					if constexpr (!D1S)
-					{
-						sumWy += wy[j];
-						sumAy += ay;
-					}
-					d2a = fma(wy[j], ra, d2a);
-					d2b = fma(ay, rb, d2b);
+					double rb, rc;
+					ebo::moment_row(wx, kx, v, rb, rc);
+					ebo::moment_acc<J>(wy[J], rb, rc, mA, mB, mC);
 					rowp += cols;
-				}
+				};
+				row(std::integral_constant<int, 0>{});
+				row(std::integral_constant<int, 1>{});
+				row(std::integral_constant<int, 2>{});
+				row(std::integral_constant<int, 3>{});
+				row(std::integral_constant<int, 4>{});
+				row(std::integral_constant<int, 5>{});
+				row(std::integral_constant<int, 6>{});
+				ebo::moment_d2(g, fx, fy, mA, mB, mC, d2a, d2b);
 			}
 			else
 			{
+				const double gfx = g * fx, gfy = g * fy;
 				double ax[7];
 				int ci[7];
 #pragma unroll
@@ -815,7 +804,7 @@ template <bool SMALL>
 // 4-5 % -- but only without spills: the first attempt (round 1) spilled inside the tap loops and was 8x slower.
 // What fits the kernel into 128 registers: the seven sums live in per-wave LDS slots instead of registers
 // across the passes, the box and everything derived from it are scalars (readfirstlane), and the D1 sums are
-// formed in the scatter pass, which leaves the gather room for its table of seven x-derivative weights (D1S).
+// formed in the scatter pass (D1S), and the gather holds four moment weights instead of seven derivative weights (tap_moments.h).
 // The sigma < 1 instantiation (library exp, the one-step floor of fix_tap) is
 // given three waves per SIMD: at four it spills a register.  It is not the reference's sigma.
 __global__ void __launch_bounds__(512, SMALL ? 4 : 3) k_eval3(const uint64_t* __restrict__ events,

@@ -29,6 +29,7 @@
 #include "eval_interior.h"
 #include "eval_plan.h"
 #include "exp_taps.h"
+#include "tap_moments.h"
 
 namespace ebo
 {

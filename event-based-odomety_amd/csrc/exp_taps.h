@@ -28,10 +28,11 @@
 
 namespace ebo
 {
-// p = exp(a), q = exp(-a) for |a| <= 1.
-EBO_EXP_FN void exp_pair(double a, double& p, double& q)
+// p = exp(4 t), q = exp(-4 t) for |t| <= 0.25: exp_pair behind its first multiply.  A caller whose argument is a
+// product with a constant folds the quarter into the constant: f * (k / 4) has the bits of (f * k) / 4, a division by
+// four being exact short of underflow (and there both are below every term the polynomials keep).
+EBO_EXP_FN void exp_pair_quarter(double t, double& p, double& q)
 {
-	const double t = a * 0.25;
 	const double u = t * t;
 	double c = 1.0 / 479001600.0;                // 1/12!
 	c = __builtin_fma(c, u, 1.0 / 3628800.0);    // 1/10!
@@ -55,10 +56,15 @@ EBO_EXP_FN void exp_pair(double a, double& p, double& q)
 	q = q * q;
 }
 
-// exp(x) for -0.5 <= x <= 0.
-EBO_EXP_FN double exp_gauss(double x)
+// p = exp(a), q = exp(-a) for |a| <= 1.
+EBO_EXP_FN void exp_pair(double a, double& p, double& q)
 {
-	const double t = x * 0.25;
+	exp_pair_quarter(a * 0.25, p, q);
+}
+
+// exp(4 t) for -0.125 <= t <= 0: exp_gauss behind its first multiply (as exp_pair_quarter).
+EBO_EXP_FN double exp_gauss_quarter(double t)
+{
 	double p = 1.0 / 39916800.0;                 // 1/11!
 	p = __builtin_fma(p, t, 1.0 / 3628800.0);
 	p = __builtin_fma(p, t, 1.0 / 362880.0);
@@ -73,5 +79,11 @@ EBO_EXP_FN double exp_gauss(double x)
 	p = __builtin_fma(p, t, 1.0);
 	p = p * p;
 	return p * p;
+}
+
+// exp(x) for -0.5 <= x <= 0.
+EBO_EXP_FN double exp_gauss(double x)
+{
+	return exp_gauss_quarter(x * 0.25);
 }
 }  // namespace ebo
